@@ -12,9 +12,14 @@ SAME rounds are used at every N: they are sharded 1024 / N per GPU ("scaling": "
 Inputs are produced by SIMULATION, not drawn from a distribution: during the untimed set-up the
 swarm is flown in closed loop with the device solver from round 0; the inputs of rounds
 [--first-round - warmup, --first-round + steps) are kept resident in HBM and replayed, one recorded round per step. The
-TIMED rounds are [--first-round, --first-round + steps) whatever --warmup is. Default --first-round 165: the rounds in
+TIMED rounds are [--first-round, --first-round + steps) whatever --warmup is; beyond WINDOW_MAX steps the WINDOW_MAX recorded
+rounds are replayed cyclically, so that the set-up does not grow with --steps. Default --first-round 165: the rounds in
 which the contracting ring reaches the 0.5 m separation limit (from round 167 on, root relaxations turn infeasible by the
 hundred: 286 of 1024 instances in round 173; the caller's shift fallback handles them) — the hard part of the flight.
+
+A plain run sets up, warms up, times the --steps steps once and prints the line; the passes that need runs of their own (event
+pass, CPU baselines and parity, device-resident loop, secondary workloads, ...) run with --full. --dump-outputs DIR writes what the
+last timed step returned.
 
 Prints ONE JSON line (rank 0). `roofline.achieved` = algorithmic bytes per launch (SURVEY.md section 8d formula x agents
 per launch) / mean kernel duration measured with HIP events on the launch stream. `roofline.after_prefilter` prices the
@@ -22,6 +27,7 @@ same launches by the bytes the kernel really has to touch once the sphere prefil
 (32-B sphere record per neighbour + 24 B per surviving (neighbour, step) pair, counted by the kernel itself).
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -33,6 +39,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
+# Distinct recorded rounds the timed steps replay, cyclically beyond it. Each recorded round costs ~9 ms of set-up flight and ~4 MB of
+# inputs (host and HBM) against ~0.1 ms per timed step; 200 rounds cover the squeeze of the default line and stop before the swarm
+# gridlocks (by round 1164, half of the instances have no solution and a step takes ~1 ms).
+WINDOW_MAX = 200
 
 
 def algorithmic_bytes(n_rob, N, P, rbar):
@@ -47,7 +57,6 @@ def workload_key(scenario, n_rob, N, world, first, K):
 
 def kernel_source_sha16():
     """Identity of the solver kernel's sources: a committed PMC summary is quoted only for the sources it was taken on."""
-    import hashlib
     h = hashlib.sha256()
     for f in ("hdsm_core.h", "hdsm_wave_gi.h", "hdsm_wave_gib.h", "hdsm_api.hip", "hdsm_types.h"):
         h.update(open(os.path.join(ROOT, "multi_agent_pkgs_amd", "csrc", f), "rb").read())
@@ -84,7 +93,8 @@ def main():
                     "forest (plumbing check). The last three are single-GPU workloads.")
     ap.add_argument("--radius", type=float, default=0.0, help="circle radius [m], default max(22, agents / 2 pi)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="wall-clock budget of the CPU baseline leg")
-    ap.add_argument("--repeats", type=int, default=3, help="repetitions of the (warm-up + timed) region; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the (warm-up + timed) region; the median is reported "
+                    "(default: 1, with --full 3)")
     ap.add_argument("--mip-gap", type=float, default=0.0, help="hdsm_params.mip_gap (0 = exact, the default; the reference runs "
                     "Gurobi at its default MIPGap 1e-4)")
     ap.add_argument("--time-limit-s", type=float, default=0.0, help="hdsm_params.time_limit_s (0 = none; AC:952 sets 0.08)")
@@ -105,20 +115,32 @@ def main():
                     "RCCL linked into libhdsm.so). gloo: testing the multi-rank flow on a box with fewer GPUs than ranks "
                     "(ranks share devices, the all-gather is staged through the host)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short windows of BASELINE configs[2] (forest) and configs[4] (forest + wall "
-                    "+ forest, H = 15) that the default single-GPU circle run appends as secondary_workloads")
+                    "+ forest, H = 15) that a --full single-GPU circle run appends as secondary_workloads")
     ap.add_argument("--no-weak-record", action="store_true", help="N > 1: skip the secondary weak-scaling record (1024 agents "
                     "per GPU)")
     ap.add_argument("--parity-sample", type=int, default=0, help="after the timed region, replay the timed rounds once more, download the "
                     "device answers and compare this many random instances per round (plus the instances that ended on a budget, up to "
                     "8 per round) with the CPU oracle -> parity_on_timed_rounds (what the secondary workloads of the default line run with; "
-                    "the default circle line compares EVERY timed instance in its cpu_baseline leg instead)")
+                    "a --full circle line compares EVERY timed instance in its cpu_baseline leg instead)")
     ap.add_argument("--parity-seconds", type=float, default=40.0, help="wall-clock budget of the --parity-sample pass (rounds beyond it are skipped)")
     ap.add_argument("--device-loop", action="store_true", help="run the device-resident-loop pass (hdsm_dswarm_round live, with its per-phase "
                     "HIP-event shares and, in obstacle worlds, a bounded orc_safe_corridor comparison) even with --no-event-pass: what the "
-                    "forest / fwf secondary records of the default line carry")
+                    "forest / fwf secondary records of a --full line carry")
     ap.add_argument("--second-window", type=int, default=-1, help="first round of a second timed window recorded in the same set-up flight "
-                    "(default: 100 for the 1024-agent circle line - rounds in which every instance has a solution - else none; 0 = none)")
+                    "(default with --full: 100 for the 1024-agent circle line - rounds in which every instance has a solution - else none; 0 = none)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure as well: the event pass (kernel_ms_*, solve "
+                    "latency, roofline on the kernel alone), host-buffer and single-instance calls, device-resident loop, CPU baselines with "
+                    "their parity check, second window, secondary workloads, three repeats and, N > 1, exchange timing and weak-scaling record. "
+                    "Without it a run sets up, warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step returned "
+                    "(traj, ctrl, used, status, obj of every agent) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if not args.full:   # a plain run: nothing that needs runs of its own besides the timed steps
+        args.no_event_pass = args.no_cpu_baseline = args.no_secondary = args.no_weak_record = True
+        if args.second_window < 0:
+            args.second_window = 0
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
 
@@ -159,15 +181,16 @@ def main():
     first, n_local = swarm.shard_range(n_rob, rank, world)
     per = (n_rob + world - 1) // world
     K, W = args.steps, args.warmup
+    R = min(K, WINDOW_MAX)   # distinct recorded rounds; timed step i replays the (i mod R)-th
     first_round = args.first_round if args.first_round >= 0 else (165 if (args.scenario == "circle" and n_rob == 1024 and N == 10) else 25)
     W = min(W, first_round)
-    rec_from, rec_to = first_round - W, first_round + K   # recorded rounds [rec_from, rec_to)
+    rec_from, rec_to = first_round - W, first_round + R   # recorded rounds [rec_from, rec_to)
     key = workload_key(args.scenario, n_rob, N, world, first_round, K)
     # a second timed window of the same flight (the default line only): rounds before the squeeze, every instance has a solution
     first2 = args.second_window if args.second_window >= 0 else (100 if (args.scenario == "circle" and n_rob == 1024 and N == 10 and first_round == 165) else 0)
-    if first2 <= 0 or first2 + K > rec_from or first2 < W or args.load_recording:
+    if first2 <= 0 or first2 + R > rec_from or first2 < W or args.load_recording:
         first2 = 0
-    rec2_from, rec2_to = first2 - W, first2 + K
+    rec2_from, rec2_to = first2 - W, first2 + R
 
     solver = lib.Solver(prm, max(n_local, 1), max(n_rob, world * per), device=dev.index)
     stream = torch.cuda.current_stream()
@@ -272,7 +295,7 @@ def main():
         if world_occ is not None:
             unrouted = loop.set_world(world_occ, world_origin, route=args.scenario != "lanes")
             assert unrouted == 0
-        rec, rec2, fails, fails_timed, fails2 = [], [], 0, 0, 0
+        rec, rec2, fails, fails2, fails_round, limits_round = [], [], 0, 0, [], []
         t_setup = time.perf_counter()
         for r in range(rec_to):
             out = loop.step(record=rec if r >= rec_from else (rec2 if first2 and rec2_from <= r < rec2_to else None))
@@ -281,9 +304,11 @@ def main():
             if r >= rec_from:
                 fails += int((out["status"] == 2).sum())
             if r >= first_round:
-                fails_timed += int((out["status"] == 2).sum())
-                limits_timed += int((out["status"] == 1).sum())
+                fails_round.append(int((out["status"] == 2).sum()))
+                limits_round.append(int((out["status"] == 1).sum()))
         t_setup = time.perf_counter() - t_setup
+        fails_timed = sum(fails_round[i % R] for i in range(K))
+        limits_timed = sum(limits_round[i % R] for i in range(K))
         if args.save_recording:
             np.savez(args.save_recording, fails=fails, fails_timed=fails_timed, **{k: np.stack([x[k] for x in rec]) for k in rec_keys})
     if world > 1:
@@ -340,8 +365,8 @@ def main():
             step(r, win)
         barrier()
         t0 = time.perf_counter()
-        for r in range(W, W + K):
-            step(r, win)
+        for i in range(K):
+            step(W + i % R, win)
         barrier()
         own = time.perf_counter() - t0
         el = own
@@ -355,7 +380,15 @@ def main():
     # W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, max over the ranks. The
     # region (warm-up included, so every repetition replays the same sequence of warm-start states) is run --repeats times
     # and the line carries the MEDIAN repetition; all of them are listed in "ms_per_step_repeats". One repetition is what the
-    # contract describes; the others only guard the line against a one-off stall of the box.
+    # contract describes (a plain run makes one); the others only guard the line against a one-off stall of the box.
+    # Before them, the end of the set-up: the recorded window is replayed, untimed, for at least 1000 steps (~0.1 s on the default
+    # line), so that the timed steps run on a device in steady state (20 steps last ~2 ms: of three back-to-back repetitions, the
+    # first used to run ~3 % slower). The count depends on the arguments only: profiles of separate runs slice the same launches.
+    n_pass = -(-1000 // (W + R))
+    for _ in range(n_pass):
+        for r in range(W + R):
+            step(r)
+    barrier()
     reps, reps_own = [], []
     for _ in range(max(1, args.repeats)):
         el, own = timed_region()
@@ -368,9 +401,45 @@ def main():
         dist.all_gather_object(gathered, own_med / K * 1e3)
         per_rank_ms = [float(x) for x in gathered]
 
+    # --dump-outputs: the output buffers of hdsm_replan_device as the LAST timed step left them, every agent of the swarm (the shards
+    # of N > 1 gathered in agent order), before any later pass writes into them. The solver stages neighbour rows through atomics, so
+    # two runs (and the set-up flights that record their inputs) agree to rounding, not bit for bit.
+    dumped = None
+    if args.dump_outputs:
+        x = rec[W + (K - 1) % R]   # the inputs of that step: a digest tells drifting inputs from drifting outputs
+        h = hashlib.sha256()
+        for k in rec_keys:
+            h.update(np.ascontiguousarray(x[k]).tobytes())
+        dig = h.hexdigest()
+        if world > 1:
+            digs = [None] * world
+            dist.all_gather_object(digs, dig)
+            dig = hashlib.sha256("".join(digs).encode()).hexdigest()
+        dumped = {"round": first_round + (K - 1) % R, "inputs_sha16": dig[:16],
+                  "what": "the recorded round the last timed step replayed, whose outputs --dump-outputs wrote, and a digest of its solver "
+                          "inputs (agent_id, state, ref, n_poly, n_rows, A, b, plans, has_plan of every rank)"}
+        got = {}
+        for name, t in (("traj", d_traj), ("ctrl", d_ctrl), ("used", d_used), ("status", d_status), ("obj", d_obj)):
+            a = t.double().cpu()
+            if world > 1:
+                full = torch.empty((world * a.shape[0],) + tuple(a.shape[1:]), dtype=a.dtype)
+                dist.all_gather_into_tensor(full, a)
+                a = full
+            got[name] = a[:n_rob].numpy()
+        row_bytes = sum(a[0].size for a in got.values()) * 8 + 8
+        keep = (64 << 20) // row_bytes
+        if n_rob > keep:   # (a fixed, seeded sample of the agents keeps the files within 64 MB)
+            idx = np.sort(np.random.default_rng(0).choice(n_rob, keep, replace=False))
+            got = {k: v[idx] for k, v in got.items()}
+            got["agent_index"] = idx.astype(np.float64)
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in got.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
     # N > 1: the exchange alone (HIP events on the launch stream around hdsm_exchange_device, nothing else queued in between)
     exchange_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         n_x = max(K, 20)
         for _ in range(3):
             exchange()
@@ -420,11 +489,11 @@ def main():
     # Two HIP-event measurements per round, both on the launch stream: around the whole entry point (pre-pass + solver kernel +
     # their launch gaps: the solve latency a caller sees) and, inside the library (hdsm_set_kernel_timing), right before and
     # right after the SOLVER KERNEL alone — the duration the roofline is priced on and the one a rocprofv3 trace shows.
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(R)]
     sph, pairs, it_all, nodes_all, kernel_only_ms = [], [], [], [], []
     dev_out = {}   # device answers of the timed rounds (this replay of the same recorded inputs), kept for the parity check below
     solver.set_kernel_timing(not args.no_event_pass)
-    for k, r in enumerate(range(W, W + K) if not args.no_event_pass else []):
+    for k, r in enumerate(range(W, W + R) if not args.no_event_pass else []):
         ev[k][0].record(stream)
         launch(r)
         ev[k][1].record(stream)
@@ -459,18 +528,18 @@ def main():
             return (time.perf_counter() - t1) / len(inputs) * 1e3
 
         # (a) the caller's arrays are ordinary pageable memory (every copy goes through the driver's staging buffer)
-        host_ms = host_pass([rec[r] for r in range(W, W + K)])
+        host_ms = host_pass([rec[r] for r in range(W, W + R)])
         # (b) the caller keeps ONE set of arrays, page-locked once with hdsm_host_register, and refills it every round (the
         # refill — the binding writing its inputs — is outside the clock, like the planner code that produces them)
         fixed = {k: np.ascontiguousarray(rec[W][k]).copy() for k in keys}
         for a in list(fixed.values()) + list(out_h.values()):
             host_register(a)
         t_pin = 0.0
-        for r in range(W, W + K):
+        for r in range(W, W + R):
             for k in keys:
                 fixed[k][...] = rec[r][k]
             t_pin += host_pass([fixed])
-        host_pinned_ms = t_pin / K
+        host_pinned_ms = t_pin / R
         for a in list(fixed.values()) + list(out_h.values()):
             host_unregister(a)
 
@@ -494,7 +563,7 @@ def main():
                 pinned = list(buf.values()) + list(o1.values()) if mode == "registered" else []
                 for arr in pinned:
                     host_register(arr)
-                for r in range(0, W + K):
+                for r in range(0, W + R):
                     for k in keys1:
                         buf[k][...] = rec[r][k][a1:a1 + 1]
                     buf["plans"][...] = rec[r]["plans"]
@@ -645,7 +714,7 @@ def main():
         loop_w = swarm.SwarmLoop(prm, cfg, n_w, rank=rank, world=world, solve=solve_w, allgather=allgather_np,
                                  radius=n_w / (2 * np.pi), reference=ref_w)
         rec_w = []
-        for r in range(first_w + K):
+        for r in range(first_w + R):
             loop_w.step(record=rec_w if r >= first_w - W else None)
 
         def stack_w(key_, dtype):
@@ -679,8 +748,8 @@ def main():
                 step_w(r)
             barrier()
             t0 = time.perf_counter()
-            for r in range(W, W + K):
-                step_w(r)
+            for i in range(K):
+                step_w(W + i % R)
             barrier()
             t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -688,7 +757,7 @@ def main():
         el_w = sorted(reps_w)[(len(reps_w) - 1) // 2]
         weak = {"scaling": "weak", "agents": n_w, "agents_per_gpu": per_w, "n_gpus": world, "value": n_w * K / el_w,
                 "unit": "agent-replans/s", "ms_per_step": el_w / K * 1e3, "ms_per_step_repeats": [e / K * 1e3 for e in reps_w],
-                "steps": K, "warmup": W, "rounds": f"{first_w}..{first_w + K - 1}",
+                "steps": K, "warmup": W, "rounds": f"{first_w}..{first_w + R - 1}",
                 "exchange_bytes_per_rank_per_round": per_w * (N + 1) * 9 * 8,
                 "exchange": "RCCL all-gather (hdsm_exchange_device)" if comm is not None else "host-staged gloo all-gather (flow check only)",
                 "what": f"{per_w} agents per GPU on a ring of {n_w} (R = n / 2 pi): every rank solves its {per_w} instances against "
@@ -707,7 +776,7 @@ def main():
         orc.lib()
         cores = os.cpu_count() or 1
         BLK = 16
-        blocks = [(r, a) for r in range(W, W + K) for a in range(0, n_local, BLK)]
+        blocks = [(r, a) for r in range(W, W + R) for a in range(0, n_local, BLK)]
         rng = np.random.default_rng(0)
         rng.shuffle(blocks)
 
@@ -735,7 +804,7 @@ def main():
         tasks = range(n_tasks)
         dt_cpu = time.perf_counter() - t1
         cpu = {"value": done / dt_cpu, "unit": "agent-replans/s", "cores": cores, "kind": "port",
-               "sample": f"{n_tasks} blocks of {BLK} agents drawn from the {K} timed rounds ({done} agent-replans) on the CPU "
+               "sample": f"{n_tasks} blocks of {BLK} agents drawn from the {R} timed rounds ({done} agent-replans) on the CPU "
                          f"restatement (oracle/hdsm_oracle.c: cold-started dense active set, not Gurobi), one block per "
                          f"thread, {cores} threads",
                "seconds": dt_cpu, "per_core_replans_per_s": done / dt_cpu / min(cores, len(tasks))}
@@ -761,7 +830,7 @@ def main():
                 n_fail0 += int((nos & (g["iters"][sl] == 0)).sum())
             parity = {"instances_compared": n_cmp, "status_mismatches": n_mis, "max_abs_traj_diff": d_traj_max,
                       "max_rel_obj_diff": d_obj_max, "no_solution_compared": n_fail, "no_solution_first_sweep_exits_compared": n_fail0,
-                      "oracle_without_verdict": n_nov, "instances_in_timed_rounds": K * n_local,
+                      "oracle_without_verdict": n_nov, "instances_in_timed_rounds": R * n_local,
                       "what": "device answers (status, trajectory, objective) of the timed rounds, downloaded in the event pass, against "
                               "the CPU oracle on the same recorded inputs (every 16-agent block the baseline leg solved); "
                               "first-sweep exits = instances the kernel ended as infeasible without an active-set operation"}
@@ -781,7 +850,7 @@ def main():
         for r in range(0, W):
             launch(r)
         outs = {}
-        for r in range(W, W + K):
+        for r in range(W, W + R):
             launch(r)
             torch.cuda.synchronize()
             outs[r] = dict(status=d_status[:n_local].cpu().numpy().copy(), traj=d_traj[:n_local].cpu().numpy().copy(),
@@ -816,7 +885,7 @@ def main():
         d_traj_max = d_obj_max = lim_gap_max = 0.0
         lim_total = int(sum((outs[r]["status"] == 1).sum() for r in outs))
         nos_total = int(sum((outs[r]["status"] == 2).sum() for r in outs))
-        for r in range(W, W + K):   # leg 1
+        for r in range(W, W + R):   # leg 1
             if time.perf_counter() - t_par > args.parity_seconds * 2.0 / 3.0:
                 break
             x, g = rec[r], outs[r]
@@ -839,7 +908,7 @@ def main():
                 n_nos_mis += int((on["status"] == 0).sum())
                 n_nos_nov += int((on["status"] == 1).sum())
             unproven_rounds += 1
-        for r in range(W, W + K):   # leg 2
+        for r in range(W, W + R):   # leg 2
             if time.perf_counter() - t_par > args.parity_seconds:
                 break
             x, g = rec[r], outs[r]
@@ -867,7 +936,7 @@ def main():
                   "no_solution_oracle_finds_a_solution": n_nos_mis, "no_solution_oracle_without_verdict": n_nos_nov,
                   "rounds_checked_for_unproven_answers": unproven_rounds,
                   "failed_instances_in_replay": nos_total,
-                  "instances_in_timed_rounds": K * n_local, "seconds": time.perf_counter() - t_par,
+                  "instances_in_timed_rounds": R * n_local, "seconds": time.perf_counter() - t_par,
                   "what": "a replay of the timed rounds after the timed region (same recorded inputs, same warm-up). Leg 1: EVERY instance the device "
                           "ended on a budget (its incumbent against the oracle's PROVEN optimum: below = a wrong answer, above = a valid but "
                           "suboptimal incumbent, as AC:948-952 lets Gurobi return at its time limit) and EVERY instance it called infeasible (the oracle "
@@ -932,7 +1001,7 @@ def main():
         secs = sorted(reps_w)[(len(reps_w) - 1) // 2]
         n_cmp = n_mis = 0
         d_max = 0.0
-        for r in range(W, W + K):   # its answers against the device's, every instance of the timed rounds
+        for r in range(W, W + R):   # its answers against the device's, every instance of the timed rounds
             if r not in dev_out:
                 continue
             g = dev_out[r]
@@ -942,12 +1011,12 @@ def main():
             both = (st_c == 0) & (g["status"] == 0)
             if both.any():
                 d_max = max(d_max, float(np.abs(last["traj"][r][both] - g["traj"][both]).max()))
-        cpu_warm = {"value": K * n_local / secs, "unit": "agent-replans/s", "cores": cores, "kind": "port-warm",
-                    "sample": f"all {K * n_local} agent-replans of the {K} timed rounds, {cores} threads, each owning a block of agents and walking "
+        cpu_warm = {"value": R * n_local / secs, "unit": "agent-replans/s", "cores": cores, "kind": "port-warm",
+                    "sample": f"all {R * n_local} agent-replans of the {R} timed rounds, {cores} threads, each owning a block of agents and walking "
                               f"the rounds in order (warm-up rounds {rec_from}..{first_round - 1} build the warm-start stores, untimed); "
                               "oracle/hdsm_cpu_port.c = the kernel's algorithm (lazy closed-form planes, sphere prefilter, normalised pick rule, "
                               "warm start) as scalar C with a textbook dense factorisation — not Gurobi, not a tuned CPU solver",
-                    "seconds": secs, "seconds_repeats": reps_w, "per_core_replans_per_s": K * n_local / secs / cores,
+                    "seconds": secs, "seconds_repeats": reps_w, "per_core_replans_per_s": R * n_local / secs / cores,
                     "active_set_operations_mean": float(last["qp_iters"][W:].mean()), "branch_and_bound_fallbacks": int(last["fallbacks"]),
                     "vs_device": {"instances_compared": n_cmp, "status_mismatches": n_mis, "max_abs_traj_diff": d_max}}
 
@@ -985,7 +1054,8 @@ def main():
             "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": names[args.scenario] + f", H={N}, poly_hor={P}, closed-loop rounds "
-                                   f"{first_round}..{first_round + K - 1} replayed (warm-up: rounds {rec_from}..{first_round - 1})",
+                                   f"{first_round}..{first_round + R - 1} replayed" + (f" cyclically over {K} steps" if K > R else "")
+                                   + f" (warm-up: rounds {rec_from}..{first_round - 1})",
                        "workload_key": key, "mip_gap": args.mip_gap, "time_limit_s": args.time_limit_s, "agents": n_rob, "agents_per_gpu": n_local, "horizon": N, "poly_hor": P,
                        "parallelism": f"agents sharded over {world} GPU(s), one RCCL all-gather per round"
                                       if world > 1 else "one GPU"},
@@ -993,9 +1063,12 @@ def main():
             "p95_solve_latency_ms": float(np.percentile(kern_ms, 95)),
             "kernel_ms_mean": mean_ms, "kernel_ms_p50": float(np.percentile(kernel_only_ms, 50)),
             "kernel_ms_p95": float(np.percentile(kernel_only_ms, 95)), "entry_point_ms_mean": float(kern_ms.mean()),
-            "kernel_ms_what": "kernel_ms_* = k_replan alone (HIP events inside the library, after the pre-pass) — what the "
-                              "roofline is priced on and what a rocprofv3 trace shows; p50/p95_solve_latency_ms and "
-                              "entry_point_ms_mean = the whole hdsm_replan_device call on an idle stream (pre-pass, kernel, launch gaps)",
+            "kernel_ms_what": ("kernel_ms_* = k_replan alone (HIP events inside the library, after the pre-pass) — what the "
+                               "roofline is priced on and what a rocprofv3 trace shows; p50/p95_solve_latency_ms and "
+                               "entry_point_ms_mean = the whole hdsm_replan_device call on an idle stream (pre-pass, kernel, launch gaps)")
+                              if not args.no_event_pass else
+                              "no event pass in this run (--full runs one): kernel_ms_*, p50/p95_solve_latency_ms, entry_point_ms_mean "
+                              "and the roofline are priced on ms_per_step",
             "host_buffer_path": None if host_ms is None else {
                 "ms_per_round": host_ms, "agent_replans_per_s": n_rob / (host_ms * 1e-3),
                 "ms_per_round_registered_arrays": host_pinned_ms,
@@ -1016,10 +1089,11 @@ def main():
                 "(1024 agents per GPU, ring of 1024 N agents, one RCCL all-gather per round, same timing contract)"),
             "failed_instances_timed_rounds": fails_timed, "failed_instances_recorded": fails, "limit_instances_timed_rounds": limits_timed,
             "setup_flight_s": t_setup,
+            "dumped_step": dumped,
             "ms_per_step_repeats": [e / K * 1e3 for e in reps],
-            "k_replan_launch_sequence": {"setup_flight": rec_to, "warmup": W, "timed": K, "repeats_of_warmup_plus_timed": len(reps),
-                                         "event_pass": 0 if args.no_event_pass else K,
-                                         "host_pass": K if host_ms is not None else 0},
+            "k_replan_launch_sequence": {"setup_flight": rec_to, "untimed_pass": n_pass * (W + R), "warmup": W, "timed": K,
+                                         "repeats_of_warmup_plus_timed": len(reps), "event_pass": 0 if args.no_event_pass else R,
+                                         "host_pass": R if host_ms is not None else 0},
             "solver_stats_timed_rounds": {"qp_iters_max": int(it_cat.max()), "qp_iters_mean": float(it_cat.mean()),
                                           "qp_iters_p99": float(np.percentile(it_cat, 99)),
                                           "nodes_max": int(np.concatenate(nodes_all).max()) if nodes_all else int(stats["nodes"].max()),

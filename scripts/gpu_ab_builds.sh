@@ -8,7 +8,7 @@ rec=/tmp/ab_rec_builds.npz
 for r in $(seq $reps); do
 for n in $names; do
   cp multi_agent_pkgs_amd/libhdsm_$n.so multi_agent_pkgs_amd/libhdsm.so
-  timeout 600 python bench.py --no-cpu-baseline --no-secondary --load-recording $rec 2>&1 | tail -1 > /tmp/ab_line.json
+  timeout 600 python bench.py --full --no-cpu-baseline --no-secondary --load-recording $rec 2>&1 | tail -1 > /tmp/ab_line.json
   python - "$n" <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_line.json").read())

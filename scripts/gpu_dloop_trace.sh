@@ -1,6 +1,7 @@
 # kernel timeline of the device-resident loop (rocprofv3 --kernel-trace of bench.py; scripts/summarize_dloop_trace.py)
 # usage: bash scripts/gpu_dloop_trace.sh [tag] [bench args]
 TAG=${1:-dloop}; shift
+set -- --full "$@"
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT

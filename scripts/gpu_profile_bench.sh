@@ -6,6 +6,7 @@
 #   4. scripts/summarize_profile.py -> profiles/<tag>_* (kernel stats of the timed launches, PMC per launch, workload key)
 TAG=${1:-r02}; shift
 ARGS=${@:-"--gpus 1 --steps 20 --warmup 5"}
+ARGS="$ARGS --full"
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT

@@ -17,10 +17,10 @@ for v in $vals; do
 done
 done
 if [ "$bench" = "1" ]; then
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r5/bench.json 2> gpurun_out/r5/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > /tmp/r5_bench.json 2> /tmp/r5_bench.err; echo "bench rc=$?"
   python - <<'PY'
 import json
-d=json.loads(open('gpurun_out/r5/bench.json').read().strip().splitlines()[-1])
+d=json.loads(open('/tmp/r5_bench.json').read().strip().splitlines()[-1])
 print('value %.3e ms %.4f kernel %.4f frac %.3f' % (d['value'], d['ms_per_step'], d['kernel_ms_mean'], d['roofline']['frac']))
 print('parity', d['parity_on_timed_rounds'] and {k: d['parity_on_timed_rounds'][k] for k in ('instances_compared','status_mismatches','max_abs_traj_diff')})
 print('second', d.get('second_window') and {k: d['second_window'][k] for k in ('value','ms_per_step','failed_instances')}, 'solved/s %.3e' % d['solved_replans_per_s'])

@@ -20,24 +20,24 @@ if has 2; then
 fi
 run() { t=$1; shift; timeout 600 python bench.py --no-cpu-baseline --no-secondary "$@" > gpurun_out/$TAG/bench_$t.json 2> gpurun_out/$TAG/bench_$t.err; echo "$t rc=$? $(python -c "import json,sys; d=json.loads(open('gpurun_out/$TAG/bench_$t.json').read().strip().splitlines()[-1]); print('%.4f ms' % d['ms_per_step'], 'limit', d['limit_instances_timed_rounds'], 'failed', d['failed_instances_timed_rounds'], 'nodes_max', d['solver_stats_timed_rounds']['nodes_max'])" 2>/dev/null)"; }
 if has 3; then
-  run cfg2_circle64 --agents 64 --first-round 35 --steps 50 --warmup 10
-  run cfg3_forest256 $C3
-  HDSM_DOMINANCE=0 run cfg3_forest256_no_dominance $C3 --no-event-pass
-  HDSM_SPLIT=0 run cfg3_forest256_unsplit $C3 --no-event-pass
-  run cfg3_forest256_rounds60_79 --scenario forest --agents 256 --first-round 60 --no-event-pass
-  run cfg5_fwf4096_h15 $C5
-  HDSM_DOMINANCE=0 run cfg5_fwf4096_h15_no_dominance $C5 --no-event-pass
-  HDSM_DOMINANCE=0 HDSM_SPLIT_BUDGET=16 HDSM_ITEM_MIN=16 run cfg5_fwf4096_h15_round5_settings $C5 --no-event-pass
-  HDSM_SPLIT_BUDGET=16 HDSM_ITEM_MIN=16 run cfg5_fwf4096_h15_budget16 $C5 --no-event-pass
-  HDSM_SPLIT=0 run cfg5_fwf4096_h15_unsplit $C5 --no-event-pass
-  run cfg5_fwf4096_h15_mipgap1e-4 $C5 --no-event-pass --mip-gap 1e-4
-  run cfg5_fwf4096_h15_deep --scenario fwf --agents 4096 --horizon 15 --first-round 30 --steps 6 --warmup 2 --no-event-pass
-  HDSM_SETUP_MFMA=0 run circle1024_setup_map_per_instance --no-event-pass
-  run circle1024_same_box --no-event-pass
-  HDSM_SETUP_MFMA=0 run circle1024_setup_map_per_instance_b --no-event-pass
-  run circle1024_same_box_b --no-event-pass
-  run circle1024_cold_start --cold-start --no-event-pass
-  run circle4096_h15 --agents 4096 --horizon 15 --first-round 20 --steps 8 --warmup 2
+  run cfg2_circle64 --full --agents 64 --first-round 35 --steps 50 --warmup 10
+  run cfg3_forest256 --full $C3
+  HDSM_DOMINANCE=0 run cfg3_forest256_no_dominance --full $C3 --no-event-pass
+  HDSM_SPLIT=0 run cfg3_forest256_unsplit --full $C3 --no-event-pass
+  run cfg3_forest256_rounds60_79 --full --scenario forest --agents 256 --first-round 60 --no-event-pass
+  run cfg5_fwf4096_h15 --full $C5
+  HDSM_DOMINANCE=0 run cfg5_fwf4096_h15_no_dominance --full $C5 --no-event-pass
+  HDSM_DOMINANCE=0 HDSM_SPLIT_BUDGET=16 HDSM_ITEM_MIN=16 run cfg5_fwf4096_h15_round5_settings --full $C5 --no-event-pass
+  HDSM_SPLIT_BUDGET=16 HDSM_ITEM_MIN=16 run cfg5_fwf4096_h15_budget16 --full $C5 --no-event-pass
+  HDSM_SPLIT=0 run cfg5_fwf4096_h15_unsplit --full $C5 --no-event-pass
+  run cfg5_fwf4096_h15_mipgap1e-4 --full $C5 --no-event-pass --mip-gap 1e-4
+  run cfg5_fwf4096_h15_deep --full --scenario fwf --agents 4096 --horizon 15 --first-round 30 --steps 6 --warmup 2 --no-event-pass
+  HDSM_SETUP_MFMA=0 run circle1024_setup_map_per_instance --full --no-event-pass
+  run circle1024_same_box --full --no-event-pass
+  HDSM_SETUP_MFMA=0 run circle1024_setup_map_per_instance_b --full --no-event-pass
+  run circle1024_same_box_b --full --no-event-pass
+  run circle1024_cold_start --full --cold-start --no-event-pass
+  run circle4096_h15 --full --agents 4096 --horizon 15 --first-round 20 --steps 8 --warmup 2
   python scripts/collect_round_profiles.py $TAG 2>&1 | tail -1
 fi
 if has 4; then

@@ -1,6 +1,7 @@
 # launch-timeline fit (scripts/timeline_fit.py) of the bench rounds for several settings of one environment knob, one -DHDSM_TIMELINE build
 # usage: bash scripts/gpu_timeline_ab.sh VAR "v1 v2 ..." [bench args]
 var=$1; vals=$2; shift 2
+set -- --full "$@"
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 cp multi_agent_pkgs_amd/libhdsm.so /tmp/libhdsm_orig.so

@@ -20,7 +20,7 @@ for tag in ("default", "mfma"):
             continue
         line = json.loads(open(jf).read().strip().splitlines()[-1])
         seq = line["k_replan_launch_sequence"]
-        lo = seq["setup_flight"] + seq["warmup"]
+        lo = seq["setup_flight"] + seq.get("untimed_pass", 0) + seq["warmup"]
         hi = lo + seq["timed"]
         for f in glob.glob(os.path.join(out, f"{tag}_pmc_{grp}", "*counter_collection.csv")):
             per = {}

@@ -15,7 +15,7 @@ root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out_dir = os.path.join(root, "gpurun_out", tag)
 line = json.loads(open(os.path.join(out_dir, "trace_bench.json")).read().strip().splitlines()[-1])
 seq = line["k_replan_launch_sequence"]
-lo = seq["setup_flight"] + seq["warmup"]
+lo = seq["setup_flight"] + seq.get("untimed_pass", 0) + seq["warmup"]
 hi = lo + seq["timed"]
 key = line["config"]["workload_key"]
 summ = {"tag": tag, "workload_key": key, "command": "python bench.py " + " ".join(sys.argv[2:]) if len(sys.argv) > 2 else None,

@@ -257,7 +257,7 @@ def test_bench_self_launches_two_ranks_and_reports_rccl_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--agents", "128",
-                        "--first-round", "20", "--repeats", "1", "--no-cpu-baseline"],
+                        "--first-round", "20", "--repeats", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -283,7 +283,7 @@ def _run_bench_two_ranks(extra, env_extra=None, timeout=900):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(env_extra or {})
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--agents", "128",
-                        "--first-round", "20", "--repeats", "1", "--no-cpu-baseline"] + extra,
+                        "--first-round", "20", "--repeats", "1", "--no-cpu-baseline", "--full"] + extra,
                        capture_output=True, text=True, timeout=timeout, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -291,13 +291,85 @@ def _run_bench_two_ranks(extra, env_extra=None, timeout=900):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_on_one_gpu_host_staged_exchange_carries_every_multi_gpu_key():
+DUMP_SHAPES = {"traj": (11, 9), "ctrl": (10, 3), "used": (4,), "status": (), "obj": ()}
+
+
+def _plain_bench(args, dump_dir):
+    """`bench.py --gpus 1 <args> --dump-outputs <dump_dir>` in a fresh process: its line and the dumped arrays."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + args + ["--dump-outputs", str(dump_dir)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    z = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert sorted(os.listdir(dump_dir)) == sorted(k + ".npy" for k in DUMP_SHAPES)
+    return z, {k: np.load(os.path.join(dump_dir, k + ".npy")) for k in DUMP_SHAPES}
+
+
+def _same_answers(a, b, tol):
+    """Two dumps of the same step: the same discrete answers, trajectories / controls / objectives equal to `tol`."""
+    assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["used"], b["used"])
+    ok = a["status"] != 2
+    for k in ("traj", "ctrl"):
+        assert np.abs(a[k][ok] - b[k][ok]).max() <= tol, k
+    assert (np.abs(a["obj"][ok] - b["obj"][ok]) / np.maximum(1.0, np.abs(a["obj"][ok]))).max() <= tol
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps once and runs none of the passes --full adds; past
+    bench.WINDOW_MAX steps it replays the recorded rounds cyclically instead of flying more; --dump-outputs writes the output
+    buffers of the LAST timed step, every agent, as float64: 230 steps over the 200 rounds 20..219 end on round 49, like 30
+    steps do, and 31 steps end on round 50."""
+    common = ["--warmup", "1", "--agents", "64", "--first-round", "20"]
+    z, out = _plain_bench(["--steps", "230"] + common, tmp_path / "k230")
+    assert z["steps"] == 230 and z["warmup"] == 1 and z["ms_per_step"] > 0 and len(z["ms_per_step_repeats"]) == 1
+    assert z["value"] == pytest.approx(64 * 1e3 / z["ms_per_step"])
+    seq = z["k_replan_launch_sequence"]
+    assert seq["timed"] == 230 and seq["repeats_of_warmup_plus_timed"] == 1 and seq["event_pass"] == 0 and seq["host_pass"] == 0
+    # the untimed steady-state passes are fixed by the arguments (ceil(1000 / (W + R)) passes of W + R steps)
+    assert seq["setup_flight"] == 20 + 200 and seq["untimed_pass"] == 5 * (1 + 200)
+    assert "20..219 replayed cyclically over 230 steps" in z["config"]["workload"]
+    for k in ("cpu_baseline", "cpu_baseline_warm", "parity_on_timed_rounds", "secondary_workloads", "second_window",
+              "single_instance_call", "device_resident_loop", "host_buffer_path"):
+        assert z[k] is None, k
+    for k, shp in DUMP_SHAPES.items():
+        assert out[k].dtype == np.float64 and out[k].shape == (64,) + shp, k
+    assert set(np.unique(out["status"])) <= {0.0, 1.0, 2.0} and (out["status"] == 0).any()
+    solved = out["status"] == 0
+    assert np.isfinite(out["traj"][solved]).all() and np.abs(out["traj"][solved]).max() > 0
+    assert z["dumped_step"]["round"] == 49 and len(z["dumped_step"]["inputs_sha16"]) == 16
+    z30, out30 = _plain_bench(["--steps", "30"] + common, tmp_path / "k30")
+    z31, out31 = _plain_bench(["--steps", "31"] + common, tmp_path / "k31")
+    assert z30["dumped_step"]["round"] == 49 and z31["dumped_step"]["round"] == 50
+    _same_answers(out, out30, 1e-9)
+    assert np.abs(out31["traj"][:, 0] - out30["traj"][:, 0]).max() > 1e-3   # (one round later the agents stand elsewhere)
+
+
+def test_bench_dumps_of_two_runs_agree_to_rounding(tmp_path):
+    """The default line twice, in two processes: the set-up flights and the replays run through a solver that stages neighbour rows
+    through atomics, so the dumped step agrees to rounding (~1e-11 observed), not bit for bit; its discrete answers are identical."""
+    args = ["--steps", "20", "--warmup", "5"]
+    za, a = _plain_bench(args, tmp_path / "a")
+    zb, b = _plain_bench(args, tmp_path / "b")
+    assert za["dumped_step"]["round"] == zb["dumped_step"]["round"] == 184
+    assert a["traj"].shape == (1024, 11, 9)
+    _same_answers(a, b, 1e-9)
+
+
+def test_bench_two_ranks_on_one_gpu_host_staged_exchange_carries_every_multi_gpu_key(tmp_path):
     """The N > 1 flow of bench.py end to end on a box with ONE GPU (what every box of this build has been): `--gpus 2 --dist-backend
     gloo` starts two ranks that share device 0, shards the swarm, runs the timed region with the barrier / max-over-ranks contract
     and a host-staged all-gather in place of hdsm_exchange_device. Every key the multi-GPU line carries must be there and sane
     (`rccl_ranks` null because no RCCL communicator exists; the exchange figures are labelled as the flow check they are) — so that
-    the first run on a multi-GPU node can only differ in the exchange itself."""
-    z = _run_bench_two_ranks(["--dist-backend", "gloo"], {"HDSM_BENCH_WEAK_PER_GPU": "64"})
+    the first run on a multi-GPU node can only differ in the exchange itself. --dump-outputs gathers both shards in agent order."""
+    z = _run_bench_two_ranks(["--dist-backend", "gloo", "--dump-outputs", str(tmp_path)], {"HDSM_BENCH_WEAK_PER_GPU": "64"})
+    traj, status = np.load(tmp_path / "traj.npy"), np.load(tmp_path / "status.npy")
+    assert traj.shape == (128, 11, 9) and status.shape == (128,)
+    assert (status[:64] == 0).any() and (status[64:] == 0).any()
+    assert np.abs(traj[:64][status[:64] == 0]).max() > 0 and np.abs(traj[64:][status[64:] == 0]).max() > 0
     assert z["n_gpus"] == 2 and z["scaling"] == "strong" and z["value"] > 0 and z["steps"] == 5 and z["warmup"] == 2
     assert z["rccl_ranks"] is None and z["exchange_error"] is None and "gloo" in z["exchange"]
     assert z["config"]["agents"] == 128 and z["config"]["agents_per_gpu"] == 64
