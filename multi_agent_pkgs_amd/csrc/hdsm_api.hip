@@ -24,6 +24,7 @@
 #include "hdsm_consts.h"
 #include "hdsm_core.h"
 #include "hdsm_level1.h"
+#include "hdsm_shapes.h"
 
 namespace {
 
@@ -45,8 +46,8 @@ int set_err(int code, const std::string& msg) {
 
 // staged neighbour rows (LDS). One workgroup per CU is resident anyway (the iteration wave needs > 256 registers,
 // a 256-register budget spills 644 B/lane), so LDS capacity is spent on fewer staging-radius retries.
-constexpr int CMAX30 = 1536;  // n <= 30
-constexpr int CMAX48 = 1024;  // n <= 48
+using hdsm::CMAX30;  // 1536 rows, n <= 30 (hdsm_shapes.h: the one list of launch shapes, shared with the CPU execution)
+using hdsm::CMAX48;  // 1024 rows, n <= 48
 
 // What a workgroup works on. Ordinary launch: block b -> instance order[b] (or b). Pass 2 of a split launch (a.item_mode): the
 // workgroups are PERSISTENT — each draws items from the queue pass 1 filled (Args::items: one open child of an open level of a
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(NT) void k_replan(const hdsm::Consts* __restrict__ 
 // rows makes the instance state fit twice into 160 KB). A single instance is bound by the latency of its one iterating
 // wave, so when there are more instances than CUs a second resident workgroup nearly doubles the throughput. Used for
 // n <= 30 only (the NV = 48 factor does not fit the halved register file).
-constexpr int CMAX_DUO = 768;
+using hdsm::CMAX_DUO;  // 768 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_duo(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -844,7 +845,7 @@ int launch_duo(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
 // 119 us against 107 us for the slowest instance, profiles/r03_launch_timeline.json); with 768 slots the late starters begin
 // when the first instances without iterations leave (~18 us) and finish inside the slowest instance. The sweeps and the set-up
 // run on half the threads (+2..3 us per instance), the staging area shrinks to 384 rows (three states in 160 KB).
-constexpr int CMAX_TRI = 384;
+using hdsm::CMAX_TRI;  // 384 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_tri(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -857,7 +858,7 @@ __global__ __launch_bounds__(NT, 2) void k_replan_tri(const hdsm::Consts* __rest
 // the three-per-CU launch ended 15-25 us after its slowest instance, set by a late starter. Four instance states fit 160 KB with
 // the small LDS layout (Shm<.., SMALL>: 4 polyhedra of <= 20 rows, 512-neighbour chunks) and a staging area of 256 rows (the
 // bench rounds stage <= 190; an overflow is re-solved by the rescue pass like for the other shared-CU kernels).
-constexpr int CMAX_QUAD = 256;
+using hdsm::CMAX_QUAD;  // 256 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_quad(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -891,9 +892,10 @@ int launch_quad(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
 // "infeasible" after two operations, deterministically per build, while builds with a spill, with -O2, with -fwrapv or with device
 // printf in the loop gave the oracle's answers; the CPU execution of the same source is right in either wave order. The cause was not
 // found — scripts/gpu_r6_overflow_raw.py reproduces it on the sources of that commit — so the product keeps ONE instantiation per
-// launch shape, each of which the whole -m gpu suite, the fuzz and the oracle check of the timed rounds run through, and the
-// overflow test fills the 256 rows of the four-per-CU kernel instead.)
-constexpr int CMAX_DUO48 = 720;
+// launch shape, each of which the whole -m gpu suite, the fuzz and the oracle check of the timed rounds run through. The 720 rows
+// of this kernel are filled and overflowed on purpose by test_gpu_abi.py::test_staging_overflow_at_each_shared_cu_capacity_is_rescued
+// and, in the CPU execution of the source together with the 320-row tuple, by tests/test_wave_shapes.py.)
+using hdsm::CMAX_DUO48;  // 720 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 1) void k_replan_duo48(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

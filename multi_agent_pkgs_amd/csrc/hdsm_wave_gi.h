@@ -113,8 +113,19 @@ __device__ __forceinline__ double rsq_nr(double x) {
 // "Then" must hold in the machine code: the increment ACQUIRES (nothing after it moves in front of it) and the other counter is read
 // ATOMICALLY (never a value the compiler kept from before). Written as a plain `s.ncold` after a relaxed atomicAdd the order was only an
 // accident of instruction scheduling — one register-allocation change later (round 6) the read of a loop-invariant-looking `s.ncold`
-// sat in front of the loop, both lists wrote through each other as soon as the area filled up, and the 320-row kernel returned
-// "infeasible" for feasible instances WITHOUT the overflow flag.
+// sat in front of the loop, and the two lists could write through each other once the area filled up. That was found while chasing
+// the 320-row H = 15 kernel that returned "infeasible" for feasible instances without the overflow flag, but it is not what broke
+// that kernel: the lists meet only with a finite hot_tau (HDSM_HOT_TAU; the product stages every row hot), and DESIGN.md section 9
+// keeps that failure open. tests/test_wave_shapes.py runs this function in the CPU execution with the threads interleaved at every
+// atomic operation, on batches that overflow the 256 / 384 / 720 / 768-row shapes and the 320-row one, with the lists meeting, and
+// audits every slot (the hooks below): no second writer, every instance the oracle's answer or flagged.
+// The CPU execution of this source (tests/wave_emu) defines the three audit hooks: it counts the writers of every slot of a sweep
+// and checks the counts when the sweep ends. Everywhere else they are empty.
+#ifndef HDSM_STAGE_AUDIT_CLAIM
+#define HDSM_STAGE_AUDIT_BEGIN(ncand, ncold, cmax)
+#define HDSM_STAGE_AUDIT_CLAIM(slot, fits)
+#define HDSM_STAGE_AUDIT_END(ncand, ncold, cmax)
+#endif
 template <int CMAX>
 __device__ __forceinline__ bool stage_slot(int32_t& ncand, int32_t& ncold, bool hot, int& slot) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -128,7 +139,11 @@ __device__ __forceinline__ bool stage_slot(int32_t& ncand, int32_t& ncold, bool 
   return slot < CMAX && slot >= other && slot >= 0;
 #else
   slot = hot ? atomicAdd(&ncand, 1) : CMAX - 1 - atomicAdd(&ncold, 1);
-  return (hot ? slot < CMAX - ncold : slot >= ncand) && slot >= 0 && slot < CMAX;
+  const bool fits = (hot ? slot < CMAX - __hip_atomic_load(&ncold, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+                         : slot >= __hip_atomic_load(&ncand, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) &&
+                    slot >= 0 && slot < CMAX;
+  HDSM_STAGE_AUDIT_CLAIM(slot, fits);
+  return fits;
 #endif
 }
 
@@ -686,6 +701,7 @@ struct WaveGI {
         s.sw[0] = 2.0 * (fmax(thresh, tol) + smax + nfmax * sqrt(d2)) * (1.0 + 1e-9);
         s.sw[1] = mx, s.sw[2] = my, s.sw[3] = mz, s.sw[4] = sqrt(r2) * (1.0 + 1e-9);
         s.nlist = 0;
+        HDSM_STAGE_AUDIT_BEGIN(s.ncand, s.ncold, CMAX);
       }
     }
     bar();
@@ -774,6 +790,7 @@ struct WaveGI {
       }
     }
     bar();
+    if (lane == 0) HDSM_STAGE_AUDIT_END(s.ncand, s.ncold, CMAX);
     if (lane == 0 && s.ncand + s.ncold > CMAX) {  // rows that found no slot advanced the counters past the capacity: clamp
       s.overflow = 1;                             // (no slot is written twice, so everything below the clamped counts is complete)
       s.wanted_raw = s.ncand + s.ncold;

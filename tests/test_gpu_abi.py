@@ -486,6 +486,54 @@ def test_staging_overflow_in_a_shared_cu_kernel_is_rescued(hdsm, oracle, monkeyp
     assert flagged[0] > 0 and flagged[1] == 0 and (st == o["status"]).all(), flagged
 
 
+# the knobs that make a small batch take one shared-CU kernel (read by hdsm_create; 0 = never)
+SHARED_CU_KNOBS = {"tri": dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="1", HDSM_QUAD_MIN="0"),
+                   "duo": dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="0", HDSM_QUAD_MIN="0"),
+                   "duo48": dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="0", HDSM_QUAD_MIN="0")}   # (H = 15: n > 30 takes k_replan_duo48)
+
+
+@pytest.mark.parametrize("shape", list(SHARED_CU_KNOBS))
+def test_staging_overflow_at_each_shared_cu_capacity_is_rescued(hdsm, oracle, monkeypatch, shape):
+    """The over-capacity batches of staging_cases (their CPU execution: tests/test_wave_shapes.py) forced onto k_replan_tri (384
+    rows), k_replan_duo (768) and k_replan_duo48 (720, H = 15: the shape whose 320-row sibling went wrong in round 6), each with one
+    instance that has more violated rows than slots. Host buffers: the rescue pass returns the oracle's answers, no flag. Device
+    pointers: the first launch answers like the oracle wherever it raises no flag and flags at least one instance; the second launch
+    on the handle carries the rescue pass — no flags, the oracle's answers."""
+    import torch
+    import staging_cases as sc
+    from test_gpu_fuzz import K
+    prm, args = sc.batch(sc.CASES[shape]["over"])
+    n_inst, n_rob = args[1].shape[0], args[7].shape[0]
+    o = sc.verdict(oracle, prm, args, n_threads=32)
+    assert (o["status"] == 0).any()
+    for k_, v in SHARED_CU_KNOBS[shape].items():
+        monkeypatch.setenv(k_, v)
+    sol = hdsm.Solver(prm, n_inst, n_rob)
+    sol_dev = hdsm.Solver(prm, n_inst, n_rob)
+    for k_ in SHARED_CU_KNOBS[shape]:
+        monkeypatch.delenv(k_)
+    g = sol.replan(*args)
+    assert (g["status"] == o["status"]).all() and (sol.last_sweep_stats(n_inst)["flags"] & 8 == 0).all(), (g["status"], o["status"])
+    ok = o["status"] == 0
+    assert np.abs(g["traj"] - o["traj"])[ok].max() < 1e-6
+    dev = torch.device("cuda", 0)
+    dt = dict(agent_id=torch.int32, state=torch.float64, ref=torch.float64, n_poly=torch.int32, n_rows=torch.int32,
+              A=torch.float64, b=torch.float64, plans=torch.float64, has_plan=torch.uint8)
+    d = {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(dt[k]).contiguous() for k, a in zip(K, args)}
+    N, P = prm.n_hor, prm.poly_hor
+    out = dict(traj=torch.zeros((n_inst, N + 1, 9), dtype=torch.float64, device=dev), ctrl=torch.zeros((n_inst, N, 3), dtype=torch.float64, device=dev),
+               used=torch.zeros((n_inst, P), dtype=torch.uint8, device=dev), status=torch.zeros(n_inst, dtype=torch.int32, device=dev),
+               obj=torch.zeros(n_inst, dtype=torch.float64, device=dev))
+    flagged = []
+    for call in range(2):
+        sol_dev.replan_device(*[d[k] for k in K], out["traj"], out["ctrl"], out["used"], out["status"], out["obj"])
+        torch.cuda.synchronize()
+        fl = sol_dev.last_sweep_stats(n_inst)["flags"]
+        f = sc.exact_or_flagged(out["status"].cpu().numpy(), out["traj"].cpu().numpy(), out["obj"].cpu().numpy(), fl, o, 1e-6)
+        flagged.append(int(f.sum()))
+    assert flagged[0] > 0 and flagged[1] == 0, flagged   # (the second: every answer the oracle's, checked above)
+
+
 def test_device_swarm_accepts_an_empty_trailing_shard(hdsm):
     """n_rob = 5 on 4 ranks: ceil split 2 + 2 + 1 + 0 — swarm.shard_range gives rank 3 first_id = n_rob and no agent. The device loop
     must take that shard (it only relays the exchange); a shard that is not a block of the split is still refused."""

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import problems
-from multi_agent_pkgs_amd.params import agile_params, default_params
+from multi_agent_pkgs_amd.params import agile_params, default_params, make_params
 
 pytestmark = pytest.mark.gpu
 
@@ -620,3 +620,34 @@ def test_the_set_up_map_on_the_matrix_cores_gives_the_answers_of_the_per_instanc
         assert np.abs(mfma["traj"] - plain["traj"])[ok].max() < 1e-9
         assert np.abs(mfma["traj"] - o["traj"])[ok].max() < 1e-7
         assert (np.abs(mfma["obj"] - o["obj"])[ok] / np.maximum(1.0, np.abs(o["obj"][ok]))).max() < 1e-6
+
+
+# every launch shape, forced by the execution knobs on an ordinary batch: (H, threads_per_instance, environment)
+FORCED_SHAPES = {"replan30_64": (10, 64, {}), "replan30": (10, 256, dict(HDSM_DUO_MIN="0")),
+                 "duo": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="0", HDSM_QUAD_MIN="0")),
+                 "tri": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="1", HDSM_QUAD_MIN="0")),
+                 "quad": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="1", HDSM_QUAD_MIN="1")),
+                 "replan48_64": (15, 64, {}), "replan48": (15, 256, dict(HDSM_DUO_MIN="0")), "duo48": (15, 256, dict(HDSM_DUO_MIN="1"))}
+
+
+@pytest.mark.parametrize("shape", list(FORCED_SHAPES))
+def test_every_launch_shape_matches_the_oracle(hdsm, oracle, monkeypatch, shape):
+    """Each of the eight k_replan* launch shapes (tests/test_wave_shapes.py: the same batches through their CPU execution) picked on
+    purpose for one batch that narrows, turns, is chamfered and has neighbours without a plan — until now only the fuzz reached some
+    of them, by chance."""
+    from test_wave_shapes import _mixed_batch
+    import staging_cases as sc
+    n_hor, threads, env = FORCED_SHAPES[shape]
+    prm = make_params(n_hor=n_hor, max_rows_static=18, poly_hor=4, threads_per_instance=threads)
+    args = _mixed_batch(prm, 16, 310 if n_hor == 10 else 317, every=2 if n_hor == 10 else 4)
+    o = sc.verdict(oracle, prm, args, n_threads=32)
+    for k_, v in env.items():
+        monkeypatch.setenv(k_, v)
+    sol = hdsm.Solver(prm, args[1].shape[0], args[7].shape[0])
+    for k_ in env:
+        monkeypatch.delenv(k_)
+    g = sol.replan(*args)
+    assert (g["status"] == o["status"]).all(), (g["status"], o["status"])
+    ok = o["status"] == 0
+    assert ok.any() and np.abs(g["traj"] - o["traj"])[ok].max() < 1e-6
+    assert (np.abs(g["obj"] - o["obj"])[ok] / np.maximum(1, np.abs(o["obj"][ok]))).max() < 1e-8

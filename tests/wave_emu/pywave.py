@@ -29,7 +29,35 @@ def new_warm_store(n_inst):
     return np.zeros((n_inst, MAXNV + 2), dtype=np.int32)
 
 
-def replan(prm, agent_id, state, ref, n_poly, n_rows, A, b, plans, has_plan, warm=None, bounds_min=256, threads=64, cmax=0, split_budget=0):
+_shapes = None
+
+
+def wave_shapes():
+    """The launch shapes the emulator runs: [{name, kernel, nv, cmax, small, threads}]. `kernel` names the k_replan* kernel of
+    libhdsm.so that has exactly this (NV, CMAX, SMALL, threads) tuple (hdsm_shapes.h); "-" marks a shape that exists here only."""
+    global _shapes
+    if _shapes is None:
+        L = lib()
+        L.wave_shapes.restype = C.c_char_p
+        _shapes = []
+        for ln in L.wave_shapes().decode().splitlines():
+            name, kernel, nv, cmax, small, threads = ln.split()
+            _shapes.append(dict(name=name, kernel=kernel, nv=int(nv), cmax=int(cmax), small=bool(int(small)), threads=int(threads)))
+    return [dict(s) for s in _shapes]
+
+
+def replan(prm, agent_id, state, ref, n_poly, n_rows, A, b, plans, has_plan, warm=None, bounds_min=256, threads=64, cmax=0, split_budget=0,
+           shape=None):
+    """Level-2 replan through the device source. shape: a name of wave_shapes() — runs exactly that (NV, CMAX, SMALL, threads)
+    tuple (threads / cmax are then taken from it); otherwise the `threads` / `cmax` spellings of wave_emu.cpp. The result also
+    holds `peak`: per instance, the largest count of staged rows any sweep reached, counted past the capacity."""
+    shape_idx = -1
+    if shape is not None:
+        names = [s["name"] for s in wave_shapes()]
+        if shape not in names:
+            raise ValueError("unknown shape %r (wave_shapes(): %s)" % (shape, ", ".join(names)))
+        shape_idx = names.index(shape)
+        threads, cmax = wave_shapes()[shape_idx]["threads"], wave_shapes()[shape_idx]["cmax"]
     N, P = prm.n_hor, prm.poly_hor
     f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
@@ -48,10 +76,15 @@ def replan(prm, agent_id, state, ref, n_poly, n_rows, A, b, plans, has_plan, war
                            _p(A, d), _p(b, d), _p(plans, d), _p(has_plan, u), _p(out["traj"], d), _p(out["ctrl"], d),
                            _p(out["used"], u), _p(out["status"], i), _p(out["obj"], d), _p(out["qp_iters"], i), _p(out["nodes"], i),
                            _p(out["sweeps"], i), _p(out["cand"], i), _p(out["flags"], C.c_uint32),
-                           _p(warm, i) if warm is not None else None, C.c_int32(bounds_min), C.c_int32(threads), C.c_int32(cmax), C.c_int32(split_budget))
+                           _p(warm, i) if warm is not None else None, C.c_int32(bounds_min), C.c_int32(threads), C.c_int32(cmax), C.c_int32(split_budget),
+                           C.c_int32(shape_idx))
     if rc == -100:
         raise RuntimeError("wavefront emulation: " + lib().wave_last_error().decode())
+    if rc == -3:
+        raise ValueError("shape %r cannot hold n = %d (or its small layout these polyhedra)" % (shape, 3 * N))
     assert rc == 0, rc
+    out["peak"] = np.zeros(n_inst, dtype=np.int32)
+    assert lib().wave_stage_peaks(_p(out["peak"], C.c_int32), C.c_int32(n_inst)) == 0
     return out
 
 

@@ -49,6 +49,8 @@ struct Runtime {
   long long clock = 0;
   long ops = 0;
   long by_kind[12] = {0};    // lockstep points by kind (1 barrier, 2 readlane, 3 ballot, 4/5 shuffle, 6 DPP, 7/8 permlane32_swap, 9 wsync)
+  bool yield_atomics = false;  // WEMU_YIELD_ATOMICS=1: every atomic operation lets the other threads run first (atomic_point)
+  long atomic_yields = 0;    // ... and counts as progress for the deadlock detector
 #ifdef WEMU_DEBUG
   void* bt[MAXT][12];
   int nbt[MAXT];
@@ -57,6 +59,19 @@ struct Runtime {
 Runtime& rt();
 void yield();                  // back to the scheduler
 [[noreturn]] void fail(const char* what);
+// Staging-slot audit (wave_emu.cpp): the hooks of hdsm_wave_gi.h's sweep. Every slot claimed inside a sweep is counted; at its end
+// no slot may have two writers (the slots held when it began count as written), and a sweep that did not overflow must have written every
+// slot between its start and end counts once.
+void stage_audit_begin(int ncand, int ncold, int cmax);
+void stage_audit_claim(int slot, bool fits);
+void stage_audit_end(int ncand, int ncold, int cmax);
+// an atomic operation: on the device the other lanes of the wavefront (and the other wavefronts) execute the same instruction in the
+// same cycles, so in WEMU_YIELD_ATOMICS mode the calling thread lets every other thread run up to its own next atomic or
+// rendezvous before it goes on — between the increment of one counter and the read of the other in stage_slot, for instance
+inline void atomic_point() {
+  Runtime& r = rt();
+  if (r.yield_atomics) ++r.atomic_yields, yield();
+}
 inline int lane() { return rt().cur & (W - 1); }
 inline Wave& my_wave() { return rt().wave[rt().cur / W]; }
 
@@ -149,21 +164,25 @@ inline int __ffsll(long long v) { return __builtin_ffsll(v); }
 inline long long clock64() { return ++wemu::rt().clock; }
 inline long long wall_clock64() { return ++wemu::rt().clock; }
 inline int atomicAdd(int* p, int v) {
+  wemu::atomic_point();
   const int old = *p;
   *p = old + v;
   return old;
 }
 inline int atomicCAS(int* p, int cmp, int val) {
+  wemu::atomic_point();
   const int old = *p;
   if (old == cmp) *p = val;
   return old;
 }
 inline int atomicExch(int* p, int v) {
+  wemu::atomic_point();
   const int old = *p;
   *p = v;
   return old;
 }
 inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) {
+  wemu::atomic_point();
   const unsigned long long old = *p;
   if (v < old) *p = v;
   return old;
@@ -171,21 +190,32 @@ inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v)
 #define __ATOMIC_RELAXED_SHIM 0
 #define __HIP_MEMORY_SCOPE_AGENT 4
 #define __HIP_MEMORY_SCOPE_WORKGROUP 2
-#define __hip_atomic_load(ptr, order, scope) (*(volatile decltype(ptr))(ptr))
+template <class T>
+inline T wemu_atomic_load(T* p) {
+  wemu::atomic_point();
+  return *(volatile T*)p;
+}
+#define __hip_atomic_load(ptr, order, scope) wemu_atomic_load(ptr)
+#define HDSM_STAGE_AUDIT_BEGIN(ncand, ncold, cmax) wemu::stage_audit_begin((ncand), (ncold), (cmax))
+#define HDSM_STAGE_AUDIT_CLAIM(slot, fits) wemu::stage_audit_claim((slot), (fits))
+#define HDSM_STAGE_AUDIT_END(ncand, ncold, cmax) wemu::stage_audit_end((ncand), (ncold), (cmax))
 #define __hip_atomic_store(ptr, val, order, scope) (*(volatile decltype(ptr))(ptr) = (val))
 #define __builtin_amdgcn_s_sleep(n) ((void)0)
 #define __threadfence() ((void)0)
 inline unsigned atomicOr(unsigned* p, unsigned v) {
+  wemu::atomic_point();
   const unsigned old = *p;
   *p = old | v;
   return old;
 }
 inline unsigned atomicAnd(unsigned* p, unsigned v) {
+  wemu::atomic_point();
   const unsigned old = *p;
   *p = old & v;
   return old;
 }
 inline unsigned atomicAdd(unsigned* p, unsigned v) {
+  wemu::atomic_point();
   const unsigned old = *p;
   *p = old + v;
   return old;

@@ -8,11 +8,13 @@
 #include <ucontext.h>
 
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../../multi_agent_pkgs_amd/csrc/hdsm_consts.h"
 #include "../../multi_agent_pkgs_amd/csrc/hdsm_core.h"
 #include "../../multi_agent_pkgs_amd/csrc/hdsm_level1.h"
+#include "../../multi_agent_pkgs_amd/csrc/hdsm_shapes.h"
 
 namespace wemu {
 namespace {
@@ -40,6 +42,43 @@ void trampoline() {
 }  // namespace
 
 Runtime& rt() { return g_rt; }
+
+// ---- staging-slot audit (the hooks of hdsm_wave_gi.h's sweep) ----
+int g_writers[4096];          // writers of each slot since the sweep began (Shm: CMAX <= 4096)
+bool g_sweep_open = false;
+int g_sweep_ncand = 0, g_sweep_ncold = 0;
+int g_stage_peak = 0;         // largest ncand + ncold any sweep of the instance reached, counted past the capacity (before the clamp)
+long g_claims = 0;            // claims audited (all instances since the library was loaded)
+void stage_audit_begin(int ncand, int ncold, int cmax) {
+  // the slots the lists hold when the sweep begins count as written once: a claim of one of them is a second writer
+  for (int k = 0; k < 4096; ++k) g_writers[k] = (k < ncand || (k >= cmax - ncold && k < cmax)) ? 1 : 0;
+  g_sweep_open = true, g_sweep_ncand = ncand, g_sweep_ncold = ncold;
+}
+void stage_audit_claim(int slot, bool fits) {
+  if (!g_sweep_open || !fits) return;
+  ++g_claims;
+  if (slot < 0 || slot >= 4096) fail("stage_slot gave a slot outside the staging area");
+  if (++g_writers[slot] > 1) fail("two writers claimed one staging slot in one sweep");
+}
+void stage_audit_end(int ncand, int ncold, int cmax) {
+  if (!g_sweep_open) return;
+  g_sweep_open = false;
+  g_stage_peak = ncand + ncold > g_stage_peak ? ncand + ncold : g_stage_peak;
+  // the slots every claim of the sweep must have filled: all of both ranges if the lists did not meet; if only one list grew, the
+  // part of its range below the other list (those claims read a constant other counter)
+  const bool met = ncand + ncold > cmax, hot_only = ncold == g_sweep_ncold, cold_only = ncand == g_sweep_ncand;
+  const int hot_end = !met ? ncand : (hot_only ? cmax - ncold : g_sweep_ncand);
+  const int cold_lo = !met ? cmax - ncold : (cold_only ? (cmax - ncold > ncand ? cmax - ncold : ncand) : cmax - g_sweep_ncold);
+  for (int k = 0; k < cmax; ++k) {
+    const bool want = k < hot_end || k >= cold_lo;  // (the slots held at the start included)
+    if (want && g_writers[k] != 1) {
+      snprintf(g_error, sizeof g_error, "staging slot %d of [0, %d) + [%d, %d) written %d times (counts %d + %d from %d + %d, capacity %d)", k,
+               hot_end, cold_lo, cmax, g_writers[k], ncand, ncold, g_sweep_ncand, g_sweep_ncold, cmax);
+      g_failed = true;
+      for (;;) swapcontext(&g_ctx[g_rt.cur], &g_main);
+    }
+  }
+}
 void yield() { swapcontext(&g_ctx[g_rt.cur], &g_main); }
 void fail(const char* what) {
   snprintf(g_error, sizeof g_error, "%s (thread %d, lockstep point %ld)", what, g_rt.cur, g_rt.ops);
@@ -55,6 +94,7 @@ bool run_block(void (*body)(void*), void* arg, int block_index, int nthreads) {
   r.block = {(unsigned)nthreads, 1, 1};
   r.bidx = {(unsigned)block_index, 0, 0};
   r.b_nlive = nthreads;
+  r.yield_atomics = getenv("WEMU_YIELD_ATOMICS") != nullptr && getenv("WEMU_YIELD_ATOMICS")[0] == '1';
   for (int w = 0; w < nthreads / W; ++w) r.wave[w].nlive = W;
   g_body = body, g_arg = arg, g_failed = false;
   if (g_stacks.size() != STACK * MAXT) g_stacks.assign(STACK * MAXT, 0);
@@ -68,19 +108,20 @@ bool run_block(void (*body)(void*), void* arg, int block_index, int nthreads) {
     makecontext(&g_ctx[l], trampoline, 0);
   }
   long idle_rounds = 0;
+  // (WEMU_ORDER=reverse: the wavefronts of the workgroup take their turns in the opposite order — what runs between two barriers must
+  // not depend on which wave gets there first; a result that changes with the order is a data race between wavefronts. Read per
+  // workgroup, so that a test can switch it in-process.)
+  const bool reverse = getenv("WEMU_ORDER") != nullptr && getenv("WEMU_ORDER")[0] == 'r';
   while (r.b_nlive > 0 && !g_failed) {
-    const long ops = r.ops;
+    const long ops = r.ops + r.atomic_yields;  // (a thread that yielded at an atomic operation goes on at its next turn: progress)
     const int live = r.b_nlive;
-    // (WEMU_ORDER=reverse: the wavefronts of the workgroup take their turns in the opposite order — what runs between two barriers must
-    // not depend on which wave gets there first; a result that changes with the order is a data race between wavefronts)
-    static const bool reverse = getenv("WEMU_ORDER") != nullptr && getenv("WEMU_ORDER")[0] == 'r';
     for (int l0 = 0; l0 < nthreads && !g_failed; ++l0) {
       const int nw = nthreads / W, l = reverse ? ((nw - 1 - l0 / W) * W + l0 % W) : l0;
       if (g_done[l]) continue;
       r.cur = l;
       swapcontext(&g_main, &g_ctx[l]);
     }
-    if (r.ops == ops && r.b_nlive == live) {
+    if (r.ops + r.atomic_yields == ops && r.b_nlive == live) {
       if (++idle_rounds > 4) {
         snprintf(g_error, sizeof g_error, "deadlock: %d of %d threads wait at __syncthreads(), wavefront 0 has %d of %d lanes at a cross-lane operation",
                  r.b_arrived, r.b_nlive, r.wave[0].arrived, r.wave[0].nlive);
@@ -96,6 +137,8 @@ const char* last_error() { return g_error; }
 }  // namespace wemu
 
 namespace {
+std::vector<int32_t> g_peaks;  // per instance of the last wave_replan (pass 1): wemu::g_stage_peak
+
 template <int NV, int CMAX, bool SMALL = false>
 struct Job {
   typename hdsm::Solver<NV, CMAX, SMALL>::S* s;
@@ -146,7 +189,9 @@ int run_all(const hdsm::Consts& c, hdsm::Args& a, int nthreads) {
     memset(static_cast<void*>(shm.get()), 0, sizeof(typename Sol::S));
     Job<NV, CMAX, SMALL> job{shm.get(), &c, a, k, k, -1};
     job.a.scratch = a.split_budget > 0 ? pass1_scratch : scratch.data() - (int64_t)k * a.scratch_stride;  // solve_instance adds out * stride
+    wemu::g_stage_peak = 0, wemu::g_sweep_open = false;
     if (!wemu::run_block(body<NV, CMAX, SMALL>, &job, k, nthreads)) return -100;
+    if (k < (int)g_peaks.size()) g_peaks[k] = wemu::g_stage_peak;
     if (getenv("WEMU_OPS")) fprintf(stderr, "instance %d: %ld lockstep points (barrier %ld, readlane %ld, ballot %ld, dpp %ld, permlane %ld, wsync %ld), %d active-set operations\n", k, wemu::rt().ops, wemu::rt().by_kind[1], wemu::rt().by_kind[2], wemu::rt().by_kind[3], wemu::rt().by_kind[6], wemu::rt().by_kind[7] + wemu::rt().by_kind[8], wemu::rt().by_kind[9], a.st_iters ? a.st_iters[k] : -1);
   }
   if (a.split_budget > 0) {
@@ -185,18 +230,70 @@ int run_all(const hdsm::Consts& c, hdsm::Args& a, int nthreads) {
 
 extern "C" const char* wave_last_error(void) { return wemu::last_error(); }
 
+// The launch shapes this library runs, (kernel, NV, CMAX, SMALL, threads): every k_replan* kernel hdsm_api.hip instantiates, with the
+// capacities of hdsm_shapes.h, and a few that exist here only (kernel "-"). tests/test_wave_shapes.py holds the first part against the
+// kernel symbols of the built libhdsm.so.
+#define WEMU_SHAPES(X)                                                                                                        \
+  X("replan30_64", "k_replan", 32, hdsm::CMAX30, false, 64)                                                                  \
+  X("replan30", "k_replan", 32, hdsm::CMAX30, false, 256)                                                                    \
+  X("replan48_64", "k_replan", 48, hdsm::CMAX48, false, 64)                                                                  \
+  X("replan48", "k_replan", 48, hdsm::CMAX48, false, 256)                                                                    \
+  X("duo", "k_replan_duo", 32, hdsm::CMAX_DUO, false, 256)                                                                   \
+  X("tri", "k_replan_tri", 32, hdsm::CMAX_TRI, false, 128)                                                                   \
+  X("quad", "k_replan_quad", 32, hdsm::CMAX_QUAD, true, 128)                                                                 \
+  X("duo48", "k_replan_duo48", 48, hdsm::CMAX_DUO48, false, 128)                                                             \
+  X("duo48_320", "-", 48, 320, false, 128) /* the 320-row instantiation the library had until round 6 (hdsm_api.hip) */     \
+  X("tiny30", "-", 32, 16, false, 64)      /* room for 16 staged rows: the overflow path at any size */                      \
+  X("tiny48", "-", 48, 16, false, 64)
+
+namespace {
+struct ShapeRow {
+  const char *name, *kernel;
+  int nv, cmax, small, threads;
+};
+#define WEMU_SHAPE_ROW(name, kernel, nv, cmax, small, threads) {name, kernel, nv, cmax, small ? 1 : 0, threads},
+const ShapeRow kShapes[] = {WEMU_SHAPES(WEMU_SHAPE_ROW)};
+constexpr int kNumShapes = sizeof kShapes / sizeof kShapes[0];
+// shape `k` of kShapes: its (NV, CMAX, SMALL) instantiation of the solver
+int run_shape(int k, const hdsm::Consts& c, hdsm::Args& a, int threads) {
+  int i = 0;
+#define WEMU_SHAPE_RUN(name, kernel, nv, cmax, small, thr) \
+  if (k == i++) return run_all<nv, cmax, small>(c, a, threads);
+  WEMU_SHAPES(WEMU_SHAPE_RUN)
+  return -1;
+}
+}  // namespace
+
+// one line per shape: "name kernel NV CMAX SMALL threads"
+extern "C" const char* wave_shapes(void) {
+  static std::string text;
+  if (text.empty())
+    for (const ShapeRow& r : kShapes) text += std::string(r.name) + " " + r.kernel + " " + std::to_string(r.nv) + " " + std::to_string(r.cmax) + " " +
+                                             std::to_string(r.small) + " " + std::to_string(r.threads) + "\n";
+  return text.c_str();
+}
+
+// per instance of the last wave_replan: the largest count of staged rows (hot + cold) a sweep reached, counted past the capacity
+extern "C" int wave_stage_peaks(int32_t* out, int32_t n) {
+  if (n > (int)g_peaks.size()) return -1;
+  memcpy(out, g_peaks.data(), sizeof(int32_t) * n);
+  return 0;
+}
+
 // Level-2 replan through the device source. `warm` = the handle's warm-start store, [(MAXNV + 2) * n_inst] int32, in/out (zeros:
 // cold; pass the same array again to continue like consecutive launches on one handle); null = warm start off.
 // `bounds_min`: swarms of at least this many agents get the sphere prefilter records, as hdsm_api.hip's launch() does.
 // `cmax` in 1..16: a build of the kernel with room for only 16 staged rows (staging-overflow tests); 256: the small LDS layout of the
-// four-per-CU kernel; 0 = the product's one-per-CU sizes.
+// four-per-CU kernel; 0 = the product's one-per-CU sizes. `shape` >= 0: exactly line `shape` of wave_shapes() — its NV, CMAX,
+// layout and thread count (`threads` and `cmax` must agree with it); an n that the shape's NV cannot hold is refused (-3).
 extern "C" int wave_replan(const hdsm_params* prm, int32_t n_inst, int32_t n_rob, const int32_t* agent_id, const double* state_curr,
                            const double* traj_ref, const int32_t* n_poly, const int32_t* n_rows_static, const double* A_static,
                            const double* b_static, const double* plans_all, const uint8_t* has_plan, double* traj_out, double* ctrl_out,
                            uint8_t* poly_used, int32_t* status, double* obj, int32_t* qp_iters, int32_t* nodes, int32_t* sweeps,
                            int32_t* cand, uint32_t* flags, int32_t* warm, int32_t bounds_min, int32_t threads, int32_t cmax,
-                           int32_t split_budget) {
+                           int32_t split_budget, int32_t shape) {
   if (threads != 64 && threads != 128 && threads != 256) return -1;
+  if (shape >= kNumShapes || (shape >= 0 && (kShapes[shape].threads != threads || kShapes[shape].cmax != cmax))) return -2;
   auto c = std::make_unique<hdsm::Consts>();
   const char* err = nullptr;
   int rc = hdsm::build_consts(prm, c.get(), &err);
@@ -238,6 +335,12 @@ extern "C" int wave_replan(const hdsm_params* prm, int32_t n_inst, int32_t n_rob
   a.bounds = (n_rob >= bounds_min) ? bounds.data() : nullptr;
   a.warm = (prm->warm_start && warm) ? warm : nullptr;
   a.split_budget = split_budget;
+  g_peaks.assign(n_inst, 0);
+  if (shape >= 0) {
+    if ((kShapes[shape].nv == 32) != (c->n <= hdsm::SPLIT_N_MAX)) return -3;  // (the product's rule: NV = 32 for n <= 30, 48 beyond)
+    if (kShapes[shape].small && !(c->P <= 4 && c->RS <= 20)) return -3;
+    return run_shape(shape, *c, a, threads);
+  }
   if (cmax > 0 && cmax <= 16)  // tiny staging capacity: exercises the overflow path in tests
     return c->n <= hdsm::SPLIT_N_MAX ? run_all<32, 16>(*c, a, threads) : run_all<48, 16>(*c, a, threads);
   if (cmax == 256 && c->n <= hdsm::SPLIT_N_MAX && c->P <= 4 && c->RS <= 20)  // the four-workgroups-per-CU shape: small LDS layout, 256 staged rows
