@@ -148,6 +148,35 @@ int hdsm_swarm_get_paths(void* swarm, int32_t pmax, double* paths, int32_t* n_pa
  * cut after pmax points, which changes nothing as long as the kept part is longer than n_hor * path_vel_max * dt (checked:
  * otherwise HDSM_ERR_CAPACITY). */
 int hdsm_swarm_reference_inputs_n(void* swarm, int32_t pmax, double* path, int32_t* n_path);
+/* ---- the path step (ABI 1.4): Agent::UpdatePath (AC:261-454) and GoalCallback (AC:2380-2388) ----------------------------------
+ * A stated stand-in for the reference's JPS3D + DMP + ShortenDMPPath (csrc/path_core.h; not its output): on the agent's local grid
+ * (the corridor's window of the world, ClearBoundary AC:1819-1854 applied), from S = the point the reference polyline starts from this
+ * round towards GetIntermediateGoal(goal) (AC:1891-1941): a 6-connected BFS from the goal voxel, a descent from the start voxel, a
+ * greedy line-of-sight shortening with the reference's Raycast. With no world the path is [S, goal]. Status per agent: 0 a new path
+ * (replaces path_curr_), 1 no free voxel within 6 of the start or goal voxel, 2 goal unreachable in the local grid, 3 more than 48
+ * points, 4 local grid or descent beyond the device workspace. On a non-zero status the agent keeps its path.
+ *   hdsm_swarm_set_goals        goals [n_local][3]; the agents whose goal changed plan a new path at the start of the next round
+ *   hdsm_swarm_set_path_period  0 (default) never; k: every agent plans a new path every k-th round, the first at the next round.
+ *                               The step runs at the start of a round, before the corridor, in whichever of
+ *                               hdsm_swarm_prepare_corridor / hdsm_swarm_prepare builds the corridor. The period and the round phase
+ *                               go into hdsm_dswarm_create and come back with hdsm_dswarm_download(swarm).
+ *   hdsm_swarm_replan_paths     every local agent now; n_failed (may be NULL) = agents with a non-zero status
+ *   hdsm_swarm_path_errors      agents whose last path step failed; codes[n_local] (may be NULL) the status per agent
+ * The stand-alone batch (hdsm_poly_octa3d_batch's pattern): for case t the local grid ldim at off[t] in the world (wdim, NULL = free
+ * space), ground_k[t], origin[t][3], start[t][3], goal[t][3], voxel size res -> paths[t][pmax][3] (rows beyond n_path[t] repeat the
+ * last point; zeros on failure), n_path[t], status[t]. hdsm_local_path_batch plans on `device` (one workgroup per case, host pointers
+ * in and out), hdsm_local_path_host on the CPU; the two agree bit for bit. HDSM_ERR_CAPACITY if some n_path > pmax.          */
+int hdsm_swarm_set_goals(void* swarm, const double* goals);
+int hdsm_swarm_set_path_period(void* swarm, int32_t period);
+int hdsm_swarm_replan_paths(void* swarm, int32_t* n_failed);
+int hdsm_swarm_path_errors(void* swarm, int32_t* codes);
+int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                          const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, int32_t pmax,
+                          double* paths, int32_t* n_path, int32_t* status);
+int hdsm_local_path_host(int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                         const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, int32_t pmax,
+                         double* paths, int32_t* n_path, int32_t* status);
+
 /* Number of local agents whose corridor generation failed in the last hdsm_swarm_prepare (seed outside the local grid, or a
  * polyhedron with more rows than max_rows_static); codes[n_local] (may be NULL) receives the hdsm_error per agent. Those
  * agents kept the polyhedra they had. */
@@ -169,7 +198,8 @@ int hdsm_swarm_prepare_corridor(void* swarm);
  * and copies out what the caller asks for (any pointer may be NULL): the agent states back into the host mirror `swarm`
  * (so that every hdsm_swarm_* diagnostic works on them), the all-gathered plans [world_size * per][N+1][9] and flags, the
  * statuses of the last round, the number of instances without solution so far.
- * The world and the configuration are those of the host mirror at hdsm_dswarm_create and stay fixed for the dswarm's life (the
+ * The world and the configuration are those of the host mirror at hdsm_dswarm_create and stay fixed for the dswarm's life; the
+ * global paths too, unless the path step is on (hdsm_swarm_set_path_period, hdsm_dswarm_set_goals: see below) (the
  * device corridor keeps each agent's last polyhedra and forms the rows of one that is asked for again from them instead of
  * growing it again — same rows, bit for bit; environment HDSM_POLY_CACHE=0 switches that off, for A/B runs). */
 int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_size, void** dswarm);
@@ -191,6 +221,15 @@ int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]);
  * from a structure recorded in the same local grid, out[2] from one recorded in another grid at the same height (the interior
  * rule), out[3] 1 if the cache is on (a world is set and HDSM_POLY_CACHE is not 0). Synchronises the device. */
 int hdsm_dswarm_cache_stats(void* dswarm, int64_t out[4]);
+
+/* The path step on the device (k_path: one workgroup per due agent, the BFS as bit planes in LDS; launched before k_corridor only
+ * in rounds where some agent is due). hdsm_dswarm_set_goals: goals [n_local][3], the changed agents plan at the next round
+ * (synchronises the device). hdsm_dswarm_path_stats: out[0] agents planned, out[1] of them failed, out[2] launches of k_path since
+ * hdsm_dswarm_create (synchronises). hdsm_dswarm_last_path_ms: with phase timing on, the duration of the last timed round's k_path
+ * (0 if that round planned nothing); hdsm_dswarm_last_phase_ms's [0] k_corridor starts after it. */
+int hdsm_dswarm_set_goals(void* dswarm, const double* goals);
+int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]);
+int hdsm_dswarm_last_path_ms(void* dswarm, float* ms);
 
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between

@@ -1316,7 +1316,7 @@ int check_common(Handle* h, int n_inst, int n_rob) {
 
 extern "C" {
 
-int32_t hdsm_version(void) { return (1 << 16) | 3; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister
+int32_t hdsm_version(void) { return (1 << 16) | 4; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister; 1.4: + the path step (hdsm_swarm_set_goals / _set_path_period / _replan_paths / _path_errors, hdsm_local_path_batch / _host, hdsm_dswarm_set_goals / _path_stats / _last_path_ms)
 
 const char* hdsm_last_error(void) { return g_err.c_str(); }
 

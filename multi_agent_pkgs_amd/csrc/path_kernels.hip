@@ -1,0 +1,104 @@
+// path_kernels.hip — the path step of path_core.h as a stand-alone batch on the device (hdsm_local_path_batch): one workgroup per
+// case, the same block planner (hdsm_path::plan_block) as the device-resident loop's k_path, host pointers in and out.
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "../../include/hdsm_swarm.h"
+#include "path_core.h"
+
+extern "C" int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                                       const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res,
+                                       void* problem);
+
+namespace {
+
+struct BatchArgs {
+  const int8_t* world;
+  int32_t wdim[3], ldim[3];
+  const int32_t *off, *ground_k;
+  const double *origin, *start, *goal;
+  double res;
+  int32_t pmax;
+  double* paths;
+  int32_t *n_path, *status;
+};
+
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_path_batch(BatchArgs a) {
+  __shared__ hdsm_path::PathLds lds;
+  const int t = (int)blockIdx.x, tid = (int)threadIdx.x;
+  hdsm_path::PathIn in;
+  in.g.world = a.world;
+  for (int ax = 0; ax < 3; ++ax) {
+    in.g.wdim[ax] = a.world ? a.wdim[ax] : 0, in.g.dim[ax] = a.ldim[ax], in.g.off[ax] = a.off[3 * (size_t)t + ax];
+    in.origin[ax] = a.origin[3 * (size_t)t + ax], in.start[ax] = a.start[3 * (size_t)t + ax], in.goal[ax] = a.goal[3 * (size_t)t + ax];
+  }
+  in.g.ground_k = a.ground_k[t];
+  in.res = a.res;
+  const int st = hdsm_path::plan_block(in, lds, tid);
+  const int np = st == hdsm_path::PATH_OK ? lds.n_out : 0;
+  if (tid == 0) a.status[t] = st, a.n_path[t] = np;
+  for (int e = tid; e < 3 * a.pmax; e += hdsm_path::THREADS) {
+    const int i = e / 3;
+    a.paths[(size_t)t * a.pmax * 3 + e] = np ? lds.out[i < np ? i : np - 1][e % 3] : 0.0;
+  }
+}
+
+}  // namespace
+
+extern "C" int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3],
+                                     const int32_t* off, const int32_t* ground_k, const double* origin, const double* start, const double* goal,
+                                     double res, int32_t pmax, double* paths, int32_t* n_path, int32_t* status) {
+  if (n < 0 || !ldim || !off || !ground_k || !origin || !start || !goal || !(res > 0) || pmax < 2 || !paths || !n_path || !status ||
+      (world && !wdim))
+    return HDSM_ERR_BAD_ARG;
+  if (n == 0) return HDSM_OK;
+  if (pmax > hdsm_sw::PATH_PTS) {  // (the device keeps PATH_PTS points: the rows beyond repeat the last point, as on the host)
+    std::vector<double> tmp((size_t)n * hdsm_sw::PATH_PTS * 3);
+    const int rc = hdsm_local_path_batch(device, n, world, wdim, ldim, off, ground_k, origin, start, goal, res, hdsm_sw::PATH_PTS, tmp.data(),
+                                         n_path, status);
+    if (rc) return rc;
+    for (int t = 0; t < n; ++t)
+      for (int i = 0; i < pmax; ++i)
+        for (int c = 0; c < 3; ++c)
+          paths[((size_t)t * pmax + i) * 3 + c] = tmp[((size_t)t * hdsm_sw::PATH_PTS + (i < hdsm_sw::PATH_PTS ? i : hdsm_sw::PATH_PTS - 1)) * 3 + c];
+    return HDSM_OK;
+  }
+  if (hipSetDevice(device) != hipSuccess) return HDSM_ERR_NO_DEVICE;
+  const size_t wbytes = world ? (size_t)wdim[0] * wdim[1] * wdim[2] : 0;
+  BatchArgs a{};
+  a.res = res, a.pmax = pmax;
+  for (int ax = 0; ax < 3; ++ax) a.wdim[ax] = world ? wdim[ax] : 0, a.ldim[ax] = ldim[ax];
+  int8_t* d_world = nullptr;
+  int32_t *d_off = nullptr, *d_gk = nullptr, *d_np = nullptr, *d_st = nullptr;
+  double *d_org = nullptr, *d_s = nullptr, *d_g = nullptr, *d_paths = nullptr;
+  hipError_t e = hipSuccess;
+  auto ok = [&](hipError_t r) {
+    if (e == hipSuccess) e = r;
+  };
+  const size_t N = (size_t)n;
+  if (world) ok(hipMalloc(&d_world, wbytes));
+  ok(hipMalloc(&d_off, N * 12)), ok(hipMalloc(&d_gk, N * 4)), ok(hipMalloc(&d_np, N * 4)), ok(hipMalloc(&d_st, N * 4));
+  ok(hipMalloc(&d_org, N * 24)), ok(hipMalloc(&d_s, N * 24)), ok(hipMalloc(&d_g, N * 24)), ok(hipMalloc(&d_paths, N * pmax * 24));
+  if (e == hipSuccess) {
+    if (world) ok(hipMemcpy(d_world, world, wbytes, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_off, off, N * 12, hipMemcpyHostToDevice)), ok(hipMemcpy(d_gk, ground_k, N * 4, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_org, origin, N * 24, hipMemcpyHostToDevice)), ok(hipMemcpy(d_s, start, N * 24, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_g, goal, N * 24, hipMemcpyHostToDevice));
+  }
+  if (e == hipSuccess) {
+    a.world = d_world, a.off = d_off, a.ground_k = d_gk, a.origin = d_org, a.start = d_s, a.goal = d_g;
+    a.paths = d_paths, a.n_path = d_np, a.status = d_st;
+    hipLaunchKernelGGL(k_path_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a);
+    ok(hipGetLastError());
+    ok(hipDeviceSynchronize());
+  }
+  if (e == hipSuccess) {
+    ok(hipMemcpy(paths, d_paths, N * pmax * 24, hipMemcpyDeviceToHost));
+    ok(hipMemcpy(n_path, d_np, N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(status, d_st, N * 4, hipMemcpyDeviceToHost));
+  }
+  void* ptrs[] = {d_world, d_off, d_gk, d_np, d_st, d_org, d_s, d_g, d_paths};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  return e == hipSuccess ? HDSM_OK : HDSM_ERR_DEVICE;
+}

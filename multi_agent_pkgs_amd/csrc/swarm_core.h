@@ -88,7 +88,7 @@ struct AgentS {
   int32_t n_poly, increment;    // poly_const_vec_.size(), increment_traj_ref_
   Poly polys[hdsm::MAXP];
   uint8_t poly_used[hdsm::MAXP];
-  int32_t external_ref, n_fail, corridor_rc, pad;
+  int32_t external_ref, n_fail, corridor_rc, path_rc;  // path_rc: status of the last path update (path_core.h)
   double path_vel;
 };
 
@@ -408,10 +408,10 @@ CD_HD double rc_intbound(double s, double ds) {  // raycast.cpp:11-20: smallest 
 CD_HD int rc_signum(int x) { return x == 0 ? 0 : (x < 0 ? -1 : 1); }
 
 // voxel_grid_util::Raycast (raycast.cpp:22-183, Amanatides-Woo with the reference's modifications) from `start` to `end`, both
-// in LOCAL VOXEL units. visit(pt) is called for every point the reference appends to its output (the real intersection points
+// in LOCAL VOXEL units (`g`: inside(i, j, k) and value(i, j, k), 100 = occupied). visit(pt) is called for every point the reference appends to its output (the real intersection points
 // with the voxel boundaries), in order. Returns true when the ray hit an occupied voxel; `hit` = the collision point.
-template <class F>
-CD_HD bool raycast(const RawWindow& g, const V3& start, const V3& end, double max_dist, V3* hit, F visit) {
+template <class G, class F>
+CD_HD bool raycast(const G& g, const V3& start, const V3& end, double max_dist, V3* hit, F visit) {
   int x = (int)floor(start[0]), y = (int)floor(start[1]), z = (int)floor(start[2]);
   const int ex = (int)floor(end[0]), ey = (int)floor(end[1]), ez = (int)floor(end[2]);
   const double max2 = max_dist * max_dist;

@@ -18,6 +18,7 @@
 
 #include "../../include/hdsm_stats.h"
 #include "../../include/hdsm_swarm.h"
+#include "path_core.h"
 #include "swarm_core.h"
 
 namespace {
@@ -68,6 +69,11 @@ struct Swarm {
   std::chrono::steady_clock::time_point t_round{};
   long long round_idx = 0;
   bool corridor_done = false;  // hdsm_swarm_prepare_corridor already ran this round
+  // the path step (path_core.h; hdsm_swarm_set_path_period / hdsm_swarm_set_goals): every agent is due in rounds with
+  // path_round % path_period == 0 (period 0: never), an agent whose goal changed in the next round
+  int path_period = 0;
+  long long path_round = 0;
+  std::vector<uint8_t> path_due;
   ~Swarm() {
     for (AgentX& a : extra) hdsm_stats_destroy(a.stats);
   }
@@ -362,6 +368,32 @@ struct Router {
   }
 };
 
+// Agent::UpdatePath (AC:261-454) for one agent, the rule of path_core.h: on success the new path replaces path_curr_, on failure
+// the agent keeps its path; the status stays in ag.path_rc (hdsm_swarm_path_errors)
+int replan_agent(const hdsm_sw::Cfg& cc, AgentS& ag) {
+  V3 out[hdsm_sw::PATH_PTS];
+  int n = 0;
+  const int st = hdsm_path::plan_serial(hdsm_path::agent_problem(cc, ag, ag.goal), out, &n);
+  ag.path_rc = st;
+  if (st == hdsm_path::PATH_OK) {
+    ag.n_path = n;
+    for (int i = 0; i < n; ++i) ag.path[i] = out[i];
+  }
+  return st;
+}
+
+// the path step at the start of a round, before the corridor (the device loop's k_path does the same in the same rounds)
+void path_round(Swarm& sw) {
+  const bool all = sw.path_period > 0 && sw.path_round % sw.path_period == 0;
+  const hdsm_sw::Cfg cc = sw.core_cfg();
+  for (int k = 0; k < sw.n_local; ++k)
+    if (all || sw.path_due[k]) {
+      replan_agent(cc, sw.agents[k]);
+      sw.path_due[k] = 0;
+    }
+  ++sw.path_round;
+}
+
 }  // namespace
 
 extern "C" {
@@ -386,6 +418,7 @@ int hdsm_swarm_create(const hdsm_params* prm, const hdsm_swarm_config* cfg, int3
   sw->prm = *prm, sw->cfg = *cfg, sw->n_rob = n_rob, sw->first_id = first_id, sw->n_local = n_local;
   sw->agents.assign(n_local, AgentS{});
   sw->extra.assign(n_local, AgentX{});
+  sw->path_due.assign(n_local, 0);
   for (int k = 0; k < n_local; ++k) {
     AgentS& a = sw->agents[k];
     a.id = first_id + k;
@@ -410,6 +443,7 @@ int hdsm_swarm_prepare(void* swarm, const double* plans_all, const uint8_t* has_
   const int N = sw->prm.n_hor, P = sw->prm.poly_hor, RS = sw->prm.max_rows_static;
   sw->t_round = std::chrono::steady_clock::now();
   sw->solve_ms = 0;
+  if (!sw->corridor_done) path_round(*sw);  // (UpdatePath's thread, AC:261-454, once per round before the corridor)
   const hdsm_sw::Cfg cc = sw->core_cfg();
   for (int k = 0; k < sw->n_local; ++k) {
     AgentS& ag = sw->agents[k];
@@ -618,6 +652,48 @@ int hdsm_swarm_route(void* swarm, int32_t* n_failed) {
   return HDSM_OK;
 }
 
+int hdsm_swarm_set_goals(void* swarm, const double* goals) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || (!goals && sw->n_local)) return HDSM_ERR_BAD_ARG;
+  for (int k = 0; k < sw->n_local; ++k) {
+    AgentS& ag = sw->agents[k];
+    const double* g = goals + 3 * (size_t)k;
+    if (g[0] == ag.goal[0] && g[1] == ag.goal[1] && g[2] == ag.goal[2]) continue;
+    ag.goal = V3{{g[0], g[1], g[2]}};
+    sw->path_due[k] = 1;
+  }
+  return HDSM_OK;
+}
+
+int hdsm_swarm_set_path_period(void* swarm, int32_t period) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || period < 0) return HDSM_ERR_BAD_ARG;
+  sw->path_period = period;
+  sw->path_round = 0;  // (the next round is due)
+  return HDSM_OK;
+}
+
+int hdsm_swarm_replan_paths(void* swarm, int32_t* n_failed) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  const hdsm_sw::Cfg cc = sw->core_cfg();
+  int failed = 0;
+  for (int k = 0; k < sw->n_local; ++k) failed += replan_agent(cc, sw->agents[k]) != hdsm_path::PATH_OK;
+  if (n_failed) *n_failed = failed;
+  return HDSM_OK;
+}
+
+int hdsm_swarm_path_errors(void* swarm, int32_t* codes) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  int n = 0;
+  for (int k = 0; k < sw->n_local; ++k) {
+    if (codes) codes[k] = sw->agents[k].path_rc;
+    n += sw->agents[k].path_rc != 0;
+  }
+  return n;
+}
+
 int hdsm_swarm_corridor_errors(void* swarm, int32_t* codes) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw) return HDSM_ERR_BAD_ARG;
@@ -655,12 +731,37 @@ int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local)
   return HDSM_OK;
 }
 
+// the path step's round phase and pending agents (and the goals of a device loop set between its rounds), in and out of the
+// device-resident loop: the mirror and the device count rounds the same way. due / goals: [n_local] / [n_local][3], may be NULL.
+int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  if (period) *period = sw->path_period;
+  if (round) *round = sw->path_round;
+  if (due)
+    for (int k = 0; k < sw->n_local; ++k) due[k] = sw->path_due[k];
+  return HDSM_OK;
+}
+
+int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || period < 0) return HDSM_ERR_BAD_ARG;
+  sw->path_period = period, sw->path_round = round;
+  for (int k = 0; k < sw->n_local; ++k) {
+    if (due) sw->path_due[k] = due[k];
+    if (goals)
+      for (int c = 0; c < 3; ++c) sw->agents[k].goal[c] = goals[3 * (size_t)k + c];
+  }
+  return HDSM_OK;
+}
+
 // GenerateSafeCorridor alone (AC:165), for callers that generate the reference elsewhere (row f1 on the device) and want the
 // reference's own order: corridor from the PREVIOUS reference, then the new reference. The following hdsm_swarm_prepare of the
 // same round does not repeat it.
 int hdsm_swarm_prepare_corridor(void* swarm) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw) return HDSM_ERR_BAD_ARG;
+  path_round(*sw);
   const hdsm_sw::Cfg cc = sw->core_cfg();
   for (int k = 0; k < sw->n_local; ++k) {
     const clock_t t0 = clock();

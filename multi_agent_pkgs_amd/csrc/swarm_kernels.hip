@@ -12,6 +12,7 @@
 // tests/test_gpu_configs.py. AC = multi_agent_planner/src/agent_class.cpp of the reference.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <cstdlib>
 #include <new>
@@ -21,6 +22,7 @@
 
 #include "../../include/hdsm.h"
 #include "../../include/hdsm_swarm.h"
+#include "path_core.h"
 #include "swarm_core.h"
 
 // (csrc/hdsm_api.hip, internal: see hdsm_dswarm_round)
@@ -44,6 +46,8 @@ extern "C" int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n
                                        hdsm_params* prm, hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3],
                                        double worigin[3]);
 extern "C" int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local);
+extern "C" int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
+extern "C" int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
 
 namespace {
 
@@ -516,6 +520,30 @@ __global__ __launch_bounds__(64) void k_commit(Cfg c, int n, int per, AgentS* ag
   if (has_direct != nullptr && lane == 0) has_direct[k] = have_s ? 1 : 0;
 }
 
+// Agent::UpdatePath (AC:261-454) by the rule of path_core.h, ONE WORKGROUP PER DUE AGENT (idx: the due agents, NULL = all n):
+// the BFS as bit planes in LDS (hdsm_path::plan_block), the same points as the host mirror's hdsm_path::plan_serial. goals[k]
+// (hdsm_dswarm_set_goals) becomes the agent's goal first. cnt[0] agents planned, cnt[1] failed.
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_path(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
+                                                              unsigned long long* cnt) {
+  __shared__ hdsm_path::PathLds lds;
+  const int tid = (int)threadIdx.x;
+  const int k = idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x;
+  AgentS& ag = agents[k];
+  const V3 goal = {{goals[3 * (size_t)k], goals[3 * (size_t)k + 1], goals[3 * (size_t)k + 2]}};
+  const hdsm_path::PathIn in = hdsm_path::agent_problem(c, ag, goal);
+  const int st = hdsm_path::plan_block(in, lds, tid);
+  __syncthreads();  // (every thread has read the agent's state)
+  const int n = lds.n_out;
+  if (tid == 0) {
+    ag.goal = goal, ag.path_rc = st;
+    if (st == hdsm_path::PATH_OK) ag.n_path = n;
+    atomicAdd(&cnt[0], 1ull);
+    if (st != hdsm_path::PATH_OK) atomicAdd(&cnt[1], 1ull);
+  }
+  if (st == hdsm_path::PATH_OK)
+    for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.out[t / 3][t % 3];
+}
+
 __global__ __launch_bounds__(256) void k_flags(int rec, int n, const double* plans, uint8_t* has) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (k >= n) return;
@@ -542,6 +570,18 @@ struct DSwarm {
   // packet in front of the next kernel, so a timed round is a few us longer than a plain one — ms_per_round is never taken from it)
   bool phase_timing = false, phase_valid = false;
   hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // the path step (k_path): period and round phase of the host mirror, the agents due at the next round (hdsm_dswarm_set_goals) and
+  // their list on the device, every agent's goal (host copy + device), counters [planned, failed], launches, the timed interval
+  int path_period = 0;
+  long long path_round = 0, path_launches = 0;
+  std::vector<uint8_t> due;
+  std::vector<double> goals;
+  int n_due = 0;
+  int32_t* d_due = nullptr;
+  double* d_goals = nullptr;
+  unsigned long long* d_path_cnt = nullptr;
+  bool path_valid = false;
+  hipEvent_t path_ev[2] = {nullptr, nullptr};
 };
 
 template <class T>
@@ -554,10 +594,12 @@ hipError_t dalloc(T** p, size_t count) {
 void free_all(DSwarm* d) {
   void* ptrs[] = {d->d_cap, d->d_agents, d->d_cache, d->d_world, d->d_path, d->d_ref_full, d->d_ref, d->d_pv, d->d_state, d->d_A, d->d_b, d->d_traj,
                   d->d_ctrl, d->d_obj, d->d_local, d->d_plans, d->d_npath, d->d_id, d->d_npoly, d->d_nrows, d->d_status, d->d_fails,
-                  d->d_used, d->d_has};
+                  d->d_used, d->d_has, d->d_due, d->d_goals, d->d_path_cnt};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t e : d->ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : d->path_ev)
     if (e) (void)hipEventDestroy(e);
 }
 
@@ -575,10 +617,13 @@ int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   HIP_TRY(hipSetDevice(d->device));
-  if (on)
+  if (on) {
     for (hipEvent_t& e : d->ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
-  d->phase_timing = on != 0, d->phase_valid = false;
+    for (hipEvent_t& e : d->path_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+  }
+  d->phase_timing = on != 0, d->phase_valid = false, d->path_valid = false;
   return HDSM_OK;
 }
 
@@ -608,6 +653,57 @@ int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]) {
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipEventSynchronize(d->ev[7]));
   for (int k = 0; k < 7; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]));
+  return HDSM_OK;
+}
+
+// The path step of the last timed round that launched k_path, in milliseconds (0 if it planned no agent): kept out of
+// hdsm_dswarm_last_phase_ms, whose [0] k_corridor starts after it.
+int hdsm_dswarm_last_path_ms(void* dswarm, float* ms) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->phase_valid) return fail(HDSM_ERR_BAD_ARG, "no round has run with hdsm_dswarm_set_phase_timing on");
+  *ms = 0.0f;
+  if (!d->path_valid) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipEventSynchronize(d->path_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, d->path_ev[0], d->path_ev[1]));
+  return HDSM_OK;
+}
+
+// GoalCallback (AC:2380-2388) for the shard: goals [n_local][3]; the agents whose goal changed plan a new path at the start of
+// the next round (k_path). Synchronises the device.
+int hdsm_dswarm_set_goals(void* dswarm, const double* goals) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (!goals && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  for (int k = 0; k < d->n_local; ++k) {
+    double* g = &d->goals[3 * (size_t)k];
+    const double* ng = goals + 3 * (size_t)k;
+    if (g[0] == ng[0] && g[1] == ng[1] && g[2] == ng[2]) continue;
+    g[0] = ng[0], g[1] = ng[1], g[2] = ng[2];
+    d->due[k] = 1;
+  }
+  std::vector<int32_t> idx;
+  for (int k = 0; k < d->n_local; ++k)
+    if (d->due[k]) idx.push_back(k);
+  d->n_due = (int)idx.size();
+  HIP_TRY(hipMemcpy(d->d_goals, d->goals.data(), d->goals.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (d->n_due) HIP_TRY(hipMemcpy(d->d_due, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return HDSM_OK;
+}
+
+// out[0] agents planned by k_path since hdsm_dswarm_create, out[1] of them without a new path, out[2] launches of k_path.
+// Synchronises the device.
+int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long cnt[2] = {0, 0};
+  HIP_TRY(hipMemcpy(cnt, d->d_path_cnt, sizeof cnt, hipMemcpyDeviceToHost));
+  out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path_launches;
   return HDSM_OK;
 }
 
@@ -674,12 +770,22 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
   ok(dalloc(&d->d_A, n * P * RS * 3)), ok(dalloc(&d->d_b, n * P * RS)), ok(dalloc(&d->d_traj, L * REC)), ok(dalloc(&d->d_ctrl, L * N * 3));
   ok(dalloc(&d->d_obj, L)), ok(dalloc(&d->d_used, L * P)), ok(dalloc(&d->d_status, L)), ok(dalloc(&d->d_local, L * REC));
   ok(dalloc(&d->d_plans, G * REC)), ok(dalloc(&d->d_has, G)), ok(dalloc(&d->d_fails, 1));
+  ok(dalloc(&d->d_due, n)), ok(dalloc(&d->d_goals, n * 3)), ok(dalloc(&d->d_path_cnt, 2));
+  d->due.assign(n, 0), d->goals.assign(n * 3, 0.0);
+  if (rc == HDSM_OK) {
+    int32_t period = 0;
+    int64_t round = 0;
+    rc = hdsm_swarm_export_path_state(swarm, &period, &round, d->due.data());
+    d->path_period = period, d->path_round = round;
+  }
   if (e == hipSuccess && n) {
     AgentS* tmp = static_cast<AgentS*>(std::malloc(n * sizeof(AgentS)));
     if (!tmp) e = hipErrorOutOfMemory;
     else {
       rc = hdsm_swarm_export_state(swarm, tmp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
       if (rc == HDSM_OK) e = hipMemcpy(d->d_agents, tmp, n * sizeof(AgentS), hipMemcpyHostToDevice);
+      for (size_t k = 0; k < n; ++k)
+        for (int q = 0; q < 3; ++q) d->goals[3 * k + q] = tmp[k].goal[q];
       std::free(tmp);
     }
   }
@@ -687,6 +793,14 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
     std::string ids(n * 4, '\0');
     for (size_t k = 0; k < n; ++k) reinterpret_cast<int32_t*>(&ids[0])[k] = d->first + (int)k;
     e = hipMemcpy(d->d_id, ids.data(), n * 4, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess && n) e = hipMemcpy(d->d_goals, d->goals.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && n) {  // agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
+    std::vector<int32_t> idx;
+    for (size_t k = 0; k < n; ++k)
+      if (d->due[k]) idx.push_back((int32_t)k);
+    d->n_due = (int)idx.size();
+    if (d->n_due) e = hipMemcpy(d->d_due, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   }
   if (e == hipSuccess && hworld) e = hipMemcpy(d->d_world, hworld, (size_t)wdim[0] * wdim[1] * wdim[2], hipMemcpyHostToDevice);
   c.world = d->d_world;
@@ -739,6 +853,27 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
   do {                \
     if (timing) HIP_TRY(hipEventRecord(d->ev[k], st)); \
   } while (0)
+  // the path step (UpdatePath, AC:261-454) at the start of the round, before the corridor: every agent in rounds of the period,
+  // else the agents whose goal changed; no launch when nobody is due
+  {
+    const bool all = d->path_period > 0 && d->path_round % d->path_period == 0;
+    const int n_plan = all ? n : d->n_due;
+    d->path_valid = false;
+    if (n_plan > 0) {
+      if (timing) HIP_TRY(hipEventRecord(d->path_ev[0], st));
+      hipLaunchKernelGGL(k_path, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
+                         d->d_path_cnt);
+      HIP_TRY(hipGetLastError());
+      if (timing) {
+        HIP_TRY(hipEventRecord(d->path_ev[1], st));
+        d->path_valid = true;
+      }
+      ++d->path_launches;
+    }
+    d->n_due = 0;
+    std::fill(d->due.begin(), d->due.end(), (uint8_t)0);
+    ++d->path_round;
+  }
   PHASE_MARK(0);
   if (n > 0) {
     hipLaunchKernelGGL(k_corridor, dim3((unsigned)n), dim3(64), d->c.has_world ? hdsm_cd::wave_lds_bytes(hdsm_cd::wave_map_radius(d->c.n_it_decomp)) : 0, st, d->c, n, d->d_agents, d->d_path, d->d_npath, d->d_id, d->d_state,
@@ -806,8 +941,9 @@ int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* 
     AgentS* tmp = static_cast<AgentS*>(std::malloc(n * sizeof(AgentS)));
     if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
     hipError_t e = hipMemcpy(tmp, d->d_agents, n * sizeof(AgentS), hipMemcpyDeviceToHost);
-    const int rc = e == hipSuccess ? hdsm_swarm_import_state(swarm, tmp, d->n_local) : HDSM_ERR_DEVICE;
+    int rc = e == hipSuccess ? hdsm_swarm_import_state(swarm, tmp, d->n_local) : HDSM_ERR_DEVICE;
     std::free(tmp);
+    if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d->path_period, d->path_round, d->due.data(), d->goals.data());
     if (rc) return fail(rc, "state download failed");
   }
   if (plans_all) {

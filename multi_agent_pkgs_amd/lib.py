@@ -27,6 +27,8 @@ EXPORTS = ("hdsm_version", "hdsm_last_error", "hdsm_default_params", "hdsm_creat
            "hdsm_swarm_reference_inputs_n", "hdsm_swarm_corridor_errors", "hdsm_swarm_yaw", "hdsm_swarm_view", "hdsm_swarm_record_solve_ms", "hdsm_swarm_shutdown", "hdsm_swarm_prepare_corridor", "hdsm_swarm_vel_cap",
            "hdsm_dswarm_create", "hdsm_dswarm_upload_plans", "hdsm_dswarm_round", "hdsm_dswarm_download", "hdsm_dswarm_destroy", "hdsm_dswarm_last_error",
            "hdsm_dswarm_set_phase_timing", "hdsm_dswarm_last_phase_ms", "hdsm_dswarm_cache_stats",
+           "hdsm_swarm_set_goals", "hdsm_swarm_set_path_period", "hdsm_swarm_replan_paths", "hdsm_swarm_path_errors", "hdsm_local_path_batch",
+           "hdsm_local_path_host", "hdsm_dswarm_set_goals", "hdsm_dswarm_path_stats", "hdsm_dswarm_last_path_ms",
            "hdsm_stats_create", "hdsm_stats_destroy", "hdsm_stats_add", "hdsm_stats_add_state", "hdsm_stats_add_latency",
            "hdsm_stats_shutdown", "hdsm_map_preprocess", "hdsm_map_preprocess_device", "hdsm_map_last_error")
 
@@ -324,3 +326,40 @@ def poly_octa3d_batch(world, ldim, off, ground_k, seed, variant, origin, n_it=42
         L.hdsm_corridor_last_error.restype = C.c_char_p
         raise HdsmError(r, L.hdsm_corridor_last_error().decode())
     return rows, n_rows, rc, cells
+
+
+PATH_PTS = 48  # points of a global path (csrc/swarm_core.h)
+
+
+def _local_path(fn, lead, world, ldim, off, ground_k, origin, start, goal, res, pmax):
+    L = load()
+    i32, d = C.c_int32, C.c_double
+    off, ground_k = _i32(off), _i32(ground_k)
+    origin, start, goal = _f64(origin), _f64(start), _f64(goal)
+    n = off.shape[0]
+    ldim = np.asarray(ldim, dtype=np.int32)
+    if world is None:
+        wp, wdim = None, None
+    else:
+        world = np.ascontiguousarray(world, dtype=np.int8)
+        wdim = np.asarray(world.shape[::-1], dtype=np.int32)
+        wp = world.ctypes.data_as(C.POINTER(C.c_int8))
+    paths = np.zeros((n, pmax, 3))
+    n_path, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rc = getattr(L, fn)(*lead, C.c_int32(n), wp, _p(wdim, i32) if wdim is not None else None, _p(ldim, i32), _p(off, i32), _p(ground_k, i32),
+                        _p(origin, d), _p(start, d), _p(goal, d), C.c_double(res), C.c_int32(pmax), _p(paths, d), _p(n_path, i32), _p(status, i32))
+    if rc:
+        raise HdsmError(rc, fn)
+    return paths, n_path, status
+
+
+def local_path_batch(world, ldim, off, ground_k, origin, start, goal, res=0.3, pmax=PATH_PTS, device=0):
+    """hdsm_local_path_batch: the path step (csrc/path_core.h) for n cases on the device. world int8 [wz][wy][wx] or None (free
+    space); off [n][3] local voxel 0 in world voxels, ground_k [n], origin/start/goal [n][3]. Returns paths [n][pmax][3],
+    n_path [n], status [n] (0 ok, 1 no free voxel, 2 unreachable, 3 too many points, 4 workspace)."""
+    return _local_path("hdsm_local_path_batch", (C.c_int32(device),), world, ldim, off, ground_k, origin, start, goal, res, pmax)
+
+
+def local_path_host(world, ldim, off, ground_k, origin, start, goal, res=0.3, pmax=PATH_PTS):
+    """hdsm_local_path_host: the same batch on the CPU (bit for bit what local_path_batch returns)."""
+    return _local_path("hdsm_local_path_host", (), world, ldim, off, ground_k, origin, start, goal, res, pmax)

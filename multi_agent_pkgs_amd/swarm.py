@@ -180,6 +180,34 @@ class SwarmShard:
             raise _lib.HdsmError(rc, "hdsm_swarm_get_paths")
         return paths, n_path
 
+    def set_goals(self, goals):
+        """GoalCallback (hdsm_swarm_set_goals): goals [n_local][3]; the agents whose goal changed plan a new path (csrc/path_core.h)
+        at the start of the next round."""
+        goals = np.ascontiguousarray(goals, dtype=np.float64).reshape(self.n_local, 3)
+        rc = self.lib.hdsm_swarm_set_goals(self.h, _p(goals, C.c_double))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_set_goals")
+
+    def set_path_period(self, period):
+        """hdsm_swarm_set_path_period: every agent plans a new path every `period`-th round (0: never, the default)."""
+        rc = self.lib.hdsm_swarm_set_path_period(self.h, C.c_int32(int(period)))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_set_path_period")
+
+    def replan_paths(self):
+        """hdsm_swarm_replan_paths: every local agent plans a new path now; returns the number that failed (kept their path)."""
+        nf = C.c_int32(0)
+        rc = self.lib.hdsm_swarm_replan_paths(self.h, C.byref(nf))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_replan_paths")
+        return nf.value
+
+    def path_errors(self):
+        """(agents whose last path step failed, status per agent)."""
+        codes = np.zeros(self.n_local, np.int32)
+        n = self.lib.hdsm_swarm_path_errors(self.h, _p(codes, C.c_int32))
+        return n, codes
+
     def corridor_errors(self):
         codes = np.zeros(self.n_local, np.int32)
         n = self.lib.hdsm_swarm_corridor_errors(self.h, _p(codes, C.c_int32))
@@ -389,6 +417,29 @@ class DeviceSwarm:
         if rc:
             raise self._err(rc)
         return {"asked": int(out[0]), "hits_same_grid": int(out[1]), "hits_interior": int(out[2]), "cache_on": bool(out[3])}
+
+    def set_goals(self, goals):
+        """hdsm_dswarm_set_goals: goals [n_local][3]; the changed agents plan a new path at the next round (on the device)."""
+        goals = np.ascontiguousarray(goals, dtype=np.float64).reshape(self.shard.n_local, 3)
+        rc = self.lib.hdsm_dswarm_set_goals(self.h, _p(goals, C.c_double))
+        if rc:
+            raise self._err(rc)
+
+    def path_stats(self):
+        """hdsm_dswarm_path_stats: agents planned by k_path, of them failed, and launches since the dswarm was created."""
+        out = (C.c_int64 * 3)()
+        rc = self.lib.hdsm_dswarm_path_stats(self.h, out)
+        if rc:
+            raise self._err(rc)
+        return {"planned": int(out[0]), "failed": int(out[1]), "launches": int(out[2])}
+
+    def last_path_ms(self):
+        """hdsm_dswarm_last_path_ms: milliseconds of k_path in the last timed round (0.0 if it planned nothing)."""
+        ms = C.c_float(0.0)
+        rc = self.lib.hdsm_dswarm_last_path_ms(self.h, C.byref(ms))
+        if rc:
+            raise self._err(rc)
+        return float(ms.value)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

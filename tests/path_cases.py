@@ -1,0 +1,235 @@
+"""Cases and an independent numpy restatement of the path step (csrc/path_core.h, steps 1-7) for the path-replanning tests.
+
+The restatement shares no code with the library: the local grid is cut out of the world with numpy, the BFS is an array
+dilation, the descent and the shortening are plain Python loops, the line-of-sight test is the Python Raycast of test_host.py,
+GetIntermediateGoal (agent_class.cpp:1891-1941) is restated from the reference text."""
+import math
+
+import numpy as np
+
+from multi_agent_pkgs_amd import scenarios as sc
+
+VS = 0.3
+LDIM = (66, 66, 20)  # floor(20 / 0.3), floor(20 / 0.3), floor(6 / 0.3): the shipped local grid
+RANGE = np.array([20.0, 20.0, 6.0])
+PATH_PTS = 48
+PLANE_BITS = 32 * 6144
+
+
+def local_grid(world, worigin, state, vs=VS, z_min=0.0):
+    """origin, off, ground_k of the local grid around `state` (environment_builder.cpp:58-67, the corridor's window)."""
+    origin = np.floor((np.asarray(state) - RANGE / 2) / vs) * vs
+    off = np.round((origin - np.asarray(worigin)) / vs).astype(np.int32)
+    gk = int(math.ceil((z_min - origin[2]) / vs - 1e-9))
+    return origin, off, gk
+
+
+def occupancy(world, off, gk, ldim=LDIM):
+    """Step 1 as a boolean [k][j][i] array: unknown and below-ground voxels occupied, outside the world free, >= 100 occupied,
+    then ClearBoundary (x and y side faces free)."""
+    dx, dy, dz = ldim
+    wz, wy, wx = world.shape
+    I, J, K = np.arange(dx) + off[0], np.arange(dy) + off[1], np.arange(dz) + off[2]
+    occ = np.zeros((dz, dy, dx), bool)
+    ki, ji, ii = (np.nonzero((K >= 0) & (K < wz))[0], np.nonzero((J >= 0) & (J < wy))[0], np.nonzero((I >= 0) & (I < wx))[0])
+    sub = world[np.ix_(K[ki], J[ji], I[ii])].astype(int)
+    occ[np.ix_(ki, ji, ii)] = (sub < 0) | (sub >= 100)
+    occ[: max(0, min(gk, dz))] = True
+    occ[:, :, 0] = occ[:, :, dx - 1] = False
+    occ[:, 0, :] = occ[:, dy - 1, :] = False
+    return occ
+
+
+def intermediate_goal(goal, origin, ldim, vs):
+    """Agent::GetIntermediateGoal (agent_class.cpp:1891-1941), the march stopped after 100 half-voxel steps."""
+    g = [goal[k] - origin[k] for k in range(3)]
+    dr = [ldim[k] * vs for k in range(3)]
+    if all(0 < g[k] < dr[k] for k in range(3)):
+        return [float(x) for x in goal]
+    c = [(ldim[k] // 2 + 0.5) * vs for k in range(3)]
+    d = [g[k] - c[k] for k in range(3)]
+    z = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+    if z > 0:
+        s = math.sqrt(z)
+        d = [x / s for x in d]
+    min_dim = vs * min(ldim)
+    p = [c[k] + (min_dim / 2) * d[k] for k in range(3)]
+    for _ in range(100):
+        if p[0] > dr[0] or p[1] > dr[1] or p[2] > dr[2] or p[0] < 0 or p[1] < 0 or p[2] < 0:
+            p = [p[k] - (0.5 * vs) * d[k] for k in range(3)]
+            break
+        p = [p[k] + (0.5 * vs) * d[k] for k in range(3)]
+    return [p[k] + origin[k] for k in range(3)]
+
+
+def _blocked(occ, v):
+    dz, dy, dx = occ.shape
+    i, j, k = v
+    return not (0 <= i < dx and 0 <= j < dy and 0 <= k < dz) or bool(occ[k, j, i])
+
+
+def _nearest_free(occ, v):
+    if not _blocked(occ, v):
+        return list(v)
+    for r in range(1, 7):
+        best, bv = None, None
+        for dk in range(-r, r + 1):
+            for dj in range(-r, r + 1):
+                for di in range(-r, r + 1):
+                    if max(abs(di), abs(dj), abs(dk)) != r or _blocked(occ, (v[0] + di, v[1] + dj, v[2] + dk)):
+                        continue
+                    d2 = di * di + dj * dj + dk * dk
+                    if best is None or d2 < best:
+                        best, bv = d2, [v[0] + di, v[1] + dj, v[2] + dk]
+        if bv is not None:
+            return bv
+    return None
+
+
+def _dilate6(a):
+    out = np.zeros_like(a)
+    out[:, :, 1:] |= a[:, :, :-1]
+    out[:, :, :-1] |= a[:, :, 1:]
+    out[:, 1:, :] |= a[:, :-1, :]
+    out[:, :-1, :] |= a[:, 1:, :]
+    out[1:] |= a[:-1]
+    out[:-1] |= a[1:]
+    return out
+
+
+def plan(world, off, gk, origin, start, goal, vs=VS, ldim=LDIM):
+    """Steps 1-7 of csrc/path_core.h. Returns (status, [points])."""
+    from test_host import _py_raycast
+    start, goal = [float(x) for x in start], [float(x) for x in goal]
+    if world is None:
+        return 0, [start, goal]
+    if (ldim[0] + 2) * (ldim[1] + 2) * ldim[2] > PLANE_BITS:
+        return 4, []
+    occ = occupancy(world, off, gk, ldim)
+    G = intermediate_goal(goal, origin, ldim, vs)
+    vox = lambda p: [int(math.floor((p[k] - origin[k]) / vs)) for k in range(3)]
+    sv0, gv0 = vox(start), vox(G)
+    sv, gv = _nearest_free(occ, sv0), _nearest_free(occ, gv0)
+    if sv is None or gv is None:
+        return 1, []
+    centre = lambda v: [origin[k] + (v[k] + 0.5) * vs for k in range(3)]
+    gq = G if gv == gv0 else centre(gv)
+    # step 5: BFS by dilation from the goal voxel until the start voxel has a level
+    level = np.full(occ.shape, -1, np.int64)
+    front = np.zeros(occ.shape, bool)
+    front[gv[2], gv[1], gv[0]] = True
+    seen = occ | front
+    level[front] = 0
+    L = 0
+    while level[sv[2], sv[1], sv[0]] < 0:
+        nxt = _dilate6(front) & ~seen
+        if not nxt.any():
+            return 2, []
+        L += 1
+        level[nxt] = L
+        seen |= nxt
+        front = nxt
+    # step 6: descent, first neighbour -x +x -y +y -z +z one level lower
+    q = [start]
+    v = list(sv)
+    dz, dy, dx = occ.shape
+    for lv in range(L, 1, -1):
+        for d in ((-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)):
+            n = [v[0] + d[0], v[1] + d[1], v[2] + d[2]]
+            if 0 <= n[0] < dx and 0 <= n[1] < dy and 0 <= n[2] < dz and level[n[2], n[1], n[0]] == lv - 1:
+                v = n
+                break
+        else:
+            raise AssertionError("descent stuck")
+        q.append(centre(v))
+    q.append(gq)
+    # step 7: greedy shortening with the reference's Raycast (limit = length + 2 voxels)
+    val = lambda i, j, k: 100 if occ[k, j, i] else 0
+    loc = lambda p: [(p[k] - origin[k]) / vs for k in range(3)]
+
+    def clear(a, b):
+        s, t = loc(a), loc(b)
+        d = [s[k] - t[k] for k in range(3)]
+        _, hit = _py_raycast(val, ldim, s, t, math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + 2.0)
+        return hit is None
+
+    m, a, out = len(q) - 1, 0, [q[0]]
+    while a < m:
+        j = a + 1
+        for c in range(m, a + 1, -1):
+            if clear(q[a], q[c]):
+                j = c
+                break
+        if len(out) == PATH_PTS:
+            return 3, []
+        out.append(q[j])
+        a = j
+    return 0, out
+
+
+def halo_world(rng, n_pillars=60, boxes=2, solid=1):
+    """Random pillars (inflated) with a potential-field halo of values 1..99, hollow sealed boxes (unreachable goals inside) and
+    solid blocks (no free voxel within six of their centre). origin (-3, -6, -0.9)."""
+    raw = np.zeros((30, 120, 120), np.int8)
+    for _ in range(n_pillars):
+        i, j = rng.integers(5, 115, 2)
+        raw[:, j, i] = 100
+    occ = sc.inflate(raw)
+    halo = sc.inflate(occ, inflation_dist=0.6)
+    world = np.where(occ >= 100, 100, np.where(halo >= 100, int(rng.integers(20, 90)), 0)).astype(np.int8)
+    sealed = []
+    for _ in range(boxes):
+        i, j = rng.integers(20, 95, 2)
+        world[3:12, j:j + 8, i:i + 8] = 100
+        world[4:11, j + 1:j + 7, i + 1:i + 7] = 0
+        sealed.append(np.array([-3.0, -6.0, -0.9]) + (np.array([i + 4, j + 4, 7]) + 0.5) * VS)
+    blocks = []
+    for _ in range(solid):
+        i, j = rng.integers(20, 90, 2)
+        world[3:28, j:j + 16, i:i + 16] = 100
+        blocks.append(np.array([-3.0, -6.0, -0.9]) + (np.array([i + 8, j + 8, 12]) + 0.5) * VS)
+    return world, np.array([-3.0, -6.0, -0.9]), sealed, blocks
+
+
+def make_cases(world, worigin, n, rng, z_lo=0.6, z_hi=3.5, sealed=(), blocks=()):
+    """n cases in `world`: agent state (the local grid around it), start S near it, goal inside / outside the grid, in the inflation
+    margin, in a sealed box or a solid block. Returns dict of arrays for hdsm_local_path_*."""
+    wz, wy, wx = world.shape
+    lo = np.asarray(worigin) + [2.0, 2.0, 0.0]
+    hi = np.asarray(worigin) + np.array([wx, wy, wz]) * VS - [2.0, 2.0, 0.0]
+    occ_idx = np.argwhere(world >= 100)
+    out = {k: [] for k in ("off", "ground_k", "origin", "start", "goal")}
+    for t in range(n):
+        state = np.array([rng.uniform(lo[0], hi[0]), rng.uniform(lo[1], hi[1]), rng.uniform(z_lo, z_hi)])
+        kind = t % 6
+        origin, off, gk = local_grid(world, worigin, state)
+        S = state + rng.uniform(-0.3, 0.3, 3)
+        if kind == 0:  # goal inside the grid
+            goal = state + rng.uniform(-9, 9, 3) * [1, 1, 0.3]
+        elif kind == 1:  # goal outside the grid
+            goal = state + rng.uniform(-40, 40, 3) * [1, 1, 0.2]
+        elif kind == 2 and len(occ_idx):  # start and goal in (or next to) occupied voxels: the inflation margin
+            near = occ_idx[rng.integers(0, len(occ_idx), 64)]
+            near = near[:, ::-1] * VS + np.asarray(worigin) + VS / 2
+            dist = np.linalg.norm(near[:, :2] - state[:2], axis=1)
+            S = near[np.argmin(dist)] + rng.uniform(-0.1, 0.1, 3)
+            S[2] = np.clip(S[2], z_lo, z_hi)
+            state = S + rng.uniform(-0.2, 0.2, 3)
+            origin, off, gk = local_grid(world, worigin, state)
+            goal = near[np.argsort(dist)[1]] + rng.uniform(-0.1, 0.1, 3)
+        elif kind == 3 and len(sealed):  # unreachable: inside a sealed hollow box
+            b = sealed[t % len(sealed)]
+            state = b + np.array([rng.uniform(-7, 7), rng.uniform(-7, 7), 0.0])
+            origin, off, gk = local_grid(world, worigin, state)
+            S, goal = state + rng.uniform(-0.3, 0.3, 3), b + rng.uniform(-0.2, 0.2, 3)
+        elif kind == 4 and len(blocks):  # goal deep inside a solid block
+            b = blocks[t % len(blocks)]
+            state = b + np.array([rng.uniform(-9, 9), rng.uniform(-9, 9), 0.0])
+            state[2] = 1.5
+            origin, off, gk = local_grid(world, worigin, state)
+            S, goal = state + rng.uniform(-0.3, 0.3, 3), b
+        else:  # far goal in some direction
+            ang = rng.uniform(0, 2 * np.pi)
+            goal = state + [30 * math.cos(ang), 30 * math.sin(ang), rng.uniform(-1, 1)]
+        out["off"].append(off), out["ground_k"].append(gk), out["origin"].append(origin), out["start"].append(S), out["goal"].append(goal)
+    return {k: np.array(v) for k, v in out.items()}
