@@ -4,9 +4,7 @@
 // There is no CPU path in this library: without a HIP device hdsm_create() fails.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <atomic>
-#include <functional>
 #include <mutex>
 
 #include <cfloat>
@@ -43,11 +41,6 @@ int set_err(int code, const std::string& msg) {
       return set_err(HDSM_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));               \
     }                                                                                                   \
   } while (0)
-
-// staged neighbour rows (LDS). One workgroup per CU is resident anyway (the iteration wave needs > 256 registers,
-// a 256-register budget spills 644 B/lane), so LDS capacity is spent on fewer staging-radius retries.
-using hdsm::CMAX30;  // 1536 rows, n <= 30 (hdsm_shapes.h: the one list of launch shapes, shared with the CPU execution)
-using hdsm::CMAX48;  // 1024 rows, n <= 48
 
 // What a workgroup works on. Ordinary launch: block b -> instance order[b] (or b). Pass 2 of a split launch (a.item_mode): the
 // workgroups are PERSISTENT — each draws items from the queue pass 1 filled (Args::items: one open child of an open level of a
@@ -137,6 +130,9 @@ __device__ __forceinline__ void run_block(typename Sol::S* sp, const hdsm::Const
   }
 }
 
+// The launch shapes of these kernels: hdsm_shapes.h (HDSM_SOLVER_SHAPES). k_replan runs ONE workgroup per CU: the iteration wave
+// needs > 256 registers (a 256-register budget spills 644 B/lane), so the LDS is spent on the largest staging area (staged
+// neighbour rows), i.e. on fewer staging-radius retries.
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT) void k_replan(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -148,7 +144,6 @@ __global__ __launch_bounds__(NT) void k_replan(const hdsm::Consts* __restrict__ 
 // rows makes the instance state fit twice into 160 KB). A single instance is bound by the latency of its one iterating
 // wave, so when there are more instances than CUs a second resident workgroup nearly doubles the throughput. Used for
 // n <= 30 only (the NV = 48 factor does not fit the halved register file).
-using hdsm::CMAX_DUO;  // 768 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_duo(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -804,48 +799,12 @@ struct Handle {
   bool defer_done = false;  // the device-resident loop records ev_done once per round (hdsm_internal_record_done), not once per call
 };
 
-template <int NV, int NT>
-int launch_nv(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
-  constexpr int CM = (NV <= 32) ? CMAX30 : CMAX48;
-  using Sol = hdsm::Solver<NV, CM>;
-  const size_t shm = sizeof(typename Sol::S);
-  auto kern = k_replan<NV, CM, NT>;
-  static thread_local int attr_dev[2] = {-1, -1};
-  if (attr_dev[a.item_mode ? 1 : 0] != h->device) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shm));
-    attr_dev[a.item_mode ? 1 : 0] = h->device;
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(NT), shm, st, h->d_consts, a);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
-
-int launch_duo(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
-  using Sol = hdsm::Solver<32, CMAX_DUO>;
-#ifndef HDSM_PROFILE  // (the counters of the profile build live in LDS: that build runs at a lower occupancy)
-  static_assert(sizeof(typename Sol::S) * 2 <= 160 * 1024, "two instances must fit the LDS of one CU");
-#endif
-  const size_t shm = sizeof(typename Sol::S);
-  auto kern = k_replan_duo<32, CMAX_DUO, 256>;
-  static thread_local int attr_dev[2] = {-1, -1};
-  if (attr_dev[a.item_mode ? 1 : 0] != h->device) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)shm));
-    attr_dev[a.item_mode ? 1 : 0] = h->device;
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), shm, st, h->d_consts, a);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
-
 // THREE workgroups of 128 threads (two wavefronts: the iterating one and one helper) per CU, for batches that outnumber the
 // resident slots of the two-per-CU kernel. A launch lasts as long as its slowest workgroup CHAIN: with 1024 instances on 512
 // slots an instance that was predicted cheap and turns out long starts late and sets the kernel time (measured: mean span
 // 119 us against 107 us for the slowest instance, profiles/r03_launch_timeline.json); with 768 slots the late starters begin
 // when the first instances without iterations leave (~18 us) and finish inside the slowest instance. The sweeps and the set-up
 // run on half the threads (+2..3 us per instance), the staging area shrinks to 384 rows (three states in 160 KB).
-using hdsm::CMAX_TRI;  // 384 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_tri(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -858,28 +817,11 @@ __global__ __launch_bounds__(NT, 2) void k_replan_tri(const hdsm::Consts* __rest
 // the three-per-CU launch ended 15-25 us after its slowest instance, set by a late starter. Four instance states fit 160 KB with
 // the small LDS layout (Shm<.., SMALL>: 4 polyhedra of <= 20 rows, 512-neighbour chunks) and a staging area of 256 rows (the
 // bench rounds stage <= 190; an overflow is re-solved by the rescue pass like for the other shared-CU kernels).
-using hdsm::CMAX_QUAD;  // 256 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 2) void k_replan_quad(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Sol = hdsm::Solver<NV, CMAX, true>;
   run_block<Sol>(reinterpret_cast<typename Sol::S*>(smem), cp, a);
-}
-int launch_quad(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
-  using Sol = hdsm::Solver<32, CMAX_QUAD, true>;
-#ifndef HDSM_PROFILE  // (the counters of the profile build live in LDS: that build runs at a lower occupancy)
-  static_assert(sizeof(typename Sol::S) * 4 <= 160 * 1024, "four instances must fit the LDS of one CU");
-#endif
-  const size_t shm = sizeof(typename Sol::S);
-  auto kern = k_replan_quad<32, CMAX_QUAD, 128>;
-  static thread_local int attr_dev = -1;
-  if (attr_dev != h->device) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    attr_dev = h->device;
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(128), shm, st, h->d_consts, a);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
 }
 
 // n > 30 (H up to 16): the factor needs more than 256 registers per lane, so a wavefront must have a SIMD to itself — but a
@@ -895,46 +837,46 @@ int launch_quad(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
 // launch shape, each of which the whole -m gpu suite, the fuzz and the oracle check of the timed rounds run through. The 720 rows
 // of this kernel are filled and overflowed on purpose by test_gpu_abi.py::test_staging_overflow_at_each_shared_cu_capacity_is_rescued
 // and, in the CPU execution of the source together with the 320-row tuple, by tests/test_wave_shapes.py.)
-using hdsm::CMAX_DUO48;  // 720 rows
 template <int NV, int CMAX, int NT>
 __global__ __launch_bounds__(NT, 1) void k_replan_duo48(const hdsm::Consts* __restrict__ cp, hdsm::Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   using Sol = hdsm::Solver<NV, CMAX>;
   run_block<Sol>(reinterpret_cast<typename Sol::S*>(smem), cp, a);
 }
-int launch_duo48(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
-  using Sol = hdsm::Solver<48, CMAX_DUO48>;
-#ifndef HDSM_PROFILE  // (the counters of the profile build live in LDS: that build runs at a lower occupancy)
-  static_assert(sizeof(typename Sol::S) * 2 <= 160 * 1024, "two instances must fit the LDS of one CU");
+
+// Every row of HDSM_SOLVER_SHAPES as it is launched: the kernel, its workgroup size and its dynamic LDS (the whole instance state).
+// hdsm_create raises each kernel's dynamic-LDS limit to its shm once.
+using SolverKernel = void (*)(const hdsm::Consts*, hdsm::Args);
+struct ShapeLaunch {
+  SolverKernel kern;
+  int threads;
+  size_t shm;
+};
+#ifdef HDSM_PROFILE  // (the counters of the profile build live in LDS: that build runs at a lower occupancy)
+constexpr bool LDS_FIT_CHECK = false;
+#else
+constexpr bool LDS_FIT_CHECK = true;
 #endif
-  const size_t shm = sizeof(typename Sol::S);
-  auto kern = k_replan_duo48<48, CMAX_DUO48, 128>;
-  static thread_local int attr_dev[2] = {-1, -1};
-  if (attr_dev[a.item_mode ? 1 : 0] != h->device) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    attr_dev[a.item_mode ? 1 : 0] = h->device;
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(128), shm, st, h->d_consts, a);
+// (per_cu is what ensure_sub counts as resident pass-2 workgroups per CU: the state of a one-per-CU kernel, with 64 threads too, is
+// held to ONE by being more than half of a CU's 160 KB)
+#define HDSM_SHAPE_LAUNCH(name, kernel, nv, cmax, small, threads, per_cu)                                                               \
+  static_assert(!LDS_FIT_CHECK || per_cu * sizeof(hdsm::Solver<nv, cmax, small>::S) <= 160 * 1024, #name ": per_cu instances must fit the LDS of one CU"); \
+  static_assert(per_cu > 1 || sizeof(hdsm::Solver<nv, cmax, small>::S) > 80 * 1024, #name ": a one-per-CU shape must not fit a CU twice");
+HDSM_SOLVER_SHAPES(HDSM_SHAPE_LAUNCH)
+#undef HDSM_SHAPE_LAUNCH
+#define HDSM_SHAPE_LAUNCH(name, kernel, nv, cmax, small, threads, per_cu) {kernel<nv, cmax, threads>, threads, sizeof(hdsm::Solver<nv, cmax, small>::S)},
+const ShapeLaunch SHAPE_LAUNCH[hdsm::NUM_SHAPES] = {HDSM_SOLVER_SHAPES(HDSM_SHAPE_LAUNCH)};
+#undef HDSM_SHAPE_LAUNCH
+
+int launch_shape(Handle* h, hdsm::Shape s, const hdsm::Args& a, hipStream_t st, int blocks) {
+  const ShapeLaunch& l = SHAPE_LAUNCH[s];
+  hipLaunchKernelGGL(l.kern, dim3(blocks), dim3(l.threads), l.shm, st, h->d_consts, a);
   HIP_TRY(hipGetLastError());
   return HDSM_OK;
 }
 
-int launch_tri(Handle* h, const hdsm::Args& a, hipStream_t st, int blocks) {
-  using Sol = hdsm::Solver<32, CMAX_TRI>;
-#ifndef HDSM_PROFILE  // (the counters of the profile build live in LDS: that build runs at a lower occupancy)
-  static_assert(sizeof(typename Sol::S) * 3 <= 160 * 1024, "three instances must fit the LDS of one CU");
-#endif
-  const size_t shm = sizeof(typename Sol::S);
-  auto kern = k_replan_tri<32, CMAX_TRI, 128>;
-  static thread_local int attr_dev = -1;
-  if (attr_dev != h->device) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    attr_dev = h->device;
-  }
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(128), shm, st, h->d_consts, a);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
+// the execution knobs the choice of shape depends on (hdsm_create settles them)
+hdsm::ShapeKnobs shape_knobs(const Handle* h) { return {h->n, h->threads, h->P, h->RS, h->duo_min, h->tri_min, h->quad_min}; }
 
 // ---- subtree splitting: set-up of pass 2, merge, lazily allocated state -------------------------------------------------
 // hdsm_replan with page-locked input arrays: ONE kernel reads them from mapped host memory (coalesced reads over PCIe) into the
@@ -1003,15 +945,14 @@ __global__ __launch_bounds__(64) void k_split_merge(int N, int P, hdsm::Args a, 
   hdsm::split_merge(N, P, a, b, (int)blockIdx.x, (int)threadIdx.x, 64);
 }
 
-hipError_t ensure_sub(Handle* h);
+hipError_t ensure_sub(Handle* h, hdsm::Shape items);
 
 // the one-per-CU kernel (largest staging area) over the batch of `a`; only instances flagged HDSM_FLAG_STAGING_OVERFLOW work
 int launch_rescue(Handle* h, const hdsm::Args& a, hipStream_t st) {
   hdsm::Args r = a;
   r.rescue = 1, r.order = nullptr, r.split_budget = 0, r.item_mode = 0, r.split_info = nullptr, r.inc_bits = nullptr, r.node_pool = nullptr;
   r.tree_flag = nullptr, r.tree_mark = 0, r.warm_out = r.warm, r.ovf_flag = nullptr;
-  if (h->n <= hdsm::SPLIT_N_MAX) return h->threads == 64 ? launch_nv<32, 64>(h, r, st, r.n_inst) : launch_nv<32, 256>(h, r, st, r.n_inst);
-  return h->threads == 64 ? launch_nv<48, 64>(h, r, st, r.n_inst) : launch_nv<48, 256>(h, r, st, r.n_inst);
+  return launch_shape(h, hdsm::pick_shape(shape_knobs(h), r.n_inst, hdsm::PASS_RESCUE), r, st, r.n_inst);
 }
 
 int launch(Handle* h, hdsm::Args a, hipStream_t st) {
@@ -1070,30 +1011,14 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   // with 256 threads the other three waves of the CU share the sweeps, the set-up and the leaf test.
   int rc;
   if (h->time_kernel) HIP_TRY(hipEventRecord(h->ev_k0, st));
-  bool small = false;  // a kernel shape with a reduced staging area was used (two or three workgroups per CU)
+  // `small`: a shape of this launch shares a CU (per_cu > 1), i.e. has a reduced staging area. It follows the shapes actually
+  // launched, not the thresholds: with HDSM_DUO_MIN=0 and HDSM_QUAD_MIN / HDSM_TRI_MIN set by hand the two can disagree.
+  bool small = false;
+  const hdsm::ShapeKnobs knobs = shape_knobs(h);
   auto solve = [&](const hdsm::Args& x, int blocks) -> int {  // the kernel shape that suits `blocks` workgroups
-    hdsm::Args y = x;
-    y.n_inst = x.n_inst;
-    // (`small` follows the shape that is actually launched — every shared-CU kernel has a reduced staging area — not the
-    // thresholds: with HDSM_DUO_MIN=0 and HDSM_QUAD_MIN / HDSM_TRI_MIN set by hand the two can disagree)
-    if (h->n <= hdsm::SPLIT_N_MAX && h->threads == 256 && h->quad_min > 0 && blocks >= h->quad_min && h->P <= 4 && h->RS <= 20) {
-      small = true;
-      return launch_quad(h, y, st, blocks);
-    }
-    if (h->n <= hdsm::SPLIT_N_MAX && h->threads == 256 && h->tri_min > 0 && blocks >= h->tri_min) {
-      small = true;
-      return launch_tri(h, y, st, blocks);
-    }
-    if (h->n <= hdsm::SPLIT_N_MAX && h->threads == 256 && h->duo_min > 0 && blocks >= h->duo_min) {
-      small = true;
-      return launch_duo(h, y, st, blocks);
-    }
-    if (h->n <= hdsm::SPLIT_N_MAX) return h->threads == 64 ? launch_nv<32, 64>(h, y, st, blocks) : launch_nv<32, 256>(h, y, st, blocks);
-    if (h->threads == 256 && h->duo_min > 0 && blocks >= h->duo_min) {
-      small = true;
-      return launch_duo48(h, y, st, blocks);
-    }
-    return h->threads == 64 ? launch_nv<48, 64>(h, y, st, blocks) : launch_nv<48, 256>(h, y, st, blocks);
+    const hdsm::Shape s = hdsm::pick_shape(knobs, blocks, hdsm::PASS_ORDINARY);
+    small = small || hdsm::SHAPES[s].per_cu > 1;
+    return launch_shape(h, s, x, st, blocks);
   };
   a.warm_out = a.warm;
   a.tree_flag = h->d_tree_flag;
@@ -1123,7 +1048,9 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
     if (*h->h_tree_flag != 0) *h->h_tree_flag = 0, h->split_ttl = 256;
     if (h->split_ttl > 0) split = true, --h->split_ttl;
   }
-  if (split && !h->sub_ready) split = ensure_sub(h) == hipSuccess;
+  // pass 2 of a split launch: persistent workgroups, as many as fit the GPU at once (per_cu of the shape per CU)
+  const hdsm::Shape items = hdsm::pick_shape(knobs, 0, hdsm::PASS_ITEMS);
+  if (split && !h->sub_ready) split = ensure_sub(h, items) == hipSuccess;
   if (!split) {
     rc = solve(a, a.n_inst);
   } else {
@@ -1155,46 +1082,20 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
     const size_t GI = (size_t)h->items_cap;
     b.st_iters = ss, b.st_nodes = ss + GI, b.st_sweeps = ss + 2 * GI, b.st_cand = ss + 3 * GI, b.st_sph = ss + 4 * GI, b.st_pairs = ss + 5 * GI;
     b.st_flags = reinterpret_cast<uint32_t*>(ss + 6 * GI), b.st_key = ss + 7 * GI;
-    // pass 2: persistent workgroups, as many as fit the GPU at once (two per CU where the shape allows it)
-    const bool two = h->threads == 256 && h->duo_min > 0;
-    small = small || two;
+    small = small || hdsm::SHAPES[items].per_cu > 1;
     // the grid: an upper bound of the items of this launch — four times what the last split launch queued (the merge leaves the
     // count in pinned host memory), at least 4096; a launch that outgrows it leaves items pending and their instances end as LIMIT
     int grid = 4096;
     if (h->h_item_total != nullptr && 4 * *h->h_item_total > grid) grid = 4 * *h->h_item_total;
     if (grid > h->items_cap) grid = h->items_cap;
-    if (h->n <= hdsm::SPLIT_N_MAX) rc = two ? launch_duo(h, b, st, grid) : (h->threads == 64 ? launch_nv<32, 64>(h, b, st, grid) : launch_nv<32, 256>(h, b, st, grid));
-    else if (two) rc = launch_duo48(h, b, st, grid);
-    else rc = h->threads == 64 ? launch_nv<48, 64>(h, b, st, grid) : launch_nv<48, 256>(h, b, st, grid);
+    rc = launch_shape(h, items, b, st, grid);
     if (rc) return rc;
     hipLaunchKernelGGL(k_split_merge, dim3(a.n_inst), dim3(64), 0, st, h->N, h->P, a, b);
     HIP_TRY(hipGetLastError());
-#ifdef HDSM_SPLIT_TRACE  // development aid (scripts/gpu_split_trace.sh): how the nodes of the handed-over instances spread over their items
-    {
-      HIP_TRY(hipStreamSynchronize(st));
-      int32_t cnt[4];
-      HIP_TRY(hipMemcpy(cnt, h->d_rec_count, sizeof cnt, hipMemcpyDeviceToHost));
-      const size_t q = (size_t)(cnt[1] < h->items_cap ? cnt[1] : h->items_cap);
-      std::vector<int32_t> nd(q), it(q);
-      if (q) {
-        HIP_TRY(hipMemcpy(it.data(), ss, q * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(nd.data(), ss + GI, q * 4, hipMemcpyDeviceToHost));
-      }
-      long long nodes_total = 0, iters_total = 0;
-      int working = 0;
-      std::vector<int> tops(nd.begin(), nd.end());
-      for (size_t k = 0; k < q; ++k) working += nd[k] > 0, nodes_total += nd[k], iters_total += it[k];
-      std::sort(tops.begin(), tops.end(), std::greater<int>());
-      std::fprintf(stderr, "HDSM_SPLIT_TRACE handed over %d of %d instances (records cap %d), %d items queued, %d worked, nodes %lld iters %lld; largest items:",
-                   cnt[0], a.n_inst, h->rec_cap, cnt[1], working, nodes_total, iters_total);
-      for (size_t k = 0; k < tops.size() && k < 12; ++k) std::fprintf(stderr, " %d", tops[k]);
-      std::fprintf(stderr, "\n");
-    }
-#endif
   }
   if (rc) return rc;
-  // Staging overflow. The kernels that share a CU have a fraction of the staging rows of the one-per-CU kernel (384 / 768 / 320
-  // against 1536 / 1024); an instance in a very dense neighbourhood can fill them with VIOLATED rows alone and then ends with
+  // Staging overflow. The kernels that share a CU have a fraction of the staging rows of the one-per-CU kernel (the CMAX column of
+  // hdsm_shapes.h); an instance in a very dense neighbourhood can fill them with VIOLATED rows alone and then ends with
   // HDSM_FLAG_STAGING_OVERFLOW. It raises a word in pinned host memory; while the handle has seen that word in the last 256
   // launches, every launch that used such a kernel is followed by a rescue pass — the one-per-CU kernel over the batch, in
   // which only the instances that carry the flag are solved again (the host-buffer entry point adds it at once, see hdsm_replan).
@@ -1234,21 +1135,17 @@ hipError_t ensure(Handle* h, Handle::Buf& b, size_t bytes) {
 }
 
 int64_t scratch_stride_for(int n) {
-  return n <= hdsm::SPLIT_N_MAX ? (int64_t)hdsm::Solver<32, CMAX30>::SNAP_STRIDE * hdsm::MAXH
-                 : (int64_t)hdsm::Solver<48, CMAX48>::SNAP_STRIDE * hdsm::MAXH;
+  return n <= hdsm::SPLIT_N_MAX ? (int64_t)hdsm::Solver<32, hdsm::CMAX30>::SNAP_STRIDE * hdsm::MAXH
+                 : (int64_t)hdsm::Solver<48, hdsm::CMAX48>::SNAP_STRIDE * hdsm::MAXH;
 }
 
 // state of the split launches, allocated on the first one: the hand-over records of pass 1 with their staged rows, the item queue,
 // outputs / statistics / guesses per item, snapshot scratch for the persistent workgroups of pass 2
-hipError_t ensure_sub(Handle* h) {
+hipError_t ensure_sub(Handle* h, hdsm::Shape items) {
   const size_t N = (size_t)h->N;
-  const bool two = h->threads == 256 && h->duo_min > 0;
-  // (resident workgroups of pass 2 per CU: two for the 256-thread shared-CU shapes, ONE for everything else — the one-per-CU kernels,
-  // with 64 threads too, are held to that by LDS: their instance state is more than half of a CU's 160 KB)
-  static_assert(sizeof(hdsm::Solver<32, CMAX30>::S) > 80 * 1024 && sizeof(hdsm::Solver<48, CMAX48>::S) > 80 * 1024,
-                "pool_cap counts ONE resident pass-2 workgroup per CU for the one-per-CU kernels");
-  h->sub_slots_n = (two ? 2 : 1) * h->cus;
-  h->rows_cap = h->n <= hdsm::SPLIT_N_MAX ? (two ? CMAX_DUO : CMAX30) : (two ? CMAX_DUO48 : CMAX48);
+  // (resident workgroups of pass 2 per CU: per_cu of its shape, see the LDS checks at SHAPE_LAUNCH)
+  h->sub_slots_n = hdsm::SHAPES[items].per_cu * h->cus;
+  h->rows_cap = hdsm::SHAPES[items].cmax;
   // (rec_cap — records: one per instance that hands its search over + one per item that hands over again — set by hdsm_create)
   h->items_cap = h->rec_cap * 16 < 4096 ? 4096 : h->rec_cap * 16;
   // snapshot scratch of pass 2: one slot per workgroup that can be resident + one per record (an item that hands over again leaves
@@ -1416,6 +1313,8 @@ int hdsm_create(const hdsm_params* params, int32_t max_instances, int32_t n_rob_
   auto ok = [&](hipError_t r) {
     if (e == hipSuccess) e = r;
   };
+  for (const ShapeLaunch& l : SHAPE_LAUNCH)  // (the instance state of most shapes is more than the default 64 KB of dynamic LDS)
+    ok(hipFuncSetAttribute(reinterpret_cast<const void*>(l.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.shm));
   ok(dmalloc(&h->d_consts, 1));
   ok(dmalloc(&h->d_scratch, I * (size_t)h->scratch_stride));
   ok(dmalloc(&h->d_stats, 8 * I));

@@ -1,7 +1,8 @@
 """Every launch shape of the solver kernel through the CPU execution of its device source (tests/wave_emu), against the oracle.
 
-libhdsm.so instantiates hdsm::Solver<NV, CMAX, SMALL> in eight (kernel, NV, CMAX, threads) shapes, with the staging capacities of
-hdsm_shapes.h; wave_shapes() lists the tuples the emulator runs. The guard below holds the two lists together. The capacity tests
+libhdsm.so instantiates hdsm::Solver<NV, CMAX, SMALL> in the eight (kernel, NV, CMAX, threads) shapes of hdsm_shapes.h;
+wave_shapes() lists the tuples the emulator runs, the same rows first. The guard below holds them against the kernel symbols of the
+built library, and the selection test checks the rule that picks a shape for a launch (hdsm::pick_shape). The capacity tests
 fill the staging area of each kernel that shares a CU up to its last row (the answer must be the oracle's, without the overflow flag)
 and beyond it (each instance the oracle's answer or HDSM_FLAG_STAGING_OVERFLOW), also with the threads interleaved at every atomic
 operation, where the two staging lists claim their slots."""
@@ -53,6 +54,40 @@ def test_every_shipped_kernel_shape_runs_in_the_emulator(wave, tmp_path):
     for t in shipped:   # the small LDS layout belongs to the four-per-CU kernel, and only to it
         assert emulated[t]["small"] == (t[0] == "k_replan_quad"), t
     assert {s["name"] for s in wave.wave_shapes() if s["kernel"] == "-"} >= {"duo48_320"}   # (CPU only: not in the library)
+
+
+def _create_knobs(n_hor, threads=256, env=None, P=4, RS=18, cus=256):
+    """The knobs of hdsm::pick_shape as hdsm_create settles them on an MI355X (256 CUs): HDSM_DUO_MIN (default CUs + 1), then
+    HDSM_TRI_MIN (2 x CUs + 1, or 0 when duo_min is 0), then HDSM_QUAD_MIN (3 x CUs + 1, or 0 when tri_min is 0)."""
+    env = env or {}
+    duo = int(env.get("HDSM_DUO_MIN", cus + 1))
+    tri = int(env.get("HDSM_TRI_MIN", 2 * cus + 1 if duo > 0 else 0))
+    quad = int(env.get("HDSM_QUAD_MIN", 3 * cus + 1 if tri > 0 else 0))
+    return dict(n=3 * n_hor, threads=threads, P=P, RS=RS, duo_min=duo, tri_min=tri, quad_min=quad)
+
+
+def test_pick_shape_chooses_the_shape_each_pass_launches(wave):
+    """hdsm::pick_shape, the one launch rule of hdsm_api.hip, for (ordinary launch or pass 1, pass 2 of a split launch, rescue):
+    on the knobs with which test_gpu_parity.py forces each shape on its batch, on the bench line and on cfg 3 and cfg 5."""
+    from test_gpu_parity import FORCED_SHAPES
+    passes = ("ordinary", "items", "rescue")
+    forced = {"replan30_64": ("replan30_64", "replan30_64", "replan30_64"), "replan30": ("replan30", "replan30", "replan30"),
+              "duo": ("duo", "duo", "replan30"), "tri": ("tri", "duo", "replan30"), "quad": ("quad", "duo", "replan30"),
+              "replan48_64": ("replan48_64", "replan48_64", "replan48_64"), "replan48": ("replan48", "replan48", "replan48"),
+              "duo48": ("duo48", "duo48", "replan48")}
+    assert set(forced) == set(FORCED_SHAPES)
+    for shape, (n_hor, threads, env) in FORCED_SHAPES.items():
+        knobs = _create_knobs(n_hor, threads, env)
+        blocks = 8 if n_hor == 10 else 4   # (test_every_launch_shape_matches_the_oracle: 16 agents, every 2nd / 4th an instance)
+        assert tuple(wave.pick_shape(knobs, blocks, p) for p in passes) == forced[shape], (shape, knobs)
+    for what, n_inst, n_hor, want in (("bench line", 1024, 10, ("quad", "duo", "replan30")), ("cfg 3", 256, 10, ("replan30", "duo", "replan30")),
+                                      ("cfg 5", 4096, 15, ("duo48", "duo48", "replan48"))):
+        assert tuple(wave.pick_shape(_create_knobs(n_hor), n_inst, p) for p in passes) == want, what
+    # the thresholds at 256 CUs, and the small LDS layout of quad (<= 4 polyhedra of <= 20 rows)
+    for blocks, want in ((256, "replan30"), (257, "duo"), (512, "duo"), (513, "tri"), (768, "tri"), (769, "quad")):
+        assert wave.pick_shape(_create_knobs(10), blocks) == want, blocks
+    assert wave.pick_shape(_create_knobs(10, P=5), 1024) == "tri" and wave.pick_shape(_create_knobs(10, RS=21), 1024) == "tri"
+    assert wave.pick_shape(_create_knobs(15), 1024) == "duo48" and wave.pick_shape(_create_knobs(15), 256) == "replan48"
 
 
 def _shapes(wave, nv):

@@ -46,6 +46,18 @@ def wave_shapes():
     return [dict(s) for s in _shapes]
 
 
+PASSES = ("ordinary", "items", "rescue")   # hdsm::ShapePass: an ordinary launch or pass 1, pass 2 of a split launch, the rescue pass
+
+
+def pick_shape(knobs, blocks, pass_="ordinary"):
+    """hdsm::pick_shape (hdsm_shapes.h): the name of the wave_shapes() row libhdsm.so launches for `blocks` workgroups in `pass_`.
+    knobs: n, threads, P, RS, duo_min, tri_min, quad_min, as hdsm_create settles them."""
+    k = lib().wave_pick_shape(*(C.c_int32(knobs[f]) for f in ("n", "threads", "P", "RS", "duo_min", "tri_min", "quad_min")),
+                              C.c_int32(blocks), C.c_int32(PASSES.index(pass_)))
+    assert k >= 0, k
+    return wave_shapes()[k]["name"]
+
+
 def replan(prm, agent_id, state, ref, n_poly, n_rows, A, b, plans, has_plan, warm=None, bounds_min=256, threads=64, cmax=0, split_budget=0,
            shape=None):
     """Level-2 replan through the device source. shape: a name of wave_shapes() — runs exactly that (NV, CMAX, SMALL, threads)

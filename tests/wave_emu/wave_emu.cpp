@@ -230,34 +230,27 @@ int run_all(const hdsm::Consts& c, hdsm::Args& a, int nthreads) {
 
 extern "C" const char* wave_last_error(void) { return wemu::last_error(); }
 
-// The launch shapes this library runs, (kernel, NV, CMAX, SMALL, threads): every k_replan* kernel hdsm_api.hip instantiates, with the
-// capacities of hdsm_shapes.h, and a few that exist here only (kernel "-"). tests/test_wave_shapes.py holds the first part against the
-// kernel symbols of the built libhdsm.so.
+// The launch shapes this library runs, X(name, kernel, NV, CMAX, SMALL, threads, per_cu): first every row of hdsm_shapes.h — the
+// k_replan* kernels hdsm_api.hip launches, in the order of hdsm::Shape — then a few that exist here only (kernel "-").
+// tests/test_wave_shapes.py holds the first part against the kernel symbols of the built libhdsm.so.
 #define WEMU_SHAPES(X)                                                                                                        \
-  X("replan30_64", "k_replan", 32, hdsm::CMAX30, false, 64)                                                                  \
-  X("replan30", "k_replan", 32, hdsm::CMAX30, false, 256)                                                                    \
-  X("replan48_64", "k_replan", 48, hdsm::CMAX48, false, 64)                                                                  \
-  X("replan48", "k_replan", 48, hdsm::CMAX48, false, 256)                                                                    \
-  X("duo", "k_replan_duo", 32, hdsm::CMAX_DUO, false, 256)                                                                   \
-  X("tri", "k_replan_tri", 32, hdsm::CMAX_TRI, false, 128)                                                                   \
-  X("quad", "k_replan_quad", 32, hdsm::CMAX_QUAD, true, 128)                                                                 \
-  X("duo48", "k_replan_duo48", 48, hdsm::CMAX_DUO48, false, 128)                                                             \
-  X("duo48_320", "-", 48, 320, false, 128) /* the 320-row instantiation the library had until round 6 (hdsm_api.hip) */     \
-  X("tiny30", "-", 32, 16, false, 64)      /* room for 16 staged rows: the overflow path at any size */                      \
-  X("tiny48", "-", 48, 16, false, 64)
+  HDSM_SOLVER_SHAPES(X)                                                                                                       \
+  X(duo48_320, -, 48, 320, false, 128, 2) /* the 320-row instantiation the library had until round 6 (hdsm_api.hip) */       \
+  X(tiny30, -, 32, 16, false, 64, 1)      /* room for 16 staged rows: the overflow path at any size */                        \
+  X(tiny48, -, 48, 16, false, 64, 1)
 
 namespace {
 struct ShapeRow {
   const char *name, *kernel;
   int nv, cmax, small, threads;
 };
-#define WEMU_SHAPE_ROW(name, kernel, nv, cmax, small, threads) {name, kernel, nv, cmax, small ? 1 : 0, threads},
+#define WEMU_SHAPE_ROW(name, kernel, nv, cmax, small, threads, per_cu) {#name, #kernel, nv, cmax, small ? 1 : 0, threads},
 const ShapeRow kShapes[] = {WEMU_SHAPES(WEMU_SHAPE_ROW)};
 constexpr int kNumShapes = sizeof kShapes / sizeof kShapes[0];
 // shape `k` of kShapes: its (NV, CMAX, SMALL) instantiation of the solver
 int run_shape(int k, const hdsm::Consts& c, hdsm::Args& a, int threads) {
   int i = 0;
-#define WEMU_SHAPE_RUN(name, kernel, nv, cmax, small, thr) \
+#define WEMU_SHAPE_RUN(name, kernel, nv, cmax, small, thr, per_cu) \
   if (k == i++) return run_all<nv, cmax, small>(c, a, threads);
   WEMU_SHAPES(WEMU_SHAPE_RUN)
   return -1;
@@ -271,6 +264,14 @@ extern "C" const char* wave_shapes(void) {
     for (const ShapeRow& r : kShapes) text += std::string(r.name) + " " + r.kernel + " " + std::to_string(r.nv) + " " + std::to_string(r.cmax) + " " +
                                              std::to_string(r.small) + " " + std::to_string(r.threads) + "\n";
   return text.c_str();
+}
+
+// hdsm::pick_shape of the product: the row of wave_shapes() (= hdsm::Shape) that hdsm_api.hip launches for `blocks` workgroups in
+// pass `pass` (0 ordinary / pass 1, 1 items = pass 2 of a split launch, 2 rescue) with these knobs
+extern "C" int wave_pick_shape(int32_t n, int32_t threads, int32_t P, int32_t RS, int32_t duo_min, int32_t tri_min, int32_t quad_min,
+                               int32_t blocks, int32_t pass) {
+  if (pass < hdsm::PASS_ORDINARY || pass > hdsm::PASS_RESCUE) return -1;
+  return hdsm::pick_shape({n, threads, P, RS, duo_min, tri_min, quad_min}, blocks, (hdsm::ShapePass)pass);
 }
 
 // per instance of the last wave_replan: the largest count of staged rows (hot + cold) a sweep reached, counted past the capacity
@@ -343,10 +344,9 @@ extern "C" int wave_replan(const hdsm_params* prm, int32_t n_inst, int32_t n_rob
   }
   if (cmax > 0 && cmax <= 16)  // tiny staging capacity: exercises the overflow path in tests
     return c->n <= hdsm::SPLIT_N_MAX ? run_all<32, 16>(*c, a, threads) : run_all<48, 16>(*c, a, threads);
-  if (cmax == 256 && c->n <= hdsm::SPLIT_N_MAX && c->P <= 4 && c->RS <= 20)  // the four-workgroups-per-CU shape: small LDS layout, 256 staged rows
-    return run_all<32, 256, true>(*c, a, threads);
-  if (c->n <= hdsm::SPLIT_N_MAX) return run_all<32, 1536>(*c, a, threads);
-  return run_all<48, 1024>(*c, a, threads);
+  if (cmax == hdsm::CMAX_QUAD && c->n <= hdsm::SPLIT_N_MAX && c->P <= 4 && c->RS <= 20)  // the four-workgroups-per-CU shape: small LDS layout
+    return run_shape(hdsm::SHAPE_quad, *c, a, threads);
+  return run_shape(c->n <= hdsm::SPLIT_N_MAX ? hdsm::SHAPE_replan30 : hdsm::SHAPE_replan48, *c, a, threads);
 }
 
 // Level 1 (fully formed per-step polyhedra, hdsm_solve) through the product's host-side split and the device source
@@ -371,6 +371,5 @@ extern "C" int wave_solve(const hdsm_params* prm, int32_t n_inst, int32_t r_max,
   a.plans = dummy_plans, a.has_plan = &zero, a.traj = traj_out, a.ctrl = ctrl_out, a.used = poly_used;
   a.status = status, a.obj = obj, a.l1_rows = sp.common.data(), a.l1_nrows = sp.n_common.data(), a.l1_rmax = sp.rc_max;
   a.st_iters = qp_iters, a.st_nodes = nodes;  // (may be null)
-  if (c->n <= hdsm::SPLIT_N_MAX) return run_all<32, 1536>(*c, a, threads);
-  return run_all<48, 1024>(*c, a, threads);
+  return run_shape(c->n <= hdsm::SPLIT_N_MAX ? hdsm::SHAPE_replan30 : hdsm::SHAPE_replan48, *c, a, threads);
 }
