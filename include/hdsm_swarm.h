@@ -176,6 +176,27 @@ int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* world, const 
 int hdsm_local_path_host(int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                          const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, int32_t pmax,
                          double* paths, int32_t* n_path, int32_t* status);
+/* ---- the path step's clearance mode (ABI 1.5): the reference's distance-map planner and ShortenDMPPath ---------------------------
+ * Opt-in. The BFS descent above stays as the stand-in for the JPS raw path; what follows it is the reference's (csrc/path_core.h,
+ * 6a-7'): the distance-map planner (a shortest path in a tunnel of radius search_rad round the descent, a step into voxel v costs
+ * 1 + v's potential 1..99, 6-connected, one iteration) and ShortenDMPPath (corners are cut only between points in potential-free
+ * voxels along rays that visit potential-free voxels alone). Status 4 also when the tunnel is wider than 15 voxels or holds more
+ * than 87168 voxels.
+ *   hdsm_swarm_set_path_clearance  search_rad 0 (default): off, the plain step. Non-zero: hdsm_swarm_replan_paths, the path period
+ *                                  and goal changes plan in clearance mode; < 0: no tunnel (every free voxel of the local grid). The
+ *                                  reference ships 1.8 (dmp_search_rad). HDSM_ERR_BAD_ARG for a radius over 15 voxels. The setting
+ *                                  goes into hdsm_dswarm_create like the path period.
+ *   hdsm_local_path_dmp_batch / _host  hdsm_local_path_batch / _host in clearance mode: the same arguments plus search_rad, and
+ *                                  cost[t] (the path's cost: the sum of 1 + potential over its steps plus the start voxel's
+ *                                  potential; -1 on failure) and n_raw[t] (voxels of the planner's chain, 0 on failure). The two
+ *                                  agree bit for bit.                                                                        */
+int hdsm_swarm_set_path_clearance(void* swarm, double search_rad);
+int hdsm_local_path_dmp_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                              const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res,
+                              double search_rad, int32_t pmax, double* paths, int32_t* n_path, int32_t* status, int32_t* cost, int32_t* n_raw);
+int hdsm_local_path_dmp_host(int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res,
+                             double search_rad, int32_t pmax, double* paths, int32_t* n_path, int32_t* status, int32_t* cost, int32_t* n_raw);
 
 /* Number of local agents whose corridor generation failed in the last hdsm_swarm_prepare (seed outside the local grid, or a
  * polyhedron with more rows than max_rows_static); codes[n_local] (may be NULL) receives the hdsm_error per agent. Those

@@ -44,19 +44,36 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_path_batch(BatchArgs a) 
   }
 }
 
-}  // namespace
+// the clearance mode (path_core.h, 6a-7'): the same arguments, the tunnel's mask as a table, the cost and the chain's length out
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp_batch(BatchArgs a, int rn, const uint32_t* rows, int32_t* cost, int32_t* n_raw) {
+  __shared__ hdsm_path::DmpLds lds;
+  const int t = (int)blockIdx.x, tid = (int)threadIdx.x;
+  hdsm_path::PathIn in;
+  in.g.world = a.world;
+  for (int ax = 0; ax < 3; ++ax) {
+    in.g.wdim[ax] = a.world ? a.wdim[ax] : 0, in.g.dim[ax] = a.ldim[ax], in.g.off[ax] = a.off[3 * (size_t)t + ax];
+    in.origin[ax] = a.origin[3 * (size_t)t + ax], in.start[ax] = a.start[3 * (size_t)t + ax], in.goal[ax] = a.goal[3 * (size_t)t + ax];
+  }
+  in.g.ground_k = a.ground_k[t];
+  in.res = a.res;
+  const int st = hdsm_path::plan_dmp_block(in, rn, rows, lds, tid);
+  const int np = st == hdsm_path::PATH_OK ? lds.p.n_out : 0;
+  if (tid == 0) a.status[t] = st, a.n_path[t] = np, cost[t] = np ? lds.cost : -1, n_raw[t] = np ? lds.n_raw : 0;
+  for (int e = tid; e < 3 * a.pmax; e += hdsm_path::THREADS) {
+    const int i = e / 3;
+    a.paths[(size_t)t * a.pmax * 3 + e] = np ? lds.p.out[i < np ? i : np - 1][e % 3] : 0.0;
+  }
+}
 
-extern "C" int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3],
-                                     const int32_t* off, const int32_t* ground_k, const double* origin, const double* start, const double* goal,
-                                     double res, int32_t pmax, double* paths, int32_t* n_path, int32_t* status) {
-  if (n < 0 || !ldim || !off || !ground_k || !origin || !start || !goal || !(res > 0) || pmax < 2 || !paths || !n_path || !status ||
-      (world && !wdim))
-    return HDSM_ERR_BAD_ARG;
+// hdsm_local_path_batch (mask == nullptr) and hdsm_local_path_dmp_batch
+int run_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+              const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, int32_t pmax, double* paths,
+              int32_t* n_path, int32_t* status, const hdsm_path::DmpMask* mask, int32_t* cost, int32_t* n_raw) {
   if (n == 0) return HDSM_OK;
   if (pmax > hdsm_sw::PATH_PTS) {  // (the device keeps PATH_PTS points: the rows beyond repeat the last point, as on the host)
     std::vector<double> tmp((size_t)n * hdsm_sw::PATH_PTS * 3);
-    const int rc = hdsm_local_path_batch(device, n, world, wdim, ldim, off, ground_k, origin, start, goal, res, hdsm_sw::PATH_PTS, tmp.data(),
-                                         n_path, status);
+    const int rc = run_batch(device, n, world, wdim, ldim, off, ground_k, origin, start, goal, res, hdsm_sw::PATH_PTS, tmp.data(), n_path, status,
+                             mask, cost, n_raw);
     if (rc) return rc;
     for (int t = 0; t < n; ++t)
       for (int i = 0; i < pmax; ++i)
@@ -70,7 +87,8 @@ extern "C" int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* wo
   a.res = res, a.pmax = pmax;
   for (int ax = 0; ax < 3; ++ax) a.wdim[ax] = world ? wdim[ax] : 0, a.ldim[ax] = ldim[ax];
   int8_t* d_world = nullptr;
-  int32_t *d_off = nullptr, *d_gk = nullptr, *d_np = nullptr, *d_st = nullptr;
+  int32_t *d_off = nullptr, *d_gk = nullptr, *d_np = nullptr, *d_st = nullptr, *d_cost = nullptr, *d_raw = nullptr;
+  uint32_t* d_rows = nullptr;
   double *d_org = nullptr, *d_s = nullptr, *d_g = nullptr, *d_paths = nullptr;
   hipError_t e = hipSuccess;
   auto ok = [&](hipError_t r) {
@@ -80,25 +98,52 @@ extern "C" int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* wo
   if (world) ok(hipMalloc(&d_world, wbytes));
   ok(hipMalloc(&d_off, N * 12)), ok(hipMalloc(&d_gk, N * 4)), ok(hipMalloc(&d_np, N * 4)), ok(hipMalloc(&d_st, N * 4));
   ok(hipMalloc(&d_org, N * 24)), ok(hipMalloc(&d_s, N * 24)), ok(hipMalloc(&d_g, N * 24)), ok(hipMalloc(&d_paths, N * pmax * 24));
+  if (mask) ok(hipMalloc(&d_cost, N * 4)), ok(hipMalloc(&d_raw, N * 4)), ok(hipMalloc(&d_rows, sizeof mask->rows));
   if (e == hipSuccess) {
     if (world) ok(hipMemcpy(d_world, world, wbytes, hipMemcpyHostToDevice));
     ok(hipMemcpy(d_off, off, N * 12, hipMemcpyHostToDevice)), ok(hipMemcpy(d_gk, ground_k, N * 4, hipMemcpyHostToDevice));
     ok(hipMemcpy(d_org, origin, N * 24, hipMemcpyHostToDevice)), ok(hipMemcpy(d_s, start, N * 24, hipMemcpyHostToDevice));
     ok(hipMemcpy(d_g, goal, N * 24, hipMemcpyHostToDevice));
+    if (mask) ok(hipMemcpy(d_rows, mask->rows, sizeof mask->rows, hipMemcpyHostToDevice));
   }
   if (e == hipSuccess) {
     a.world = d_world, a.off = d_off, a.ground_k = d_gk, a.origin = d_org, a.start = d_s, a.goal = d_g;
     a.paths = d_paths, a.n_path = d_np, a.status = d_st;
-    hipLaunchKernelGGL(k_path_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a);
+    if (mask) hipLaunchKernelGGL(k_dmp_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a, mask->rn, d_rows, d_cost, d_raw);
+    else hipLaunchKernelGGL(k_path_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a);
     ok(hipGetLastError());
     ok(hipDeviceSynchronize());
   }
   if (e == hipSuccess) {
     ok(hipMemcpy(paths, d_paths, N * pmax * 24, hipMemcpyDeviceToHost));
     ok(hipMemcpy(n_path, d_np, N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(status, d_st, N * 4, hipMemcpyDeviceToHost));
+    if (mask) ok(hipMemcpy(cost, d_cost, N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(n_raw, d_raw, N * 4, hipMemcpyDeviceToHost));
   }
-  void* ptrs[] = {d_world, d_off, d_gk, d_np, d_st, d_org, d_s, d_g, d_paths};
+  void* ptrs[] = {d_world, d_off, d_gk, d_np, d_st, d_org, d_s, d_g, d_paths, d_cost, d_raw, d_rows};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   return e == hipSuccess ? HDSM_OK : HDSM_ERR_DEVICE;
+}
+
+}  // namespace
+
+extern "C" int hdsm_local_path_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3],
+                                     const int32_t* off, const int32_t* ground_k, const double* origin, const double* start, const double* goal,
+                                     double res, int32_t pmax, double* paths, int32_t* n_path, int32_t* status) {
+  if (n < 0 || !ldim || !off || !ground_k || !origin || !start || !goal || !(res > 0) || pmax < 2 || !paths || !n_path || !status ||
+      (world && !wdim))
+    return HDSM_ERR_BAD_ARG;
+  return run_batch(device, n, world, wdim, ldim, off, ground_k, origin, start, goal, res, pmax, paths, n_path, status, nullptr, nullptr, nullptr);
+}
+
+extern "C" int hdsm_local_path_dmp_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3],
+                                         const int32_t* off, const int32_t* ground_k, const double* origin, const double* start,
+                                         const double* goal, double res, double search_rad, int32_t pmax, double* paths, int32_t* n_path,
+                                         int32_t* status, int32_t* cost, int32_t* n_raw) {
+  if (n < 0 || !ldim || !off || !ground_k || !origin || !start || !goal || !(res > 0) || !(search_rad == search_rad) || pmax < 2 || !paths ||
+      !n_path || !status || !cost || !n_raw || (world && !wdim))
+    return HDSM_ERR_BAD_ARG;
+  hdsm_path::DmpMask mask;
+  hdsm_path::dmp_build_mask(search_rad, res, &mask);  // (a radius over DMP_MAX_RN voxels: status 4 for every case in a world)
+  return run_batch(device, n, world, wdim, ldim, off, ground_k, origin, start, goal, res, pmax, paths, n_path, status, &mask, cost, n_raw);
 }

@@ -74,6 +74,10 @@ struct Swarm {
   int path_period = 0;
   long long path_round = 0;
   std::vector<uint8_t> path_due;
+  // the path step's clearance mode (hdsm_swarm_set_path_clearance): the tunnel's radius (0: off, the plain step) and its mask
+  double path_clearance = 0;
+  hdsm_path::DmpMask dmp_mask{};
+  const hdsm_path::DmpMask* dmp() const { return path_clearance != 0 ? &dmp_mask : nullptr; }
   ~Swarm() {
     for (AgentX& a : extra) hdsm_stats_destroy(a.stats);
   }
@@ -370,10 +374,12 @@ struct Router {
 
 // Agent::UpdatePath (AC:261-454) for one agent, the rule of path_core.h: on success the new path replaces path_curr_, on failure
 // the agent keeps its path; the status stays in ag.path_rc (hdsm_swarm_path_errors)
-int replan_agent(const hdsm_sw::Cfg& cc, AgentS& ag) {
+// (dmp: the tunnel's mask in clearance mode, else NULL)
+int replan_agent(const hdsm_sw::Cfg& cc, AgentS& ag, const hdsm_path::DmpMask* dmp) {
   V3 out[hdsm_sw::PATH_PTS];
-  int n = 0;
-  const int st = hdsm_path::plan_serial(hdsm_path::agent_problem(cc, ag, ag.goal), out, &n);
+  int n = 0, cost = 0, n_raw = 0;
+  const hdsm_path::PathIn in = hdsm_path::agent_problem(cc, ag, ag.goal);
+  const int st = dmp ? hdsm_path::plan_dmp_serial(in, *dmp, out, &n, &cost, &n_raw) : hdsm_path::plan_serial(in, out, &n);
   ag.path_rc = st;
   if (st == hdsm_path::PATH_OK) {
     ag.n_path = n;
@@ -388,7 +394,7 @@ void path_round(Swarm& sw) {
   const hdsm_sw::Cfg cc = sw.core_cfg();
   for (int k = 0; k < sw.n_local; ++k)
     if (all || sw.path_due[k]) {
-      replan_agent(cc, sw.agents[k]);
+      replan_agent(cc, sw.agents[k], sw.dmp());
       sw.path_due[k] = 0;
     }
   ++sw.path_round;
@@ -673,12 +679,21 @@ int hdsm_swarm_set_path_period(void* swarm, int32_t period) {
   return HDSM_OK;
 }
 
+int hdsm_swarm_set_path_clearance(void* swarm, double search_rad) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !(search_rad == search_rad)) return HDSM_ERR_BAD_ARG;
+  hdsm_path::DmpMask mask{};
+  if (search_rad != 0 && !hdsm_path::dmp_build_mask(search_rad, sw->cfg.voxel_size, &mask)) return HDSM_ERR_BAD_ARG;  // over DMP_MAX_RN voxels
+  sw->path_clearance = search_rad, sw->dmp_mask = mask;
+  return HDSM_OK;
+}
+
 int hdsm_swarm_replan_paths(void* swarm, int32_t* n_failed) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw) return HDSM_ERR_BAD_ARG;
   const hdsm_sw::Cfg cc = sw->core_cfg();
   int failed = 0;
-  for (int k = 0; k < sw->n_local; ++k) failed += replan_agent(cc, sw->agents[k]) != hdsm_path::PATH_OK;
+  for (int k = 0; k < sw->n_local; ++k) failed += replan_agent(cc, sw->agents[k], sw->dmp()) != hdsm_path::PATH_OK;
   if (n_failed) *n_failed = failed;
   return HDSM_OK;
 }
@@ -740,6 +755,14 @@ int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, u
   if (round) *round = sw->path_round;
   if (due)
     for (int k = 0; k < sw->n_local; ++k) due[k] = sw->path_due[k];
+  return HDSM_OK;
+}
+
+// the clearance radius of the path step (0: off), for the device-resident loop
+int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !search_rad) return HDSM_ERR_BAD_ARG;
+  *search_rad = sw->path_clearance;
   return HDSM_OK;
 }
 

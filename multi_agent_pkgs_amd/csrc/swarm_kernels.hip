@@ -47,6 +47,7 @@ extern "C" int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n
                                        double worigin[3]);
 extern "C" int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local);
 extern "C" int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
+extern "C" int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
 extern "C" int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
 
 namespace {
@@ -544,6 +545,29 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_path(Cfg c, const int32_
     for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.out[t / 3][t % 3];
 }
 
+// k_path in clearance mode (path_core.h, 6a-7': the distance-map planner and ShortenDMPPath after the descent); rn, rows: the tunnel's
+// mask (hdsm_path::DmpMask). The same bookkeeping as k_path.
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
+                                                             unsigned long long* cnt, int rn, const uint32_t* rows) {
+  __shared__ hdsm_path::DmpLds lds;
+  const int tid = (int)threadIdx.x;
+  const int k = idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x;
+  AgentS& ag = agents[k];
+  const V3 goal = {{goals[3 * (size_t)k], goals[3 * (size_t)k + 1], goals[3 * (size_t)k + 2]}};
+  const hdsm_path::PathIn in = hdsm_path::agent_problem(c, ag, goal);
+  const int st = hdsm_path::plan_dmp_block(in, rn, rows, lds, tid);
+  __syncthreads();  // (every thread has read the agent's state)
+  const int n = lds.p.n_out;
+  if (tid == 0) {
+    ag.goal = goal, ag.path_rc = st;
+    if (st == hdsm_path::PATH_OK) ag.n_path = n;
+    atomicAdd(&cnt[0], 1ull);
+    if (st != hdsm_path::PATH_OK) atomicAdd(&cnt[1], 1ull);
+  }
+  if (st == hdsm_path::PATH_OK)
+    for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.p.out[t / 3][t % 3];
+}
+
 __global__ __launch_bounds__(256) void k_flags(int rec, int n, const double* plans, uint8_t* has) {
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (k >= n) return;
@@ -582,6 +606,10 @@ struct DSwarm {
   unsigned long long* d_path_cnt = nullptr;
   bool path_valid = false;
   hipEvent_t path_ev[2] = {nullptr, nullptr};
+  // the clearance mode (hdsm_swarm_set_path_clearance before hdsm_dswarm_create): k_dmp instead of k_path, the mask's rows on the device
+  bool dmp = false;
+  int dmp_rn = 0;
+  uint32_t* d_dmp_rows = nullptr;
 };
 
 template <class T>
@@ -594,7 +622,7 @@ hipError_t dalloc(T** p, size_t count) {
 void free_all(DSwarm* d) {
   void* ptrs[] = {d->d_cap, d->d_agents, d->d_cache, d->d_world, d->d_path, d->d_ref_full, d->d_ref, d->d_pv, d->d_state, d->d_A, d->d_b, d->d_traj,
                   d->d_ctrl, d->d_obj, d->d_local, d->d_plans, d->d_npath, d->d_id, d->d_npoly, d->d_nrows, d->d_status, d->d_fails,
-                  d->d_used, d->d_has, d->d_due, d->d_goals, d->d_path_cnt};
+                  d->d_used, d->d_has, d->d_due, d->d_goals, d->d_path_cnt, d->d_dmp_rows};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (hipEvent_t e : d->ev)
@@ -778,6 +806,17 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
     rc = hdsm_swarm_export_path_state(swarm, &period, &round, d->due.data());
     d->path_period = period, d->path_round = round;
   }
+  if (rc == HDSM_OK) {
+    double rad = 0;
+    rc = hdsm_swarm_export_path_clearance(swarm, &rad);
+    if (rc == HDSM_OK && rad != 0) {
+      hdsm_path::DmpMask mask{};
+      if (!hdsm_path::dmp_build_mask(rad, d->cfg.voxel_size, &mask)) rc = HDSM_ERR_BAD_ARG;
+      d->dmp = true, d->dmp_rn = mask.rn;
+      ok(dalloc(&d->d_dmp_rows, sizeof mask.rows / sizeof mask.rows[0]));
+      if (e == hipSuccess) ok(hipMemcpy(d->d_dmp_rows, mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
+    }
+  }
   if (e == hipSuccess && n) {
     AgentS* tmp = static_cast<AgentS*>(std::malloc(n * sizeof(AgentS)));
     if (!tmp) e = hipErrorOutOfMemory;
@@ -861,8 +900,12 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
     d->path_valid = false;
     if (n_plan > 0) {
       if (timing) HIP_TRY(hipEventRecord(d->path_ev[0], st));
-      hipLaunchKernelGGL(k_path, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
-                         d->d_path_cnt);
+      if (d->dmp)
+        hipLaunchKernelGGL(k_dmp, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
+                           d->d_path_cnt, d->dmp_rn, d->d_dmp_rows);
+      else
+        hipLaunchKernelGGL(k_path, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
+                           d->d_path_cnt);
       HIP_TRY(hipGetLastError());
       if (timing) {
         HIP_TRY(hipEventRecord(d->path_ev[1], st));

@@ -28,7 +28,7 @@ EXPORTS = ("hdsm_version", "hdsm_last_error", "hdsm_default_params", "hdsm_creat
            "hdsm_dswarm_create", "hdsm_dswarm_upload_plans", "hdsm_dswarm_round", "hdsm_dswarm_download", "hdsm_dswarm_destroy", "hdsm_dswarm_last_error",
            "hdsm_dswarm_set_phase_timing", "hdsm_dswarm_last_phase_ms", "hdsm_dswarm_cache_stats",
            "hdsm_swarm_set_goals", "hdsm_swarm_set_path_period", "hdsm_swarm_replan_paths", "hdsm_swarm_path_errors", "hdsm_local_path_batch",
-           "hdsm_local_path_host", "hdsm_dswarm_set_goals", "hdsm_dswarm_path_stats", "hdsm_dswarm_last_path_ms",
+           "hdsm_local_path_host", "hdsm_swarm_set_path_clearance", "hdsm_local_path_dmp_batch", "hdsm_local_path_dmp_host", "hdsm_dswarm_set_goals", "hdsm_dswarm_path_stats", "hdsm_dswarm_last_path_ms",
            "hdsm_stats_create", "hdsm_stats_destroy", "hdsm_stats_add", "hdsm_stats_add_state", "hdsm_stats_add_latency",
            "hdsm_stats_shutdown", "hdsm_map_preprocess", "hdsm_map_preprocess_device", "hdsm_map_last_error")
 
@@ -331,7 +331,7 @@ def poly_octa3d_batch(world, ldim, off, ground_k, seed, variant, origin, n_it=42
 PATH_PTS = 48  # points of a global path (csrc/swarm_core.h)
 
 
-def _local_path(fn, lead, world, ldim, off, ground_k, origin, start, goal, res, pmax):
+def _local_path(fn, lead, world, ldim, off, ground_k, origin, start, goal, res, pmax, search_rad=None):
     L = load()
     i32, d = C.c_int32, C.c_double
     off, ground_k = _i32(off), _i32(ground_k)
@@ -346,11 +346,15 @@ def _local_path(fn, lead, world, ldim, off, ground_k, origin, start, goal, res, 
         wp = world.ctypes.data_as(C.POINTER(C.c_int8))
     paths = np.zeros((n, pmax, 3))
     n_path, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    extra_in = () if search_rad is None else (C.c_double(search_rad),)
+    cost, n_raw = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+    extra_out = () if search_rad is None else (_p(cost, i32), _p(n_raw, i32))
     rc = getattr(L, fn)(*lead, C.c_int32(n), wp, _p(wdim, i32) if wdim is not None else None, _p(ldim, i32), _p(off, i32), _p(ground_k, i32),
-                        _p(origin, d), _p(start, d), _p(goal, d), C.c_double(res), C.c_int32(pmax), _p(paths, d), _p(n_path, i32), _p(status, i32))
+                        _p(origin, d), _p(start, d), _p(goal, d), C.c_double(res), *extra_in, C.c_int32(pmax), _p(paths, d), _p(n_path, i32),
+                        _p(status, i32), *extra_out)
     if rc:
         raise HdsmError(rc, fn)
-    return paths, n_path, status
+    return (paths, n_path, status) if search_rad is None else (paths, n_path, status, cost, n_raw)
 
 
 def local_path_batch(world, ldim, off, ground_k, origin, start, goal, res=0.3, pmax=PATH_PTS, device=0):
@@ -363,3 +367,16 @@ def local_path_batch(world, ldim, off, ground_k, origin, start, goal, res=0.3, p
 def local_path_host(world, ldim, off, ground_k, origin, start, goal, res=0.3, pmax=PATH_PTS):
     """hdsm_local_path_host: the same batch on the CPU (bit for bit what local_path_batch returns)."""
     return _local_path("hdsm_local_path_host", (), world, ldim, off, ground_k, origin, start, goal, res, pmax)
+
+
+def local_path_dmp_batch(world, ldim, off, ground_k, origin, start, goal, search_rad=1.8, res=0.3, pmax=PATH_PTS, device=0):
+    """hdsm_local_path_dmp_batch: local_path_batch in clearance mode (the distance-map planner in a tunnel of radius search_rad round
+    the descent, < 0 no tunnel, and ShortenDMPPath). Returns paths, n_path, status, cost [n] (the path's cost, -1 on failure) and
+    n_raw [n] (voxels of the planner's chain)."""
+    return _local_path("hdsm_local_path_dmp_batch", (C.c_int32(device),), world, ldim, off, ground_k, origin, start, goal, res, pmax,
+                       search_rad=float(search_rad))
+
+
+def local_path_dmp_host(world, ldim, off, ground_k, origin, start, goal, search_rad=1.8, res=0.3, pmax=PATH_PTS):
+    """hdsm_local_path_dmp_host: the same batch on the CPU (bit for bit what local_path_dmp_batch returns)."""
+    return _local_path("hdsm_local_path_dmp_host", (), world, ldim, off, ground_k, origin, start, goal, res, pmax, search_rad=float(search_rad))

@@ -188,6 +188,13 @@ class SwarmShard:
         if rc:
             raise _lib.HdsmError(rc, "hdsm_swarm_set_goals")
 
+    def set_path_clearance(self, search_rad):
+        """hdsm_swarm_set_path_clearance: 0 (the default) the plain path step; non-zero: the distance-map planner in a tunnel of that
+        radius round the descent (< 0: no tunnel) and ShortenDMPPath. The reference ships 1.8. Set before DeviceSwarm is made."""
+        rc = self.lib.hdsm_swarm_set_path_clearance(self.h, C.c_double(float(search_rad)))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_set_path_clearance")
+
     def set_path_period(self, period):
         """hdsm_swarm_set_path_period: every agent plans a new path every `period`-th round (0: never, the default)."""
         rc = self.lib.hdsm_swarm_set_path_period(self.h, C.c_int32(int(period)))
