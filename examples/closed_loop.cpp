@@ -35,6 +35,7 @@ int main(int argc, char** argv) {
     return 2;
   }
   if (hdsm_swarm_create(&prm, &cfg, n, 0, n, starts.data(), goals.data(), &swarm) != HDSM_OK) return 2;
+  if (hdsm_swarm_set_audit(swarm, 1, 1.0) != HDSM_OK) return 2;  // the flight audit: separation over the whole flown step
 
   std::vector<int32_t> id(n), n_poly(n), n_rows(n * P), status(n);
   std::vector<double> state(9 * n), ref(6 * N * n), A((size_t)n * P * RS * 3), b((size_t)n * P * RS);
@@ -43,7 +44,7 @@ int main(int argc, char** argv) {
   std::vector<double> plans_new(plans.size()), pos(3 * n), dist(n);
   std::vector<int32_t> nfail(n);
 
-  double solve_ms = 0, min_sep = 1e9;
+  double solve_ms = 0;
   int failures = 0;
   for (int r = 0; r < rounds; ++r) {
     if (hdsm_swarm_prepare(swarm, plans.data(), has.data(), id.data(), state.data(), ref.data(), n_poly.data(), n_rows.data(),
@@ -61,18 +62,30 @@ int main(int argc, char** argv) {
     if (hdsm_swarm_commit(swarm, traj.data(), ctrl.data(), used.data(), status.data(), plans_new.data(), has_new.data()) != HDSM_OK)
       return 3;
     plans.swap(plans_new), has.swap(has_new);
-    hdsm_swarm_state(swarm, pos.data(), dist.data(), nfail.data());
-    for (int i = 0; i < n; ++i)
-      for (int j = i + 1; j < n; ++j) {
-        const double dx = pos[3 * i] - pos[3 * j], dy = pos[3 * i + 1] - pos[3 * j + 1], dz = pos[3 * i + 2] - pos[3 * j + 2];
-        min_sep = std::fmin(min_sep, std::sqrt(dx * dx + dy * dy + dz * dz));
-      }
+    if (hdsm_swarm_audit(swarm, plans.data(), has.data()) != HDSM_OK) return 3;  // after the gather: the records of all agents
   }
+  hdsm_swarm_state(swarm, pos.data(), dist.data(), nfail.data());
   double far = 0;
   for (int k = 0; k < n; ++k) far = std::fmax(far, dist[k]);
+  // the flight report: the smallest separation ratio flown (sigma = 1: the ellipsoids of two drones touch), who and when
+  std::vector<hdsm_flight_report> rep(n);
+  if (hdsm_swarm_flight_report(swarm, rep.data()) != HDSM_OK) return 3;
+  int worst = 0;
+  long long close_rounds = 0;
+  double flown = 0, speed_max = 0;
+  for (int k = 0; k < n; ++k) {
+    if (rep[k].sep2_min < rep[worst].sep2_min) worst = k;
+    close_rounds += rep[k].close_rounds, flown += rep[k].dist, speed_max = std::fmax(speed_max, rep[k].speed_max);
+  }
+  // sigma of a lone agent: infinite (no partner). With the equal radii of the default parameters the safety ellipsoid is a sphere and
+  // sigma * 2 * drone_radius is the centre distance in metres; with unequal radii it is no length, and only sigma is printed.
+  const double sigma = rep[worst].sep_partner >= 0 ? std::sqrt(rep[worst].sep2_min) : INFINITY;
+  const double approach = prm.drone_radius == prm.drone_z_offset ? sigma * 2 * prm.drone_radius : NAN;
   std::printf("closed_loop: %d agents, %d rounds, %.3f ms per replan round through hdsm_replan (host buffers), "
               "instances without solution %d, closest approach %.3f m, farthest agent %.2f m from its goal\n",
-              n, rounds, solve_ms / rounds, failures, min_sep, far);
+              n, rounds, solve_ms / rounds, failures, approach, far);
+  std::printf("flight report: sigma_min %.4f (agents %d and %d, round %lld), agent-rounds below sigma 1: %lld, %.1f m flown, top speed %.2f m/s\n",
+              sigma, worst, (int)rep[worst].sep_partner, (long long)rep[worst].sep_round, close_rounds, flown, speed_max);
   hdsm_swarm_destroy(swarm);
   hdsm_destroy(solver);
   return 0;

@@ -335,7 +335,9 @@ const char* hdsm_last_error(void);
 /* Library/ABI version: (major << 16) | minor. 1.1: hdsm_params grew the execution knobs and time_limit_s;
  * 1.2: + hdsm_poly_octa3d_batch_wave / hdsm_poly_octa3d_device_wave (hdsm_swarm.h), hdsm_set_kernel_timing /
  * hdsm_last_kernel_ms; 1.3: + hdsm_host_register / hdsm_host_unregister, hdsm_swarm_yaw / hdsm_swarm_view
- * (hdsm_swarm.h); nothing removed or changed.                                                                */
+ * (hdsm_swarm.h); 1.4: + the path step, 1.5: + its clearance mode, 1.6: + the flight audit and the state history
+ * (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report /
+ * _last_audit_round / _last_audit_ms / _set_history / _download_history; all in hdsm_swarm.h); nothing removed or changed.   */
 int32_t hdsm_version(void);
 
 #ifdef __cplusplus

@@ -252,6 +252,78 @@ int hdsm_dswarm_set_goals(void* dswarm, const double* goals);
 int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]);
 int hdsm_dswarm_last_path_ms(void* dswarm, float* ms);
 
+/* ---- the flight audit (ABI 1.6): separation, obstacle contact and state history of what was flown ------------------------------
+ * Opt-in; with the audit and the history off nothing is launched, allocated or written. One definition (csrc/audit_core.h) shared by
+ * the host form, the host mirror and the device loop (k_audit_pack / k_audit / k_audit_track, csrc/audit_kernels.hip):
+ *   separation   q = (dx^2 + dy^2) / (2 drone_radius)^2 + dz^2 / (2 drone_z_offset)^2 of the vector between two agents, sigma = sqrt(q);
+ *                q >= 1 is what the separating planes ask for (AC:1158-1170). Both agents fly their records synchronously and
+ *                linearly through the sub-steps s < step_plan (plans[.][s][0:3] -> plans[.][s+1][0:3]); the minimum of q along a
+ *                sub-step is taken in closed form, so the whole flown segment is covered, not only the round boundaries. An agent's
+ *                sep2 is the minimum of q over sub-steps and partners (ties: the smaller sub-step, then the lower id); without a
+ *                partner sep2 = DBL_MAX and partner = -1. Agents with has_plan == 0 are neither subjects nor partners (their
+ *                record is the empty one and their flight report does not advance).
+ *   own track    per sub-step the world voxel under the end point (>= 100 occupied, < 0 unknown, 1..99 summed into pot), whether the
+ *                reference's Raycast from the start to the end point hits an occupied voxel of the world grid (crossed), the length
+ *                flown, and speed = |v| of plans[.][step_plan] (what SaveStateHistory averages, AC:1994-2008). Outside the world: free.
+ * hdsm_flight_audit_host / _batch: plans_all [n_rob][n_hor+1][9], has_plan [n_rob], the subjects [first, first + n_local), the
+ * world int8 [wdim[2]][wdim[1]][wdim[0]] (NULL = free space; wdim, worigin, voxel_size then unused) -> out[n_local]. The batch form
+ * takes host pointers and copies in and out (PCIe-inclusive); the two agree bit for bit. HDSM_ERR_BAD_ARG for radii <= 0,
+ * step_plan < 1 or > n_hor, or a window outside [0, n_rob). */
+typedef struct hdsm_audit_round {      /* one agent, one round */
+  double  sep2;                        /* min q; DBL_MAX without a partner                      */
+  int32_t partner, substep;            /* global id (-1), sub-step of the minimum               */
+  int32_t occupied, unknown, crossed;  /* of this round's step_plan positions / sub-segments    */
+  int32_t pot;                         /* sum of the potential values 1..99 under them          */
+  double  dist, speed;
+} hdsm_audit_round;
+
+typedef struct hdsm_flight_report {    /* one agent, since the audit was first switched on      */
+  int64_t rounds, positions;           /* rounds audited; positions sampled (rounds * step_plan) */
+  double  sep2_min;  int32_t sep_partner, sep_substep;  int64_t sep_round; /* sep_round: index among the audited rounds, -1 none */
+  int64_t close_rounds;                /* rounds with q < sep_warn^2                            */
+  int64_t occupied, unknown, crossed, pot_sum;
+  double  dist, speed_sum, speed_max;  /* mean speed = speed_sum / rounds (AC:1994-2008)        */
+} hdsm_flight_report;
+
+int hdsm_flight_audit_host(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan, int32_t first,
+                           int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world, const int32_t wdim[3],
+                           const double worigin[3], double voxel_size, hdsm_audit_round* out);
+int hdsm_flight_audit_batch(int32_t device, int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan,
+                            int32_t first, int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world,
+                            const int32_t wdim[3], const double worigin[3], double voxel_size, hdsm_audit_round* out);
+/* The host mirror. hdsm_swarm_set_audit: on / off and sep_warn (> 0; the reference value is 1.0); the flight record starts when the
+ * audit is switched on for the first time and is kept from then on. hdsm_swarm_audit adds one round: call it after the gather, with
+ * the records all agents published this round (radii of hdsm_params, step_plan of the configuration, the world of
+ * hdsm_swarm_set_world); an error while the audit is off. hdsm_swarm_flight_report: report[n_local]; an error if the audit was
+ * never switched on. hdsm_swarm_get_audit: the setting as it stands (sep_warn may be NULL) — also after hdsm_dswarm_download
+ * brought back what the device loop was left with. */
+int hdsm_swarm_set_audit(void* swarm, int32_t on, double sep_warn);
+int hdsm_swarm_get_audit(void* swarm, int32_t* on, double* sep_warn);
+int hdsm_swarm_audit(void* swarm, const double* plans_all, const uint8_t* has_plan);
+int hdsm_swarm_flight_report(void* swarm, hdsm_flight_report* report);
+/* The device loop. The setting and the record go into hdsm_dswarm_create and come back with hdsm_dswarm_download(swarm): a flight
+ * taken over in mid-air keeps its record. The audit runs at the end of hdsm_dswarm_round (after k_commit, on several ranks after
+ * the exchange) on the records of all agents. hdsm_dswarm_set_audit switches it later (synchronises), hdsm_dswarm_flight_report
+ * synchronises and copies report[n_local], hdsm_dswarm_last_audit_round the last round's out[n_local] (an error while the audit is off
+ * or before its first round). hdsm_dswarm_last_audit_ms: with phase timing on, the duration of the last timed round's audit
+ * launches; 0 if that round launched none. hdsm_dswarm_last_phase_ms keeps its seven entries: the audit starts after [6].
+ * History (state_hist_, AC:240-245): hdsm_dswarm_set_history(capacity_rounds) allocates capacity x n_local x 9 doubles on the
+ * device (0: off, frees them; any call starts an empty history) and every round writes state_curr after the commit into it. When it
+ * is full, recording stops and the rounds lost are counted: it never wraps. hdsm_dswarm_download_history synchronises and copies the
+ * first min(recorded, max_rounds) rounds into hist [.][n_local][9] (hist may be NULL), n_rounds = rounds recorded, dropped = rounds
+ * lost; with a host mirror given, every recorded round not yet delivered is appended once to each agent's planner record (stamp =
+ * the mirror's (round + 1) dt step_plan, as after a host round), so hdsm_swarm_shutdown writes state_hist_<id>.csv and the velocity
+ * lines for a device flight as it does for a host flight. The mirror's round count, which makes the stamps, advances by the rounds
+ * delivered this way and by nothing else of a device flight: hdsm_dswarm_download does not move it (as before 1.6), so rounds flown
+ * on the device without a history, or lost to a full one, leave no gap in the stamps — a host round flown afterwards is stamped as
+ * the next one after the last record. */
+int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn);
+int hdsm_dswarm_flight_report(void* dswarm, hdsm_flight_report* report);
+int hdsm_dswarm_last_audit_round(void* dswarm, hdsm_audit_round* out);
+int hdsm_dswarm_last_audit_ms(void* dswarm, float* ms);
+int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds);
+int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_t max_rounds, int32_t* n_rounds, int32_t* dropped);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

@@ -18,6 +18,7 @@
 
 #include "../../include/hdsm_stats.h"
 #include "../../include/hdsm_swarm.h"
+#include "audit_core.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -78,6 +79,11 @@ struct Swarm {
   double path_clearance = 0;
   hdsm_path::DmpMask dmp_mask{};
   const hdsm_path::DmpMask* dmp() const { return path_clearance != 0 ? &dmp_mask : nullptr; }
+  // the flight audit (audit_core.h; hdsm_swarm_set_audit): the record starts when the audit is first switched on and is kept
+  bool audit_on = false, audit_ever = false;
+  double sep_warn = 1.0;
+  std::vector<hdsm_flight_report> flight;
+  std::vector<hdsm_audit_round> audit_last;
   ~Swarm() {
     for (AgentX& a : extra) hdsm_stats_destroy(a.stats);
   }
@@ -718,6 +724,78 @@ int hdsm_swarm_corridor_errors(void* swarm, int32_t* codes) {
     n += sw->agents[k].corridor_rc != 0;
   }
   return n;
+}
+
+// ---- the flight audit of the host mirror (audit_core.h) ----
+int hdsm_swarm_set_audit(void* swarm, int32_t on, double sep_warn) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !(sep_warn > 0)) return HDSM_ERR_BAD_ARG;
+  if (on && !sw->audit_ever) {
+    sw->flight.resize((size_t)sw->n_local);
+    for (hdsm_flight_report& r : sw->flight) hdsm_audit::empty_report(&r);
+    sw->audit_ever = true;
+  }
+  sw->audit_on = on != 0, sw->sep_warn = sep_warn;
+  return HDSM_OK;
+}
+
+int hdsm_swarm_get_audit(void* swarm, int32_t* on, double* sep_warn) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !on) return HDSM_ERR_BAD_ARG;
+  *on = sw->audit_on ? 1 : 0;
+  if (sep_warn) *sep_warn = sw->sep_warn;
+  return HDSM_OK;
+}
+
+int hdsm_swarm_audit(void* swarm, const double* plans_all, const uint8_t* has_plan) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !plans_all || !has_plan || !sw->audit_on) return HDSM_ERR_BAD_ARG;
+  sw->audit_last.resize((size_t)sw->n_local);
+  const int rc = hdsm_flight_audit_host(sw->n_rob, plans_all, has_plan, sw->prm.n_hor, sw->cfg.step_plan, sw->first_id, sw->n_local,
+                                        sw->prm.drone_radius, sw->prm.drone_z_offset, sw->has_world ? sw->world.data() : nullptr, sw->wdim,
+                                        sw->worigin, sw->cfg.voxel_size, sw->audit_last.data());
+  if (rc) return rc;
+  const double warn2 = sw->sep_warn * sw->sep_warn;
+  for (int k = 0; k < sw->n_local; ++k)
+    if (has_plan[sw->first_id + k]) hdsm_audit::accumulate(&sw->flight[k], sw->audit_last[k], sw->cfg.step_plan, warn2);
+  return HDSM_OK;
+}
+
+int hdsm_swarm_flight_report(void* swarm, hdsm_flight_report* report) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !sw->audit_ever || (sw->n_local && !report)) return HDSM_ERR_BAD_ARG;
+  for (int k = 0; k < sw->n_local; ++k) report[k] = sw->flight[k];
+  return HDSM_OK;
+}
+
+// the audit's setting and record in and out of the device-resident loop (report [n_local], may be NULL)
+int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !on || !ever || !sep_warn) return HDSM_ERR_BAD_ARG;
+  *on = sw->audit_on ? 1 : 0, *ever = sw->audit_ever ? 1 : 0, *sep_warn = sw->sep_warn;
+  if (report && sw->audit_ever)
+    for (int k = 0; k < sw->n_local; ++k) report[k] = sw->flight[k];
+  return HDSM_OK;
+}
+int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !(sep_warn > 0) || (sw->n_local && !report)) return HDSM_ERR_BAD_ARG;
+  sw->audit_on = on != 0, sw->audit_ever = true, sw->sep_warn = sep_warn;
+  sw->flight.assign(report, report + sw->n_local);
+  return HDSM_OK;
+}
+// rounds flown on the device into the planner records (state_hist_, AC:240-245): rows [n_rounds][n_local][9], stamped as the
+// rounds hdsm_swarm_commit books. round_idx counts the rounds with a record: it advances here and in hdsm_swarm_commit only
+// (hdsm_swarm_import_state leaves it alone), so device rounds that were not recorded leave no gap in the stamps.
+int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || n_rounds < 0 || (n_rounds && sw->n_local && !rows)) return HDSM_ERR_BAD_ARG;
+  for (int r = 0; r < n_rounds; ++r) {
+    const double stamp = (double)(sw->round_idx + 1) * sw->prm.dt * sw->cfg.step_plan;
+    for (int k = 0; k < sw->n_local; ++k) hdsm_stats_add_state(sw->extra[k].stats, stamp, rows + ((size_t)r * sw->n_local + k) * 9, 9);
+    ++sw->round_idx;
+  }
+  return HDSM_OK;
 }
 
 // ---- hooks of the device-resident loop (swarm_kernels.hip): the plain agent states and the configuration of a shard ----

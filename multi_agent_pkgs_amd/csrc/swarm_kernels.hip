@@ -22,6 +22,7 @@
 
 #include "../../include/hdsm.h"
 #include "../../include/hdsm_swarm.h"
+#include "audit_device.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -49,6 +50,9 @@ extern "C" int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32
 extern "C" int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
 extern "C" int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
 extern "C" int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
+extern "C" int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report);
+extern "C" int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report);
+extern "C" int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows);
 
 namespace {
 
@@ -610,7 +614,35 @@ struct DSwarm {
   bool dmp = false;
   int dmp_rn = 0;
   uint32_t* d_dmp_rows = nullptr;
+  // the flight audit and the state history (audit_kernels.hip; both opt-in: nothing below is allocated or launched while they are off)
+  bool audit_on = false, audit_ever = false, audit_valid = false;
+  long long audit_rounds = 0;  // rounds audited by this dswarm (hdsm_dswarm_last_audit_round needs one)
+  double sep_warn = 1.0;
+  hdsm_audit::DeviceBufs abuf;
+  hdsm_flight_report* d_report = nullptr;
+  hipEvent_t audit_ev[2] = {nullptr, nullptr};
+  double* d_hist = nullptr;
+  int hist_cap = 0, hist_n = 0, hist_dropped = 0, hist_delivered = 0;
 };
+
+// the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports
+int audit_setup(DSwarm* d, const hdsm_flight_report* init) {
+  if (d->abuf.d_round == nullptr) {
+    if (hdsm_audit::device_alloc(&d->abuf, d->per * d->world, d->n_local, d->c.step_plan) != hipSuccess)
+      return fail(HDSM_ERR_DEVICE, "flight audit: allocation failed");
+  }
+  if (d->d_report == nullptr && (init != nullptr || d->audit_on)) {
+    std::vector<hdsm_flight_report> rep((size_t)d->n_local);
+    for (int k = 0; k < d->n_local; ++k) {
+      if (init) rep[k] = init[k];
+      else hdsm_audit::empty_report(&rep[k]);
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_report), (rep.size() + 1) * sizeof(hdsm_flight_report)));
+    if (!rep.empty()) HIP_TRY(hipMemcpy(d->d_report, rep.data(), rep.size() * sizeof(hdsm_flight_report), hipMemcpyHostToDevice));
+    d->audit_ever = true;
+  }
+  return HDSM_OK;
+}
 
 template <class T>
 hipError_t dalloc(T** p, size_t count) {
@@ -629,6 +661,11 @@ void free_all(DSwarm* d) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : d->path_ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : d->audit_ev)
+    if (e) (void)hipEventDestroy(e);
+  hdsm_audit::device_free(&d->abuf);
+  if (d->d_report) (void)hipFree(d->d_report);
+  if (d->d_hist) (void)hipFree(d->d_hist);
 }
 
 }  // namespace
@@ -650,8 +687,10 @@ int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on) {
       if (!e) HIP_TRY(hipEventCreate(&e));
     for (hipEvent_t& e : d->path_ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
+    for (hipEvent_t& e : d->audit_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
   }
-  d->phase_timing = on != 0, d->phase_valid = false, d->path_valid = false;
+  d->phase_timing = on != 0, d->phase_valid = false, d->path_valid = false, d->audit_valid = false;
   return HDSM_OK;
 }
 
@@ -843,6 +882,16 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
   }
   if (e == hipSuccess && hworld) e = hipMemcpy(d->d_world, hworld, (size_t)wdim[0] * wdim[1] * wdim[2], hipMemcpyHostToDevice);
   c.world = d->d_world;
+  if (e == hipSuccess && rc == HDSM_OK) {  // the audit's setting and record of the mirror (a flight taken over keeps its record)
+    int32_t on = 0, ever = 0;
+    rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d->sep_warn, nullptr);
+    if (rc == HDSM_OK && ever) {
+      std::vector<hdsm_flight_report> rep(n);
+      rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d->sep_warn, rep.data());
+      d->audit_on = on != 0;
+      if (rc == HDSM_OK) rc = audit_setup(d, rep.data());
+    }
+  }
   if (e != hipSuccess || rc) {
     free_all(d);
     delete d;
@@ -957,6 +1006,25 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
   }
   PHASE_MARK(7);
 #undef PHASE_MARK
+  // the flight audit and the history row, on this round's records of all agents (only when one of them is on)
+  d->audit_valid = false;
+  if (d->hist_cap > 0 && d->hist_n == d->hist_cap) ++d->hist_dropped;
+  const bool hist = d->hist_cap > 0 && d->hist_n < d->hist_cap;
+  if ((d->audit_on || hist) && n > 0) {
+    if (timing) HIP_TRY(hipEventRecord(d->audit_ev[0], st));
+    hdsm_audit::World wd{};
+    wd.world = d->c.has_world ? d->d_world : nullptr, wd.voxel_size = d->c.voxel_size;
+    for (int k = 0; k < 3; ++k) wd.wdim[k] = d->c.wdim[k], wd.worigin[k] = d->c.worigin[k];
+    HIP_TRY(hdsm_audit::launch(d->abuf, d->audit_on, d->d_plans, d->d_has, d->c.N, d->first, hdsm_audit::weights(d->prm.drone_radius, d->prm.drone_z_offset),
+                               wd, d->d_report, d->sep_warn * d->sep_warn, &d->d_agents[0].state_curr[0], sizeof(AgentS),
+                               hist ? d->d_hist + (size_t)d->hist_n * n * 9 : nullptr, st));
+    if (timing) {
+      HIP_TRY(hipEventRecord(d->audit_ev[1], st));
+      d->audit_valid = true;
+    }
+    if (d->audit_on) ++d->audit_rounds;
+  }
+  if (hist) ++d->hist_n;
   if (timing) d->phase_valid = true;
   ++d->rounds;
   return HDSM_OK;
@@ -987,6 +1055,11 @@ int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* 
     int rc = e == hipSuccess ? hdsm_swarm_import_state(swarm, tmp, d->n_local) : HDSM_ERR_DEVICE;
     std::free(tmp);
     if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d->path_period, d->path_round, d->due.data(), d->goals.data());
+    if (rc == HDSM_OK && d->audit_ever) {
+      std::vector<hdsm_flight_report> rep(n);
+      if (hipMemcpy(rep.data(), d->d_report, n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
+      else rc = hdsm_swarm_import_audit(swarm, d->audit_on ? 1 : 0, d->sep_warn, rep.data());
+    }
     if (rc) return fail(rc, "state download failed");
   }
   if (plans_all) {
@@ -997,6 +1070,99 @@ int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* 
   if (has_plan) HIP_TRY(hipMemcpy(has_plan, d->d_has, G, hipMemcpyDeviceToHost));
   if (status && n) HIP_TRY(hipMemcpy(status, d->d_status, n * 4, hipMemcpyDeviceToHost));
   if (failed_total) HIP_TRY(hipMemcpy(failed_total, d->d_fails, 4, hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+
+// ---- the flight audit and the state history of the device loop (audit_kernels.hip) ----
+int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (!(sep_warn > 0)) return fail(HDSM_ERR_BAD_ARG, "sep_warn must be positive");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  d->audit_on = on != 0, d->sep_warn = sep_warn;
+  if (on) {
+    const int rc = audit_setup(d, nullptr);
+    if (rc) return rc;
+    if (d->phase_timing)
+      for (hipEvent_t& e : d->audit_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+  }
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_flight_report(void* dswarm, hdsm_flight_report* report) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (d->n_local && !report)) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->audit_ever) return fail(HDSM_ERR_BAD_ARG, "the flight audit was never switched on");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (d->n_local) HIP_TRY(hipMemcpy(report, d->d_report, (size_t)d->n_local * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_last_audit_round(void* dswarm, hdsm_audit_round* out) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (d->n_local && !out)) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->audit_on || d->audit_rounds == 0) return fail(HDSM_ERR_BAD_ARG, "no round has been audited (hdsm_dswarm_set_audit)");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (d->n_local) HIP_TRY(hipMemcpy(out, d->abuf.d_round, (size_t)d->n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+// The audit's launches of the last timed round (pack, sweep, track; or the history write alone), in milliseconds; 0 when that round
+// launched none or no round was timed. Kept out of hdsm_dswarm_last_phase_ms: the audit starts after its [6].
+int hdsm_dswarm_last_audit_ms(void* dswarm, float* ms) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  *ms = 0.0f;
+  if (!d->audit_valid) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipEventSynchronize(d->audit_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, d->audit_ev[0], d->audit_ev[1]));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || capacity_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "bad argument");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (d->d_hist) (void)hipFree(d->d_hist);
+  d->d_hist = nullptr, d->hist_cap = 0, d->hist_n = d->hist_dropped = d->hist_delivered = 0;
+  if (capacity_rounds > 0) {
+    const int rc = audit_setup(d, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_hist), ((size_t)capacity_rounds * d->n_local * 9 + 1) * sizeof(double)));
+    d->hist_cap = capacity_rounds;
+    if (d->phase_timing)
+      for (hipEvent_t& e : d->audit_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+  }
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_t max_rounds, int32_t* n_rounds, int32_t* dropped) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || max_rounds < 0 || (hist == nullptr && max_rounds > 0)) return fail(HDSM_ERR_BAD_ARG, "bad argument");
+  if (d->hist_cap == 0) return fail(HDSM_ERR_BAD_ARG, "the history is off (hdsm_dswarm_set_history)");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t row = (size_t)d->n_local * 9;
+  const int n_copy = d->hist_n < max_rounds ? d->hist_n : max_rounds;
+  if (n_copy > 0 && row) HIP_TRY(hipMemcpy(hist, d->d_hist, (size_t)n_copy * row * sizeof(double), hipMemcpyDeviceToHost));
+  if (swarm && d->hist_n > d->hist_delivered) {  // every recorded round reaches the mirror's planner records once
+    const int m = d->hist_n - d->hist_delivered;
+    std::vector<double> rows((size_t)m * row);
+    if (row) HIP_TRY(hipMemcpy(rows.data(), d->d_hist + (size_t)d->hist_delivered * row, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const int rc = hdsm_swarm_append_history(swarm, m, rows.data());
+    if (rc) return fail(rc, "hdsm_swarm_append_history");
+    d->hist_delivered = d->hist_n;
+  }
+  if (n_rounds) *n_rounds = d->hist_n;
+  if (dropped) *dropped = d->hist_dropped;
   return HDSM_OK;
 }
 

@@ -29,6 +29,9 @@ EXPORTS = ("hdsm_version", "hdsm_last_error", "hdsm_default_params", "hdsm_creat
            "hdsm_dswarm_set_phase_timing", "hdsm_dswarm_last_phase_ms", "hdsm_dswarm_cache_stats",
            "hdsm_swarm_set_goals", "hdsm_swarm_set_path_period", "hdsm_swarm_replan_paths", "hdsm_swarm_path_errors", "hdsm_local_path_batch",
            "hdsm_local_path_host", "hdsm_swarm_set_path_clearance", "hdsm_local_path_dmp_batch", "hdsm_local_path_dmp_host", "hdsm_dswarm_set_goals", "hdsm_dswarm_path_stats", "hdsm_dswarm_last_path_ms",
+           "hdsm_flight_audit_host", "hdsm_flight_audit_batch", "hdsm_swarm_set_audit", "hdsm_swarm_get_audit", "hdsm_swarm_audit", "hdsm_swarm_flight_report",
+           "hdsm_dswarm_set_audit", "hdsm_dswarm_flight_report", "hdsm_dswarm_last_audit_round", "hdsm_dswarm_last_audit_ms",
+           "hdsm_dswarm_set_history", "hdsm_dswarm_download_history",
            "hdsm_stats_create", "hdsm_stats_destroy", "hdsm_stats_add", "hdsm_stats_add_state", "hdsm_stats_add_latency",
            "hdsm_stats_shutdown", "hdsm_map_preprocess", "hdsm_map_preprocess_device", "hdsm_map_last_error")
 
@@ -380,3 +383,53 @@ def local_path_dmp_batch(world, ldim, off, ground_k, origin, start, goal, search
 def local_path_dmp_host(world, ldim, off, ground_k, origin, start, goal, search_rad=1.8, res=0.3, pmax=PATH_PTS):
     """hdsm_local_path_dmp_host: the same batch on the CPU (bit for bit what local_path_dmp_batch returns)."""
     return _local_path("hdsm_local_path_dmp_host", (), world, ldim, off, ground_k, origin, start, goal, res, pmax, search_rad=float(search_rad))
+
+
+# ---- the flight audit (include/hdsm_swarm.h, csrc/audit_core.h) ----
+AUDIT_ROUND = np.dtype([("sep2", "<f8"), ("partner", "<i4"), ("substep", "<i4"), ("occupied", "<i4"), ("unknown", "<i4"),
+                        ("crossed", "<i4"), ("pot", "<i4"), ("dist", "<f8"), ("speed", "<f8")])          # hdsm_audit_round
+FLIGHT_REPORT = np.dtype([("rounds", "<i8"), ("positions", "<i8"), ("sep2_min", "<f8"), ("sep_partner", "<i4"), ("sep_substep", "<i4"),
+                          ("sep_round", "<i8"), ("close_rounds", "<i8"), ("occupied", "<i8"), ("unknown", "<i8"), ("crossed", "<i8"),
+                          ("pot_sum", "<i8"), ("dist", "<f8"), ("speed_sum", "<f8"), ("speed_max", "<f8")])  # hdsm_flight_report
+assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104
+
+
+def _flight_audit(fn, lead, plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world, worigin, voxel_size):
+    L = load()
+    plans_all, has_plan = _f64(plans_all), _u8(has_plan)
+    n_rob, n_hor = plans_all.shape[0], plans_all.shape[1] - 1
+    assert plans_all.ndim == 3 and plans_all.shape[2] == 9 and has_plan.shape == (n_rob,)
+    n_local = n_rob - first if n_local is None else int(n_local)
+    if world is None:
+        wp, wdim, worg = None, None, None
+    else:
+        world = np.ascontiguousarray(world, dtype=np.int8)
+        wdim = np.asarray(world.shape[::-1], dtype=np.int32)
+        worg = _f64(np.asarray(worigin, dtype=np.float64).reshape(3))
+        wp = world.ctypes.data_as(C.POINTER(C.c_int8))
+    out = np.zeros(max(n_local, 0), AUDIT_ROUND)
+    rc = getattr(L, fn)(*lead, C.c_int32(n_rob), _p(plans_all, C.c_double), _p(has_plan, C.c_uint8), C.c_int32(n_hor), C.c_int32(int(step_plan)),
+                        C.c_int32(int(first)), C.c_int32(n_local), C.c_double(float(drone_radius)), C.c_double(float(drone_z_offset)), wp,
+                        _p(wdim, C.c_int32) if wdim is not None else None, _p(worg, C.c_double) if worg is not None else None,
+                        C.c_double(float(voxel_size)), C.c_void_p(out.ctypes.data))
+    if rc:
+        raise HdsmError(rc, fn)
+    return out
+
+
+def flight_audit_host(plans_all, has_plan, step_plan=1, first=0, n_local=None, drone_radius=0.25, drone_z_offset=0.25, world=None,
+                      worigin=(0.0, 0.0, 0.0), voxel_size=0.3):
+    """hdsm_flight_audit_host: what the agents [first, first + n_local) flew in one round of published records plans_all
+    [n_rob][n_hor+1][9] (has_plan [n_rob]): an AUDIT_ROUND record per subject — sep2 (the continuous minimum of the separation
+    ratio squared over the step_plan sub-steps and all partners), partner, substep, and the own-track figures on `world`
+    (int8 [wz][wy][wx] at voxel_size with voxel (0,0,0) at worigin; None = free space)."""
+    return _flight_audit("hdsm_flight_audit_host", (), plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world,
+                         worigin, voxel_size)
+
+
+def flight_audit_batch(plans_all, has_plan, step_plan=1, first=0, n_local=None, drone_radius=0.25, drone_z_offset=0.25, world=None,
+                       worigin=(0.0, 0.0, 0.0), voxel_size=0.3, device=0):
+    """hdsm_flight_audit_batch: the same audit on the device (k_audit_pack, k_audit, k_audit_track; host arrays in and out), bit
+    for bit what flight_audit_host returns."""
+    return _flight_audit("hdsm_flight_audit_batch", (C.c_int32(device),), plans_all, has_plan, step_plan, first, n_local, drone_radius,
+                         drone_z_offset, world, worigin, voxel_size)

@@ -242,6 +242,42 @@ class SwarmShard:
             raise _lib.HdsmError(rc, "hdsm_swarm_commit")
         return plans_local, has_local
 
+    def set_audit(self, on=True, sep_warn=1.0):
+        """hdsm_swarm_set_audit: the flight audit of the host mirror (csrc/audit_core.h). The flight record starts when it is first
+        switched on; a round counts as close when its separation ratio is below sep_warn. SwarmLoop.step audits every round while
+        it is on, and a DeviceSwarm made from this shard takes the setting and the record over."""
+        rc = self.lib.hdsm_swarm_set_audit(self.h, C.c_int32(1 if on else 0), C.c_double(float(sep_warn)))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_set_audit")
+
+    @property
+    def audit_on(self):
+        """hdsm_swarm_get_audit: whether the mirror audits — asked of the library, so that a setting brought back from a device
+        loop (DeviceSwarm.download) counts like one made here."""
+        on = C.c_int32(0)
+        rc = self.lib.hdsm_swarm_get_audit(self.h, C.byref(on), None)
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_get_audit")
+        return bool(on.value)
+
+    def audit(self, plans_all, has_plan):
+        """hdsm_swarm_audit: one round into the flight record — the records all agents published this round (after the gather)."""
+        plans_all = np.ascontiguousarray(plans_all, dtype=np.float64)
+        has_plan = np.ascontiguousarray(has_plan, dtype=np.uint8)
+        if plans_all.shape != (self.n_rob, self.prm.n_hor + 1, 9) or has_plan.shape != (self.n_rob,):
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "audit: plans_all [n_rob][n_hor+1][9] and has_plan [n_rob] expected")
+        rc = self.lib.hdsm_swarm_audit(self.h, _p(plans_all, C.c_double), _p(has_plan, C.c_uint8))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_audit")
+
+    def flight_report(self):
+        """hdsm_swarm_flight_report: the flight record per local agent (lib.FLIGHT_REPORT); an error if the audit was never on."""
+        rep = np.zeros(self.n_local, _lib.FLIGHT_REPORT)
+        rc = self.lib.hdsm_swarm_flight_report(self.h, C.c_void_p(rep.ctypes.data))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_flight_report")
+        return rep
+
     def state(self):
         pos = np.zeros((self.n_local, 3))
         dist = np.zeros(self.n_local)
@@ -312,6 +348,8 @@ class SwarmLoop:
             self.plans_all = full
         else:
             self.plans_all, self.has_plan = plans_local, has_local
+        if self.shard.audit_on:
+            self.shard.audit(self.plans_all, self.has_plan)
         self.round_idx += 1
         return out
 
@@ -448,6 +486,56 @@ class DeviceSwarm:
             raise self._err(rc)
         return float(ms.value)
 
+    def set_audit(self, on=True, sep_warn=1.0):
+        """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
+        rc = self.lib.hdsm_dswarm_set_audit(self.h, C.c_int32(1 if on else 0), C.c_double(float(sep_warn)))
+        if rc:
+            raise self._err(rc)
+
+    def flight_report(self):
+        """hdsm_dswarm_flight_report: the flight record per local agent (lib.FLIGHT_REPORT); an error if the audit was never on."""
+        rep = np.zeros(self.shard.n_local, _lib.FLIGHT_REPORT)
+        rc = self.lib.hdsm_dswarm_flight_report(self.h, C.c_void_p(rep.ctypes.data))
+        if rc:
+            raise self._err(rc)
+        return rep
+
+    def last_audit_round(self):
+        """hdsm_dswarm_last_audit_round: what the last round's audit found per local agent (lib.AUDIT_ROUND)."""
+        out = np.zeros(self.shard.n_local, _lib.AUDIT_ROUND)
+        rc = self.lib.hdsm_dswarm_last_audit_round(self.h, C.c_void_p(out.ctypes.data))
+        if rc:
+            raise self._err(rc)
+        return out
+
+    def last_audit_ms(self):
+        """hdsm_dswarm_last_audit_ms: milliseconds of the audit's launches in the last timed round (0.0 if it launched none)."""
+        ms = C.c_float(0.0)
+        rc = self.lib.hdsm_dswarm_last_audit_ms(self.h, C.byref(ms))
+        if rc:
+            raise self._err(rc)
+        return float(ms.value)
+
+    def set_history(self, capacity_rounds):
+        """hdsm_dswarm_set_history: record state_curr of every local agent after each round's commit, for capacity_rounds rounds
+        (then recording stops and the lost rounds are counted); 0 switches it off. Starts an empty history."""
+        rc = self.lib.hdsm_dswarm_set_history(self.h, C.c_int32(int(capacity_rounds)))
+        if rc:
+            raise self._err(rc)
+        self._hist_cap = int(capacity_rounds)
+
+    def history(self, mirror=True):
+        """hdsm_dswarm_download_history: (hist [n_rounds][n_local][9], rounds dropped). mirror=True also appends every round not yet
+        delivered to the planner records of the host mirror (state_hist_<id>.csv of hdsm_swarm_shutdown), once."""
+        cap = getattr(self, "_hist_cap", 0)
+        hist = np.zeros((max(cap, 1), self.shard.n_local, 9))
+        n, dropped = C.c_int32(0), C.c_int32(0)
+        rc = self.lib.hdsm_dswarm_download_history(self.h, self.shard.h if mirror else None, _p(hist, C.c_double), C.c_int32(cap), C.byref(n),
+                                                   C.byref(dropped))
+        if rc:
+            raise self._err(rc)
+        return hist[: n.value].copy(), dropped.value
+
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
             self.lib.hdsm_dswarm_destroy(self.h)
@@ -458,3 +546,25 @@ class DeviceSwarm:
             self.close()
         except Exception:
             pass
+
+
+def flight_summary(reports, first_id=0):
+    """Folds per-agent flight records (lib.FLIGHT_REPORT, of one shard or concatenated in id order starting at first_id) into a swarm
+    summary: sigma_min (the smallest separation ratio flown, None without a pair) with both ids, the sub-step and the agent's audited
+    round; close_rounds (agent-rounds below sep_warn: a close pair counts once for each of its agents); the totals; the mean
+    potential under the positions flown, pot_sum / positions; the mean and the largest speed."""
+    rep = np.asarray(reports)
+    out = dict(agents=int(rep.size), rounds=int(rep["rounds"].max()) if rep.size else 0, positions=int(rep["positions"].sum()),
+               sigma_min=None, sigma_min_agent=-1, sigma_min_partner=-1, sigma_min_substep=0, sigma_min_round=-1,
+               close_rounds=int(rep["close_rounds"].sum()), occupied=int(rep["occupied"].sum()), unknown=int(rep["unknown"].sum()),
+               crossed=int(rep["crossed"].sum()), pot_sum=int(rep["pot_sum"].sum()), dist=float(rep["dist"].sum()))
+    out["mean_potential"] = out["pot_sum"] / out["positions"] if out["positions"] else 0.0
+    flown = rep["rounds"] > 0
+    out["mean_speed"] = float((rep["speed_sum"][flown] / rep["rounds"][flown]).mean()) if flown.any() else 0.0
+    out["max_speed"] = float(rep["speed_max"].max()) if rep.size else 0.0
+    paired = np.nonzero(rep["sep_partner"] >= 0)[0]
+    if paired.size:
+        k = paired[np.lexsort((paired, rep["sep2_min"][paired]))[0]]     # smallest sep2_min, then the lower id
+        out.update(sigma_min=float(np.sqrt(rep["sep2_min"][k])), sigma_min_agent=int(first_id + k), sigma_min_partner=int(rep["sep_partner"][k]),
+                   sigma_min_substep=int(rep["sep_substep"][k]), sigma_min_round=int(rep["sep_round"][k]))
+    return out
