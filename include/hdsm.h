@@ -270,6 +270,26 @@ int hdsm_map_preprocess(int32_t device, const hdsm_map_config* cfg, int32_t n_gr
 /* Device pointers on `hip_stream`; scratch = 2 * n_grids * nx*ny*nz bytes of device memory.                  */
 int hdsm_map_preprocess_device(int32_t device, const hdsm_map_config* cfg, int32_t n_grids, const int32_t dim[3],
                                const int8_t* grids_in, int8_t* grids_out, void* scratch, void* hip_stream);
+/* The region form (ABI 1.7): the raw grid changed only inside the box lo[3] .. lo + bdim[3] (voxels, x y z). The three stages are
+ * local with Chebyshev radii rn0 = rn1 = ceil(inflation_dist / voxel_size), rn2 = ceil(potential_dist / voxel_size), so the
+ * processed grid can change only inside W = box (+) R, R = rn0 + rn1 + rn2, clipped to the grid, and W is exact once the stages
+ * have run on the working box = box (+) 2R, clipped. The same nine passes run on the working box alone and only W is written.
+ *   hdsm_map_region_extent         host arithmetic: W (write_lo, write_dim) and the working box (work_lo, work_dim); any output may
+ *                                  be NULL. A working box of fewer than four voxels is widened to four.
+ *   hdsm_map_region_scratch_bytes  device memory hdsm_map_preprocess_region_device needs for this box (0 on a bad argument); the
+ *                                  whole grid as the box gives the bound for every box: 4 * nx*ny*nz.
+ *   hdsm_map_preprocess_region_device  device pointers, asynchronous on hip_stream. raw_full: the raw grid AFTER the edit; out_full:
+ *                                  the processed grid of before the edit on entry, of after it on return (== hdsm_map_preprocess
+ *                                  of the edited raw grid, bit for bit).
+ *   hdsm_map_preprocess_region     host pointers: copies both grids in, runs, copies out_full back, synchronises (tests, tools).
+ * A box that is not inside the grid: HDSM_ERR_BAD_ARG. An empty box (some bdim 0): nothing happens. Errors: hdsm_map_last_error. */
+int hdsm_map_region_extent(const hdsm_map_config* cfg, const int32_t dim[3], const int32_t lo[3], const int32_t bdim[3], int32_t write_lo[3],
+                           int32_t write_dim[3], int32_t work_lo[3], int32_t work_dim[3]);
+size_t hdsm_map_region_scratch_bytes(const hdsm_map_config* cfg, const int32_t dim[3], const int32_t lo[3], const int32_t bdim[3]);
+int hdsm_map_preprocess_region_device(int32_t device, const hdsm_map_config* cfg, const int32_t dim[3], const int8_t* raw_full, int8_t* out_full,
+                                      const int32_t lo[3], const int32_t bdim[3], void* scratch, void* hip_stream);
+int hdsm_map_preprocess_region(int32_t device, const hdsm_map_config* cfg, const int32_t dim[3], const int8_t* raw_full, int8_t* out_full,
+                               const int32_t lo[3], const int32_t bdim[3]);
 const char* hdsm_map_last_error(void);
 
 /* Stand-alone plane generator = Agent::GenerateTimeAwareSafeCorridor's inner maths (AC:1100-1205) for one
@@ -337,7 +357,10 @@ const char* hdsm_last_error(void);
  * hdsm_last_kernel_ms; 1.3: + hdsm_host_register / hdsm_host_unregister, hdsm_swarm_yaw / hdsm_swarm_view
  * (hdsm_swarm.h); 1.4: + the path step, 1.5: + its clearance mode, 1.6: + the flight audit and the state history
  * (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report /
- * _last_audit_round / _last_audit_ms / _set_history / _download_history; all in hdsm_swarm.h); nothing removed or changed.   */
+ * _last_audit_round / _last_audit_ms / _set_history / _download_history; all in hdsm_swarm.h); 1.7: + map updates in flight
+ * (hdsm_map_region_extent / _region_scratch_bytes / hdsm_map_preprocess_region / _region_device here; hdsm_swarm_update_world,
+ * hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats in
+ * hdsm_swarm.h); nothing removed or changed.   */
 int32_t hdsm_version(void);
 
 #ifdef __cplusplus

@@ -84,6 +84,14 @@ int hdsm_swarm_set_reference(void* swarm, const double* ref_full, const double* 
  * the same polyhedra. NULL occupancy = back to free space. The global path stays the straight segment
  * start -> goal (f3, JPS + DMP, is not built): the caller is responsible for worlds in which that is collision-free. */
 int hdsm_swarm_set_world(void* swarm, const int8_t* occupancy, const int32_t dim[3], const double origin[3]);
+/* A map update (ABI 1.7; VoxelGridResponseCallback / MappingUtilVoxelGridCallback, AC:2310-2378, for the shared world): the box
+ * lo[3] .. lo + bdim[3] (world voxels, x y z) of the PROCESSED world given to hdsm_swarm_set_world takes values
+ * [bdim[2]][bdim[1]][bdim[0]] as they are. From the next hdsm_swarm_prepare / _prepare_corridor / path step on everything reads the new
+ * voxels, exactly as after hdsm_swarm_set_world of the edited grid. Polyhedra an agent keeps (AC:1253-1282) are not checked against
+ * the new voxels — the reference keeps them too — and global paths adapt only through the path step (its period, a goal change,
+ * hdsm_swarm_replan_paths): an edit plans nothing by itself. HDSM_ERR_BAD_ARG without a world or for a box not inside it; an empty
+ * box is a no-op. */
+int hdsm_swarm_update_world(void* swarm, const int8_t* values, const int32_t lo[3], const int32_t bdim[3]);
 
 /* Next row f2, first piece — the convex voxel decomposition GenerateSafeCorridor calls for every seed
  * (convex_decomp_lib::GetPolyOcta3D, convex_decomp_util/src/convex_decomp.cpp:5-376): a cuboid of free voxels grown
@@ -219,8 +227,9 @@ int hdsm_swarm_prepare_corridor(void* swarm);
  * and copies out what the caller asks for (any pointer may be NULL): the agent states back into the host mirror `swarm`
  * (so that every hdsm_swarm_* diagnostic works on them), the all-gathered plans [world_size * per][N+1][9] and flags, the
  * statuses of the last round, the number of instances without solution so far.
- * The world and the configuration are those of the host mirror at hdsm_dswarm_create and stay fixed for the dswarm's life; the
- * global paths too, unless the path step is on (hdsm_swarm_set_path_period, hdsm_dswarm_set_goals: see below) (the
+ * The world and the configuration are those of the host mirror at hdsm_dswarm_create; the configuration stays fixed for the dswarm's
+ * life, the world changes only through hdsm_dswarm_update_world* / _set_raw_world (ABI 1.7, below); the
+ * global paths are fixed too, unless the path step is on (hdsm_swarm_set_path_period, hdsm_dswarm_set_goals: see below) (the
  * device corridor keeps each agent's last polyhedra and forms the rows of one that is asked for again from them instead of
  * growing it again — same rows, bit for bit; environment HDSM_POLY_CACHE=0 switches that off, for A/B runs). */
 int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_size, void** dswarm);
@@ -251,6 +260,44 @@ int hdsm_dswarm_cache_stats(void* dswarm, int64_t out[4]);
 int hdsm_dswarm_set_goals(void* dswarm, const double* goals);
 int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]);
 int hdsm_dswarm_last_path_ms(void* dswarm, float* ms);
+
+/* ---- map updates in flight (ABI 1.7): the device world edited box by box between two rounds ------------------------------------------
+ * Opt-in: a flight that calls none of these is launch for launch what it was. Boxes are lo[3] .. lo + bdim[3] in world voxels (x y z),
+ * values [bdim[2]][bdim[1]][bdim[0]]; a box not inside the world, a dswarm without a world: HDSM_ERR_BAD_ARG; an empty box: a no-op.
+ *   hdsm_dswarm_update_world      PROCESSED values (host pointer; synchronises, like hdsm_dswarm_set_goals) into the device world.
+ *                                 The resident raw grid, if any, is not touched: the two then disagree inside the box, and a later
+ *                                 raw update whose W meets it writes W from the raw grid again, over those values. Use one kind of
+ *                                 update per dswarm, or repeat the processed edit after raw ones.
+ *   hdsm_dswarm_set_raw_world     uploads a RAW grid of the world's dimensions (-1 unknown, 0 free, 100 occupied) and keeps it on the
+ *                                 device with the scratch of the region pre-processing (4 bytes per world voxel), runs
+ *                                 hdsm_map_preprocess_device on it into the device world and drops every cache entry. Synchronises,
+ *                                 and reads the whole grid once on the host to check its values (a set-up call, not one for between
+ *                                 two rounds). Bad arguments are refused before anything is touched; after HDSM_ERR_DEVICE the
+ *                                 device world is undefined, no raw world is resident and the cache is empty.
+ *   hdsm_dswarm_update_world_raw  RAW values (host pointer; synchronises) into the resident raw grid, then
+ *                                 hdsm_map_preprocess_region_device into the device world: the world is then hdsm_map_preprocess
+ *                                 of the edited raw grid, bit for bit. An error before hdsm_dswarm_set_raw_world.
+ *   hdsm_dswarm_update_world_raw_device  the same with a device pointer, asynchronous on hip_stream. It MUST be the stream the rounds
+ *                                 run on: the edit is then ordered between two rounds (the values are read when the stream gets
+ *                                 there: keep them alive and unchanged until then). On another stream the edit races with a round.
+ * The corridor's polyhedron cache: every update drops the entries whose decomposition could have looked at a written voxel (the
+ * seed's voxel +- wave_map_radius(n_it_decomp) + 1 meets the written box — the box itself, or W of hdsm_map_region_extent for a raw
+ * update; k_cache_invalidate, one lane per agent and entry); the others stay, and the slot of a dropped entry is the first to be used again. Polyhedra an agent KEEPS (AC:1253-1282) are not checked
+ * against the new voxels, as in the reference and in the host mirror. Global paths adapt only through the path step (its period,
+ * hdsm_dswarm_set_goals), as in the reference: an edit plans nothing by itself.
+ * Several ranks: every rank holds its own copy of the world; the caller applies the same edit on every rank between the same two
+ * rounds — nothing here communicates.
+ *   hdsm_dswarm_download_world    synchronises and copies the processed device world out ([wdim[2]][wdim[1]][wdim[0]]), e.g. into
+ *                                 hdsm_swarm_set_world of the mirror before a takeover.
+ *   hdsm_dswarm_world_stats       out[0] updates applied, out[1] voxels written by them (the box, or W, summed), out[2] cache entries
+ *                                 dropped (hdsm_dswarm_set_raw_world's included), out[3] 1 if a raw world is resident. Synchronises
+ *                                 the device once an update has been applied (out[2] is counted there). */
+int hdsm_dswarm_update_world(void* dswarm, const int8_t* values, const int32_t lo[3], const int32_t bdim[3]);
+int hdsm_dswarm_set_raw_world(void* dswarm, const hdsm_map_config* map_cfg, const int8_t* raw_full);
+int hdsm_dswarm_update_world_raw(void* dswarm, const int8_t* raw_values, const int32_t lo[3], const int32_t bdim[3]);
+int hdsm_dswarm_update_world_raw_device(void* dswarm, const int8_t* d_raw_values, const int32_t lo[3], const int32_t bdim[3], void* hip_stream);
+int hdsm_dswarm_download_world(void* dswarm, int8_t* world);
+int hdsm_dswarm_world_stats(void* dswarm, int64_t out[4]);
 
 /* ---- the flight audit (ABI 1.6): separation, obstacle contact and state history of what was flown ------------------------------
  * Opt-in; with the audit and the history off nothing is launched, allocated or written. One definition (csrc/audit_core.h) shared by

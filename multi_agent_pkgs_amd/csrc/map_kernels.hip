@@ -14,6 +14,7 @@
 // Byte work, HBM/L2-bound: thread <-> voxel, x fastest, so every tap of every pass is a coalesced byte stream.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -197,11 +198,85 @@ __global__ __launch_bounds__(256) void k_pass(Dims d, int rn, MapTables tb, cons
   }
 }
 
+// ---- the region form: the raw grid changed inside a box D only ----------------------------------------------------------------
+// The three stages are local with Chebyshev radii rn0, rn1, rn2, so the processed grid can change only inside W = D (+) R,
+// R = rn0 + rn1 + rn2, and W is exact once the stages have run on the working box B = D (+) 2R (each stage's result is valid on
+// its input region shrunk by its radius). Both boxes are clipped to the grid: where a face of B is a face of the grid, "no tap
+// beyond it" is the grid's own rule; where it is not, it lies R voxels or more outside W and what the passes make of the missing
+// taps never reaches a voxel that is written. So B is gathered into a dense field of its own and the SAME nine passes (k_pass, the
+// packed quads included) run on it as on a small grid. The one rule that is about the world's borders and not the field's — a
+// voxel seeds SetUncertainToUnknown only rn0 voxels or more inside the GRID — is decided here, in global coordinates, while
+// gathering: k_region_gather writes the seeds as a byte field (0 seed, 255 none) and the first pass reads it as any distance field.
+struct Region {
+  int nx, ny, nz;     // the grid
+  int bx, by, bz;     // B: origin in the grid
+  int bnx, bny, bnz;  //    extents
+  int wx, wy, wz;     // W: origin in the grid
+  int wnx, wny, wnz;  //    extents
+};
+
+// thread <-> up to four voxels of one row of the box (x fastest): the rows of the grid are read and written as contiguous bytes
+__global__ __launch_bounds__(256) void k_region_gather(Region r, int rn0, const int8_t* __restrict__ raw, int8_t* __restrict__ box,
+                                                       uint8_t* __restrict__ seeds) {
+  const int qpr = (r.bnx + VPT - 1) / VPT, rows = r.bny * r.bnz;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < qpr * rows; q += gridDim.x * blockDim.x) {
+    const int row = q / qpr, x0 = (q - row * qpr) * VPT, z = row / r.bny, y = row - z * r.bny;
+    const int gy = y + r.by, gz = z + r.bz;
+    const int n = r.bnx - x0 < VPT ? r.bnx - x0 : VPT;
+    const bool inner_row = gy >= rn0 && gy < r.ny - rn0 && gz >= rn0 && gz < r.nz - rn0;
+    const int8_t* in = raw + ((size_t)gz * r.ny + gy) * r.nx + (r.bx + x0);
+    const size_t o = (size_t)row * r.bnx + x0;
+    uint32_t v4 = 0;
+    if (n == VPT) v4 = load4(in);
+    else
+      for (int k = 0; k < n; ++k) v4 |= (uint32_t)(uint8_t)in[k] << (8 * k);
+    uint32_t s4 = inner_row ? far_unless(v4, 0xffffffffu) : 0xffffffffu;
+#pragma unroll
+    for (int k = 0; k < VPT; ++k) {
+      const int gx = r.bx + x0 + k;
+      if (gx < rn0 || gx >= r.nx - rn0) s4 |= 0xffu << (8 * k);
+    }
+    if (n == VPT) store4(box + o, v4), store4(seeds + o, s4);
+    else
+      for (int k = 0; k < n; ++k) box[o + k] = (int8_t)byte_of(v4, k), seeds[o + k] = (uint8_t)byte_of(s4, k);
+  }
+}
+
+// ... and the voxels of W leave the box for the processed grid: nothing outside W is written
+__global__ __launch_bounds__(256) void k_region_scatter(Region r, const int8_t* __restrict__ box, int8_t* __restrict__ out) {
+  const int qpr = (r.wnx + VPT - 1) / VPT, rows = r.wny * r.wnz;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < qpr * rows; q += gridDim.x * blockDim.x) {
+    const int row = q / qpr, x0 = (q - row * qpr) * VPT, z = row / r.wny, y = row - z * r.wny;
+    const int gy = y + r.wy, gz = z + r.wz, gx = r.wx + x0;
+    const int n = r.wnx - x0 < VPT ? r.wnx - x0 : VPT;
+    const int8_t* in = box + ((size_t)(gz - r.bz) * r.bny + (gy - r.by)) * r.bnx + (gx - r.bx);
+    int8_t* o = out + ((size_t)gz * r.ny + gy) * r.nx + gx;
+    if (n == VPT) store4(o, load4(in));
+    else
+      for (int k = 0; k < n; ++k) o[k] = in[k];
+  }
+}
+
 thread_local std::string g_map_err;
 
 // CreateMask (VG:192-226) folded into tables indexed by squared length; fails if two offsets of equal squared length
 // disagree (they do not for any setting tried; the check keeps the equivalence honest).
+int build_tables_uncached(const hdsm_map_config& c, MapTables* tb);
+// (an edit in flight asks for the tables of the same configuration every call: the last ones built are kept per thread)
 int build_tables(const hdsm_map_config& c, MapTables* tb) {
+  thread_local bool have = false;
+  thread_local hdsm_map_config last_cfg;
+  thread_local MapTables last_tb;
+  if (have && last_cfg.voxel_size == c.voxel_size && last_cfg.inflation_dist == c.inflation_dist && last_cfg.potential_dist == c.potential_dist &&
+      last_cfg.potential_pow == c.potential_pow) {
+    *tb = last_tb;
+    return HDSM_OK;
+  }
+  const int rc = build_tables_uncached(c, tb);
+  if (rc == HDSM_OK) last_cfg = c, last_tb = *tb, have = true;
+  return rc;
+}
+int build_tables_uncached(const hdsm_map_config& c, MapTables* tb) {
   std::memset(tb, 0, sizeof *tb);
   const double res = c.voxel_size;
   tb->rn0 = (int)std::ceil(c.inflation_dist / res);
@@ -317,6 +392,100 @@ bool bad_args(const hdsm_map_config* cfg, int32_t n_grids, const int32_t* dim, c
          cfg->inflation_dist < 0 || cfg->potential_dist < 0 || cfg->potential_pow < 0;
 }
 
+// W and B of an edit box (lo, bdim) that lies inside the grid; an empty box gives empty W and B. A working box of fewer than four
+// voxels (R = 0 and a tiny edit) is widened to four — the passes fetch quads — which costs nothing in exactness: a wider B is
+// still a B.
+void region_boxes(const MapTables& tb, const int32_t dim[3], const int32_t lo[3], const int32_t bdim[3], Region* r) {
+  const int R = tb.rn0 + tb.rn1 + tb.rn2;
+  int wl[3], wh[3], bl[3], bh[3];
+  for (int ax = 0; ax < 3; ++ax) {
+    if (bdim[ax] == 0) {
+      *r = Region{dim[0], dim[1], dim[2], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      return;
+    }
+    wl[ax] = std::max(lo[ax] - R, 0), wh[ax] = std::min(lo[ax] + bdim[ax] + R, dim[ax]);
+    bl[ax] = std::max(lo[ax] - 2 * R, 0), bh[ax] = std::min(lo[ax] + bdim[ax] + 2 * R, dim[ax]);
+  }
+  auto vox = [&]() { return (int64_t)(bh[0] - bl[0]) * (bh[1] - bl[1]) * (bh[2] - bl[2]); };
+  for (bool grew = true; vox() < VPT && grew;) {
+    grew = false;
+    for (int ax = 0; ax < 3 && vox() < VPT; ++ax) {
+      if (bh[ax] < dim[ax]) ++bh[ax], grew = true;
+      else if (bl[ax] > 0) --bl[ax], grew = true;
+    }
+  }
+  *r = Region{dim[0], dim[1], dim[2], bl[0], bl[1], bl[2], bh[0] - bl[0], bh[1] - bl[1], bh[2] - bl[2],
+              wl[0], wl[1], wl[2], wh[0] - wl[0], wh[1] - wl[1], wh[2] - wl[2]};
+}
+
+bool bad_region_args(const hdsm_map_config* cfg, const int32_t* dim, const int32_t* lo, const int32_t* bdim) {
+  if (!cfg || !dim || !lo || !bdim || dim[0] < 1 || dim[1] < 1 || dim[2] < 1 || !(cfg->voxel_size > 0) || cfg->inflation_dist < 0 ||
+      cfg->potential_dist < 0 || cfg->potential_pow < 0) {
+    g_map_err = "null or invalid argument";
+    return true;
+  }
+  for (int ax = 0; ax < 3; ++ax)
+    if (bdim[ax] < 0 || lo[ax] < 0 || lo[ax] > dim[ax] || bdim[ax] > dim[ax] - lo[ax]) {
+      g_map_err = "the edit box does not lie inside the grid";
+      return true;
+    }
+  return false;
+}
+
+constexpr int kRegionFields = 4;  // box-sized byte fields of the region form: the raw box and three working fields
+
+int run_region(const hdsm_map_config* cfg, const int32_t dim[3], const int8_t* d_raw, int8_t* d_out, const int32_t lo[3], const int32_t bdim[3],
+               uint8_t* scratch, hipStream_t st) {
+  MapTables tb;
+  if (int rc = build_tables(*cfg, &tb)) return rc;
+  const int64_t gvox = (int64_t)dim[0] * dim[1] * dim[2];
+  if (gvox < VPT) {
+    g_map_err = "grids of fewer than 4 voxels are not supported";
+    return HDSM_ERR_BAD_ARG;
+  }
+  if (gvox >= (int64_t)1 << 30) {
+    g_map_err = "grid too large (>= 2^30 voxels)";
+    return HDSM_ERR_CAPACITY;
+  }
+  Region r;
+  region_boxes(tb, dim, lo, bdim, &r);
+  if (r.wnx == 0) return HDSM_OK;
+  const int vox = r.bnx * r.bny * r.bnz;
+  Dims d{r.bnx, r.bny, r.bnz, vox};
+  int8_t* rawbox = reinterpret_cast<int8_t*>(scratch);
+  uint8_t* a = scratch + (size_t)vox;
+  uint8_t* b = scratch + 2 * (size_t)vox;
+  uint8_t* c = scratch + 3 * (size_t)vox;
+  int8_t* stage0 = reinterpret_cast<int8_t*>(b);
+  int8_t* inflated = reinterpret_cast<int8_t*>(a);
+  int8_t* final_box = reinterpret_cast<int8_t*>(c);
+  const dim3 block(256);
+  auto blocks_for = [](int nx, int rows) { return dim3((unsigned)std::min<int>((((nx + VPT - 1) / VPT) * rows + 255) / 256, 4096)); };
+  const dim3 grid((unsigned)std::min<int>(((vox + VPT - 1) / VPT + 255) / 256, 4096));
+  const uint8_t* nou = nullptr;
+  const int8_t* nog = nullptr;
+  int8_t* no8 = nullptr;
+  uint8_t* nod = nullptr;
+  hipLaunchKernelGGL(k_region_gather, blocks_for(r.bnx, r.bny * r.bnz), block, 0, st, r, tb.rn0, d_raw, rawbox, c);
+  // the nine passes of run_device on the box (the seeds of SetUncertainToUnknown come from the gather: pass one is a plain x pass)
+  hipLaunchKernelGGL((k_pass<0, 0, 0, false>), grid, block, 0, st, d, tb.rn0, tb, nog, c, a, no8);
+  hipLaunchKernelGGL((k_pass<1, 0, 0, false>), grid, block, 0, st, d, tb.rn0, tb, nog, a, c, no8);
+  hipLaunchKernelGGL((k_pass<2, 0, 3, false>), grid, block, 0, st, d, tb.rn0, tb, rawbox, c, nod, stage0);
+  hipLaunchKernelGGL((k_pass<0, 1, 0, true>), grid, block, 0, st, d, tb.rn1, tb, stage0, nou, a, no8);
+  hipLaunchKernelGGL((k_pass<1, 0, 0, true>), grid, block, 0, st, d, tb.rn1, tb, nog, a, c, no8);
+  hipLaunchKernelGGL((k_pass<2, 0, 1, true>), grid, block, 0, st, d, tb.rn1, tb, stage0, c, nod, inflated);
+  hipLaunchKernelGGL((k_pass<0, 1, 0, true>), grid, block, 0, st, d, tb.rn2, tb, inflated, nou, c, no8);
+  hipLaunchKernelGGL((k_pass<1, 0, 0, true>), grid, block, 0, st, d, tb.rn2, tb, nog, c, b, no8);
+  hipLaunchKernelGGL((k_pass<2, 0, 2, true>), grid, block, 0, st, d, tb.rn2, tb, inflated, b, nod, final_box);
+  hipLaunchKernelGGL(k_region_scatter, blocks_for(r.wnx, r.wny * r.wnz), block, 0, st, r, final_box, d_out);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    g_map_err = hipGetErrorString(e);
+    return HDSM_ERR_DEVICE;
+  }
+  return HDSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -351,6 +520,74 @@ int hdsm_map_preprocess(int32_t device, const hdsm_map_config* cfg, int32_t n_gr
   if (e == hipSuccess) rc = run_device(cfg, n_grids, dim, d_in, d_out, d_scr, nullptr);
   if (e == hipSuccess && rc == HDSM_OK) e = hipMemcpy(grids_out, d_out, total, hipMemcpyDeviceToHost);
   (void)hipFree(d_in), (void)hipFree(d_out), (void)hipFree(d_scr);
+  if (e != hipSuccess) {
+    g_map_err = hipGetErrorString(e);
+    return HDSM_ERR_DEVICE;
+  }
+  return rc;
+}
+
+int hdsm_map_region_extent(const hdsm_map_config* cfg, const int32_t dim[3], const int32_t lo[3], const int32_t bdim[3], int32_t write_lo[3],
+                           int32_t write_dim[3], int32_t work_lo[3], int32_t work_dim[3]) {
+  if (bad_region_args(cfg, dim, lo, bdim)) return HDSM_ERR_BAD_ARG;
+  MapTables tb;
+  if (int rc = build_tables(*cfg, &tb)) return rc;
+  Region r;
+  region_boxes(tb, dim, lo, bdim, &r);
+  if (write_lo) write_lo[0] = r.wx, write_lo[1] = r.wy, write_lo[2] = r.wz;
+  if (write_dim) write_dim[0] = r.wnx, write_dim[1] = r.wny, write_dim[2] = r.wnz;
+  if (work_lo) work_lo[0] = r.bx, work_lo[1] = r.by, work_lo[2] = r.bz;
+  if (work_dim) work_dim[0] = r.bnx, work_dim[1] = r.bny, work_dim[2] = r.bnz;
+  return HDSM_OK;
+}
+
+size_t hdsm_map_region_scratch_bytes(const hdsm_map_config* cfg, const int32_t dim[3], const int32_t lo[3], const int32_t bdim[3]) {
+  int32_t wd[3];
+  if (hdsm_map_region_extent(cfg, dim, lo, bdim, nullptr, nullptr, nullptr, wd) != HDSM_OK) return 0;
+  return (size_t)kRegionFields * wd[0] * wd[1] * wd[2];
+}
+
+int hdsm_map_preprocess_region_device(int32_t device, const hdsm_map_config* cfg, const int32_t dim[3], const int8_t* raw_full, int8_t* out_full,
+                                      const int32_t lo[3], const int32_t bdim[3], void* scratch, void* hip_stream) {
+  if (bad_region_args(cfg, dim, lo, bdim)) return HDSM_ERR_BAD_ARG;
+  if (!raw_full || !out_full) {
+    g_map_err = "null grid";
+    return HDSM_ERR_BAD_ARG;
+  }
+  if (bdim[0] == 0 || bdim[1] == 0 || bdim[2] == 0) return HDSM_OK;
+  if (!scratch) {
+    g_map_err = "null scratch";
+    return HDSM_ERR_BAD_ARG;
+  }
+  if (hipSetDevice(device) != hipSuccess) return HDSM_ERR_NO_DEVICE;
+  return run_region(cfg, dim, raw_full, out_full, lo, bdim, static_cast<uint8_t*>(scratch), static_cast<hipStream_t>(hip_stream));
+}
+
+int hdsm_map_preprocess_region(int32_t device, const hdsm_map_config* cfg, const int32_t dim[3], const int8_t* raw_full, int8_t* out_full,
+                               const int32_t lo[3], const int32_t bdim[3]) {
+  if (bad_region_args(cfg, dim, lo, bdim)) return HDSM_ERR_BAD_ARG;
+  if (!raw_full || !out_full) {
+    g_map_err = "null grid";
+    return HDSM_ERR_BAD_ARG;
+  }
+  if (bdim[0] == 0 || bdim[1] == 0 || bdim[2] == 0) return HDSM_OK;
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= device || hipSetDevice(device) != hipSuccess) {
+    g_map_err = "no HIP device";
+    return HDSM_ERR_NO_DEVICE;
+  }
+  const size_t total = (size_t)dim[0] * dim[1] * dim[2], scr = hdsm_map_region_scratch_bytes(cfg, dim, lo, bdim);
+  int8_t *d_raw = nullptr, *d_out = nullptr;
+  uint8_t* d_scr = nullptr;
+  hipError_t e = hipMalloc(&d_raw, total);
+  if (e == hipSuccess) e = hipMalloc(&d_out, total);
+  if (e == hipSuccess) e = hipMalloc(&d_scr, scr ? scr : 1);
+  int rc = HDSM_OK;
+  if (e == hipSuccess) e = hipMemcpy(d_raw, raw_full, total, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_out, out_full, total, hipMemcpyHostToDevice);
+  if (e == hipSuccess) rc = run_region(cfg, dim, d_raw, d_out, lo, bdim, d_scr, nullptr);
+  if (e == hipSuccess && rc == HDSM_OK) e = hipMemcpy(out_full, d_out, total, hipMemcpyDeviceToHost);
+  (void)hipFree(d_raw), (void)hipFree(d_out), (void)hipFree(d_scr);
   if (e != hipSuccess) {
     g_map_err = hipGetErrorString(e);
     return HDSM_ERR_DEVICE;

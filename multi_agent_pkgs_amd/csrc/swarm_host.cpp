@@ -595,6 +595,24 @@ int hdsm_swarm_set_world(void* swarm, const int8_t* occupancy, const int32_t dim
   return HDSM_OK;
 }
 
+// A map update (VoxelGridResponseCallback / MappingUtilVoxelGridCallback, AC:2310-2378, for the shared world): the box lo .. lo + bdim
+// of the processed world takes `values` [bdim[2]][bdim[1]][bdim[0]] as they are. Everything reads the world at the moment it runs, so
+// the next corridor / path step sees the new voxels as after hdsm_swarm_set_world of the edited grid; kept polyhedra are not looked at
+// again (AC:1253-1282 keeps them too).
+int hdsm_swarm_update_world(void* swarm, const int8_t* values, const int32_t lo[3], const int32_t bdim[3]) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !sw->has_world || !lo || !bdim) return HDSM_ERR_BAD_ARG;
+  for (int ax = 0; ax < 3; ++ax)
+    if (bdim[ax] < 0 || lo[ax] < 0 || lo[ax] > sw->wdim[ax] || bdim[ax] > sw->wdim[ax] - lo[ax]) return HDSM_ERR_BAD_ARG;
+  if (bdim[0] == 0 || bdim[1] == 0 || bdim[2] == 0) return HDSM_OK;
+  if (!values) return HDSM_ERR_BAD_ARG;
+  for (int k = 0; k < bdim[2]; ++k)
+    for (int j = 0; j < bdim[1]; ++j)
+      std::memcpy(&sw->world[((size_t)(lo[2] + k) * sw->wdim[1] + (lo[1] + j)) * sw->wdim[0] + lo[0]], values + ((size_t)k * bdim[1] + j) * bdim[0],
+                  (size_t)bdim[0]);
+  return HDSM_OK;
+}
+
 int hdsm_swarm_set_paths(void* swarm, const double* paths, const int32_t* n_path, int32_t pmax) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw || !paths || !n_path || pmax < 2) return HDSM_ERR_BAD_ARG;

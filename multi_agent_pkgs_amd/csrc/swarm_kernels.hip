@@ -91,6 +91,7 @@ static_assert(SLAB + 4096 <= 64 * 1024, "k_corridor: dynamic + static LDS exceed
 // formed from the entry — with the arithmetic a decomposition in ITS grid would use, origin included (rows_from_structure), so the
 // host mirror, which grows the polyhedron again, gets the same bits.
 constexpr int CACHE_POLYS = 6;
+constexpr int32_t kCacheHole = INT32_MIN;  // seed_w[.][0] of an entry a map update dropped (k_cache_invalidate): no request has it
 struct PolyCache {
   hdsm_cd::PolyStruct ps[CACHE_POLYS];
   int32_t seed_w[CACHE_POLYS][3], off[CACHE_POLYS][3], ground_w[CACHE_POLYS], interior[CACHE_POLYS];
@@ -317,13 +318,16 @@ __device__ __forceinline__ void corridor_step_wave(const Cfg& c, AgentS& ag, con
         } else {
           ag.polys[n_poly].seed = seed_world;
           if (pc != nullptr && rad > 0) {  // (rad = 0: the plain form ran; it keeps no chamfer sources)
-            const int slot = pc->next;
+            int slot = pc->next;  // (a slot a map update emptied is filled first, and the ring does not move for it)
+            bool hole = false;
+            for (int k = 0; k < pc->n && !hole; ++k)
+              if (pc->seed_w[k][0] == kCacheHole) slot = k, hole = true;
             hdsm_cd::wave_poly_structure(lds, hdsm_cd::Cell{seed[0], seed[1], seed[2]}, &pc->ps[slot], lane);
             if (lane < 3) pc->seed_w[slot][lane] = seed_w[lane], pc->off[slot][lane] = off_w[lane];
             __syncthreads();
             if (lane == 0) {
               pc->ground_w[slot] = ground_w, pc->interior[slot] = interior ? 1 : 0;
-              pc->next = (slot + 1) % CACHE_POLYS, pc->n = pc->n < CACHE_POLYS ? pc->n + 1 : CACHE_POLYS;
+              if (!hole) pc->next = (slot + 1) % CACHE_POLYS, pc->n = pc->n < CACHE_POLYS ? pc->n + 1 : CACHE_POLYS;
             }
           }
         }
@@ -579,6 +583,41 @@ __global__ __launch_bounds__(256) void k_flags(int rec, int n, const double* pla
   has[k] = (v == v) ? 1 : 0;
 }
 
+// ---- map updates in flight (ABI 1.7) ----
+// values [bdim[2]][bdim[1]][bdim[0]] into the box lo .. lo + bdim of a grid [.][ny][nx]: thread <-> up to four voxels of one row
+__global__ __launch_bounds__(256) void k_box_put(const int8_t* __restrict__ vals, int8_t* __restrict__ grid, int nx, int ny, int lx, int ly, int lz,
+                                                 int bx, int by, int bz) {
+  const int qpr = (bx + 3) / 4, rows = by * bz;
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < qpr * rows; q += gridDim.x * blockDim.x) {
+    const int row = q / qpr, x0 = (q - row * qpr) * 4, z = row / by, y = row - z * by;
+    const int n = bx - x0 < 4 ? bx - x0 : 4;
+    const int8_t* in = vals + (size_t)row * bx + x0;
+    int8_t* out = grid + ((size_t)(lz + z) * ny + (ly + y)) * nx + (lx + x0);
+    if (n == 4) __builtin_memcpy(out, in, 4);
+    else
+      for (int k = 0; k < n; ++k) out[k] = in[k];
+  }
+}
+
+// The polyhedron cache after voxels lo .. hi (inclusive, world voxels) were written: one lane per (agent, entry). An entry whose
+// decomposition could have looked at a written voxel — its seed +- (rad + 1): wave_map_radius and one voxel of margin — is dropped,
+// the others stay. A dropped entry becomes a hole: its seed voxel is set to kCacheHole, so it is never found again, and the agent's
+// n / next are left as they are; the next polyhedron k_corridor records goes into the first hole, so the agent keeps its six slots.
+// (An entry is read only through the comparison of its seed voxel, so nothing else of it needs clearing.)
+__global__ __launch_bounds__(256) void k_cache_invalidate(PolyCache* cache, int n_agents, int rad, int lx, int ly, int lz, int hx, int hy, int hz,
+                                                          unsigned long long* dropped) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= n_agents * CACHE_POLYS) return;
+  PolyCache& pc = cache[t / CACHE_POLYS];
+  const int e = t % CACHE_POLYS;
+  if (e >= pc.n || pc.seed_w[e][0] == kCacheHole) return;
+  const int sx = pc.seed_w[e][0], sy = pc.seed_w[e][1], sz = pc.seed_w[e][2];
+  const bool meets = sx + rad >= lx && sx - rad <= hx && sy + rad >= ly && sy - rad <= hy && sz + rad >= lz && sz - rad <= hz;
+  if (!meets) return;
+  pc.seed_w[e][0] = kCacheHole;
+  atomicAdd(dropped, 1ull);
+}
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -623,6 +662,16 @@ struct DSwarm {
   hipEvent_t audit_ev[2] = {nullptr, nullptr};
   double* d_hist = nullptr;
   int hist_cap = 0, hist_n = 0, hist_dropped = 0, hist_delivered = 0;
+  // map updates in flight (nothing below is allocated or launched before the first hdsm_dswarm_update_world* / _set_raw_world): the
+  // resident raw grid with the map configuration and the scratch of the region pre-processing, the staging buffer of the
+  // host-pointer forms, updates applied, voxels written, and the device's count of cache entries dropped
+  int8_t* d_raw = nullptr;
+  uint8_t* d_map_scr = nullptr;
+  hdsm_map_config mcfg{};
+  int8_t* d_edit = nullptr;
+  size_t edit_cap = 0;
+  long long world_updates = 0, world_voxels = 0;
+  unsigned long long* d_dropped = nullptr;
 };
 
 // the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports
@@ -666,6 +715,54 @@ void free_all(DSwarm* d) {
   hdsm_audit::device_free(&d->abuf);
   if (d->d_report) (void)hipFree(d->d_report);
   if (d->d_hist) (void)hipFree(d->d_hist);
+  for (void* p : {static_cast<void*>(d->d_raw), static_cast<void*>(d->d_map_scr), static_cast<void*>(d->d_edit), static_cast<void*>(d->d_dropped)})
+    if (p) (void)hipFree(p);
+}
+
+// the box lo .. lo + bdim inside the device world? (0 empty, 1 yes, < 0 an error)
+int world_box(DSwarm* d, const int32_t* lo, const int32_t* bdim) {
+  if (!d || !lo || !bdim) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world (hdsm_swarm_set_world before hdsm_dswarm_create)");
+  for (int ax = 0; ax < 3; ++ax)
+    if (bdim[ax] < 0 || lo[ax] < 0 || lo[ax] > d->c.wdim[ax] || bdim[ax] > d->c.wdim[ax] - lo[ax])
+      return fail(HDSM_ERR_BAD_ARG, "the box does not lie inside the world");
+  return (bdim[0] == 0 || bdim[1] == 0 || bdim[2] == 0) ? 0 : 1;
+}
+
+// values (device) into the box of `grid` (the device world or the resident raw grid), on st
+int put_box(DSwarm* d, const int8_t* d_vals, int8_t* grid, const int32_t lo[3], const int32_t bdim[3], hipStream_t st) {
+  const int quads = ((bdim[0] + 3) / 4) * bdim[1] * bdim[2];
+  hipLaunchKernelGGL(k_box_put, dim3((unsigned)std::min((quads + 255) / 256, 4096)), dim3(256), 0, st, d_vals, grid, d->c.wdim[0], d->c.wdim[1], lo[0],
+                     lo[1], lo[2], bdim[0], bdim[1], bdim[2]);
+  HIP_TRY(hipGetLastError());
+  return HDSM_OK;
+}
+
+// drops the cache entries that could have looked at the written voxels wlo .. wlo + wdim (NULL: every entry), on st, and books the update
+int invalidate(DSwarm* d, const int32_t* wlo, const int32_t* wdim, hipStream_t st) {
+  if (!d->d_dropped) HIP_TRY(dalloc(&d->d_dropped, 1));
+  if (!d->d_cache || d->n_local == 0) return HDSM_OK;
+  const int rad = hdsm_cd::wave_map_radius(d->c.n_it_decomp) + 1;
+  const int big = 1 << 29;
+  const int l[3] = {wlo ? wlo[0] : -big, wlo ? wlo[1] : -big, wlo ? wlo[2] : -big};
+  const int h[3] = {wlo ? wlo[0] + wdim[0] - 1 : big, wlo ? wlo[1] + wdim[1] - 1 : big, wlo ? wlo[2] + wdim[2] - 1 : big};
+  hipLaunchKernelGGL(k_cache_invalidate, dim3((unsigned)((d->n_local * CACHE_POLYS + 255) / 256)), dim3(256), 0, st, d->d_cache, d->n_local, rad, l[0], l[1],
+                     l[2], h[0], h[1], h[2], d->d_dropped);
+  HIP_TRY(hipGetLastError());
+  return HDSM_OK;
+}
+
+// the host values of a box into the staging buffer (the device is idle: the callers have synchronised)
+int stage_box(DSwarm* d, const int8_t* values, const int32_t bdim[3]) {
+  const size_t bytes = (size_t)bdim[0] * bdim[1] * bdim[2];
+  if (bytes > d->edit_cap) {
+    if (d->d_edit) (void)hipFree(d->d_edit);
+    d->d_edit = nullptr, d->edit_cap = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_edit), bytes));
+    d->edit_cap = bytes;
+  }
+  HIP_TRY(hipMemcpy(d->d_edit, values, bytes, hipMemcpyHostToDevice));
+  return HDSM_OK;
 }
 
 }  // namespace
@@ -1163,6 +1260,110 @@ int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_
   }
   if (n_rounds) *n_rounds = d->hist_n;
   if (dropped) *dropped = d->hist_dropped;
+  return HDSM_OK;
+}
+
+// ---- map updates in flight (ABI 1.7; semantics in hdsm_swarm.h) ----
+int hdsm_dswarm_update_world(void* dswarm, const int8_t* values, const int32_t lo[3], const int32_t bdim[3]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  const int k = world_box(d, lo, bdim);
+  if (k <= 0) return k;
+  if (!values) return fail(HDSM_ERR_BAD_ARG, "null values");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = stage_box(d, values, bdim)) return rc;
+  if (int rc = put_box(d, d->d_edit, d->d_world, lo, bdim, nullptr)) return rc;
+  if (int rc = invalidate(d, lo, bdim, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  ++d->world_updates, d->world_voxels += (long long)bdim[0] * bdim[1] * bdim[2];
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_raw_world(void* dswarm, const hdsm_map_config* map_cfg, const int8_t* raw_full) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !map_cfg || !raw_full) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world (hdsm_swarm_set_world before hdsm_dswarm_create)");
+  const size_t vox = (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2];
+  for (size_t i = 0; i < vox; ++i)
+    if (raw_full[i] != -1 && raw_full[i] != 0 && raw_full[i] != 100) return fail(HDSM_ERR_BAD_ARG, "a raw grid holds -1, 0 and 100 only");
+  if (vox < 4 || vox >= ((size_t)1 << 30)) return fail(HDSM_ERR_BAD_ARG, "a raw world needs 4 .. 2^30 - 1 voxels");
+  const int32_t zero[3] = {0, 0, 0};
+  const size_t scr = hdsm_map_region_scratch_bytes(map_cfg, d->c.wdim, zero, d->c.wdim);  // the largest box; >= the full form's 2 vox
+  if (scr == 0) return fail(HDSM_ERR_BAD_ARG, std::string("map configuration: ") + hdsm_map_last_error());
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!d->d_raw) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_raw), vox));
+  if (!d->d_map_scr) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_map_scr), scr));
+  HIP_TRY(hipMemcpy(d->d_raw, raw_full, vox, hipMemcpyHostToDevice));
+  // (the arguments were checked above: what can still fail is a launch, and then the device world is no longer the old one —
+  // the cache is emptied on that way out too)
+  const int rc = hdsm_map_preprocess_device(d->device, map_cfg, 1, d->c.wdim, d->d_raw, d->d_world, d->d_map_scr, nullptr);
+  if (rc == HDSM_OK) d->mcfg = *map_cfg;
+  const int rc2 = invalidate(d, nullptr, nullptr, nullptr);
+  if (rc) {
+    (void)hipFree(d->d_raw);  // (no raw world is resident: the raw update calls keep refusing)
+    d->d_raw = nullptr;
+    return fail(rc, std::string("hdsm_map_preprocess_device: ") + hdsm_map_last_error());
+  }
+  if (rc2) return rc2;
+  HIP_TRY(hipDeviceSynchronize());
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_update_world_raw_device(void* dswarm, const int8_t* d_raw_values, const int32_t lo[3], const int32_t bdim[3], void* hip_stream) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  const int k = world_box(d, lo, bdim);
+  if (k < 0) return k;
+  if (!d->d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
+  if (k == 0) return HDSM_OK;
+  if (!d_raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
+  HIP_TRY(hipSetDevice(d->device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  int32_t wlo[3], wdim[3];
+  if (int rc = hdsm_map_region_extent(&d->mcfg, d->c.wdim, lo, bdim, wlo, wdim, nullptr, nullptr)) return fail(rc, hdsm_map_last_error());
+  if (int rc = put_box(d, d_raw_values, d->d_raw, lo, bdim, st)) return rc;
+  if (int rc = hdsm_map_preprocess_region_device(d->device, &d->mcfg, d->c.wdim, d->d_raw, d->d_world, lo, bdim, d->d_map_scr, st))
+    return fail(rc, std::string("hdsm_map_preprocess_region_device: ") + hdsm_map_last_error());
+  if (int rc = invalidate(d, wlo, wdim, st)) return rc;
+  ++d->world_updates, d->world_voxels += (long long)wdim[0] * wdim[1] * wdim[2];
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_update_world_raw(void* dswarm, const int8_t* raw_values, const int32_t lo[3], const int32_t bdim[3]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  const int k = world_box(d, lo, bdim);
+  if (k < 0) return k;
+  if (!d->d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
+  if (k == 0) return HDSM_OK;
+  if (!raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = stage_box(d, raw_values, bdim)) return rc;
+  if (int rc = hdsm_dswarm_update_world_raw_device(dswarm, d->d_edit, lo, bdim, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_world(void* dswarm, int8_t* world) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !world) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(world, d->d_world, (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2], hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_world_stats(void* dswarm, int64_t out[4]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->world_updates, out[1] = d->world_voxels, out[2] = 0, out[3] = d->d_raw ? 1 : 0;
+  if (!d->d_dropped) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned long long n = 0;
+  HIP_TRY(hipMemcpy(&n, d->d_dropped, sizeof n, hipMemcpyDeviceToHost));
+  out[2] = (int64_t)n;
   return HDSM_OK;
 }
 

@@ -33,7 +33,10 @@ EXPORTS = ("hdsm_version", "hdsm_last_error", "hdsm_default_params", "hdsm_creat
            "hdsm_dswarm_set_audit", "hdsm_dswarm_flight_report", "hdsm_dswarm_last_audit_round", "hdsm_dswarm_last_audit_ms",
            "hdsm_dswarm_set_history", "hdsm_dswarm_download_history",
            "hdsm_stats_create", "hdsm_stats_destroy", "hdsm_stats_add", "hdsm_stats_add_state", "hdsm_stats_add_latency",
-           "hdsm_stats_shutdown", "hdsm_map_preprocess", "hdsm_map_preprocess_device", "hdsm_map_last_error")
+           "hdsm_stats_shutdown", "hdsm_map_preprocess", "hdsm_map_preprocess_device", "hdsm_map_last_error",
+           "hdsm_map_region_extent", "hdsm_map_region_scratch_bytes", "hdsm_map_preprocess_region", "hdsm_map_preprocess_region_device",
+           "hdsm_swarm_update_world", "hdsm_dswarm_update_world", "hdsm_dswarm_set_raw_world", "hdsm_dswarm_update_world_raw",
+           "hdsm_dswarm_update_world_raw_device", "hdsm_dswarm_download_world", "hdsm_dswarm_world_stats")
 
 
 class HdsmError(RuntimeError):
@@ -306,6 +309,39 @@ def map_preprocess_device(cfg, d_in, d_out, d_scratch, stream=None, device=0):
     if rc:
         L.hdsm_map_last_error.restype = C.c_char_p
         raise HdsmError(rc, L.hdsm_map_last_error().decode())
+
+
+def _map_error(rc):
+    L = load()
+    L.hdsm_map_last_error.restype = C.c_char_p
+    return HdsmError(rc, L.hdsm_map_last_error().decode())
+
+
+def map_region_extent(cfg, dim, lo, bdim):
+    """hdsm_map_region_extent: for an edit box lo .. lo + bdim (x, y, z voxels) of a raw grid of dimensions dim (nx, ny, nz), the
+    box W the processed grid can change in and the working box the stages run on: (write_lo, write_dim, work_lo, work_dim), each an
+    int32 array of three. Host arithmetic only."""
+    dim, lo, bdim = _i32(dim), _i32(lo), _i32(bdim)
+    out = [np.zeros(3, np.int32) for _ in range(4)]
+    rc = load().hdsm_map_region_extent(C.byref(cfg), _p(dim, C.c_int32), _p(lo, C.c_int32), _p(bdim, C.c_int32), *[_p(o, C.c_int32) for o in out])
+    if rc:
+        raise _map_error(rc)
+    return tuple(out)
+
+
+def map_preprocess_region(cfg, raw_full, out_full, lo, bdim, device=0):
+    """hdsm_map_preprocess_region: raw_full int8 [nz][ny][nx] is the raw grid AFTER an edit inside the box lo .. lo + bdim (x, y, z),
+    out_full the processed grid of BEFORE it. Returns the processed grid of after it (a new array): the nine passes run on the
+    working box only, and only W is written. Runs on the GPU."""
+    raw = np.ascontiguousarray(raw_full, dtype=np.int8)
+    out = np.array(out_full, dtype=np.int8, order="C", copy=True)
+    assert raw.ndim == 3 and out.shape == raw.shape
+    dim, lo, bdim = np.asarray(raw.shape[::-1], dtype=np.int32), _i32(lo), _i32(bdim)
+    rc = load().hdsm_map_preprocess_region(C.c_int32(device), C.byref(cfg), _p(dim, C.c_int32), _p(raw, C.c_int8), _p(out, C.c_int8),
+                                           _p(lo, C.c_int32), _p(bdim, C.c_int32))
+    if rc:
+        raise _map_error(rc)
+    return out
 
 
 def poly_octa3d_batch(world, ldim, off, ground_k, seed, variant, origin, n_it=42, res=0.3, max_rows=32, device=0, wave=False):

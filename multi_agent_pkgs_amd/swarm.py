@@ -93,6 +93,7 @@ class SwarmShard:
         goals = np.ascontiguousarray(goals, dtype=np.float64)
         self.n_local = starts.shape[0]
         self.h = C.c_void_p()
+        self.world_shape = None
         rc = self.lib.hdsm_swarm_create(C.byref(self.prm), C.byref(self.cfg), self.n_rob, self.first_id,
                                         self.n_local, _p(starts, C.c_double), _p(goals, C.c_double),
                                         C.byref(self.h))
@@ -110,6 +111,7 @@ class SwarmShard:
 
     def set_world(self, occupancy, origin=(0.0, 0.0, 0.0)):
         """occupancy int8 [nz][ny][nx] at cfg.voxel_size (>= 100 occupied, already inflated), or None for free space."""
+        self.world_shape = None
         if occupancy is None:
             rc = self.lib.hdsm_swarm_set_world(self.h, None, _p(np.zeros(3, np.int32), C.c_int32), _p(np.zeros(3), C.c_double))
         else:
@@ -120,6 +122,19 @@ class SwarmShard:
                                                _p(org, C.c_double))
         if rc:
             raise _lib.HdsmError(rc, "hdsm_swarm_set_world")
+        if occupancy is not None:
+            self.world_shape = occ.shape  # (wz, wy, wx): what DeviceSwarm.download_world returns
+
+    def update_world(self, values, lo):
+        """hdsm_swarm_update_world: values int8 [bz][by][bx] replace the box of the processed world that starts at voxel lo (x, y, z).
+        From the next corridor / path step on everything reads the new voxels; kept polyhedra are not checked again and paths
+        adapt only through the path step."""
+        vals = np.ascontiguousarray(values, dtype=np.int8)
+        assert vals.ndim == 3
+        lo, bdim = np.asarray(lo, dtype=np.int32), np.asarray(vals.shape[::-1], dtype=np.int32)
+        rc = self.lib.hdsm_swarm_update_world(self.h, _p(vals, C.c_int8), _p(lo, C.c_int32), _p(bdim, C.c_int32))
+        if rc:
+            raise _lib.HdsmError(rc, "hdsm_swarm_update_world")
 
     def prepare_corridor(self):
         """GenerateSafeCorridor alone (hdsm_swarm_prepare_corridor): the reference's order when the reference trajectory is
@@ -321,6 +336,10 @@ class SwarmLoop:
             return failed
         return 0
 
+    def update_world(self, values, lo):
+        """A map update between two rounds (SwarmShard.update_world)."""
+        self.shard.update_world(values, lo)
+
     def step(self, record=None):
         if self.reference is not None:
             self.shard.prepare_corridor()  # AC:165 before AC:171
@@ -485,6 +504,65 @@ class DeviceSwarm:
         if rc:
             raise self._err(rc)
         return float(ms.value)
+
+    # ---- map updates in flight (include/hdsm_swarm.h, ABI 1.7) ----
+    @staticmethod
+    def _box(values, lo):
+        vals = np.ascontiguousarray(values, dtype=np.int8)
+        assert vals.ndim == 3
+        return vals, np.asarray(lo, dtype=np.int32), np.asarray(vals.shape[::-1], dtype=np.int32)
+
+    def update_world(self, values, lo):
+        """hdsm_dswarm_update_world: PROCESSED values int8 [bz][by][bx] into the box of the device world that starts at voxel lo
+        (x, y, z); the cache entries that looked at the box are dropped. Synchronises."""
+        vals, lo, bdim = self._box(values, lo)
+        rc = self.lib.hdsm_dswarm_update_world(self.h, _p(vals, C.c_int8), _p(lo, C.c_int32), _p(bdim, C.c_int32))
+        if rc:
+            raise self._err(rc)
+
+    def set_raw_world(self, map_cfg, raw_full):
+        """hdsm_dswarm_set_raw_world: a RAW grid int8 [wz][wy][wx] (-1, 0, 100) becomes resident, the device world its
+        hdsm_map_preprocess with map_cfg (params.MapConfig); every cache entry is dropped. Synchronises."""
+        raw = np.ascontiguousarray(raw_full, dtype=np.int8)
+        if raw.shape != self.shard.world_shape:
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "set_raw_world: a grid of the world's dimensions expected")
+        rc = self.lib.hdsm_dswarm_set_raw_world(self.h, C.byref(map_cfg), _p(raw, C.c_int8))
+        if rc:
+            raise self._err(rc)
+
+    def update_world_raw(self, raw_values, lo, stream=None):
+        """hdsm_dswarm_update_world_raw: RAW values int8 [bz][by][bx] into the resident raw grid at voxel lo, the region pre-processing
+        into the device world, the cache entries that looked at the written box W dropped. A numpy array: copied in, synchronises.
+        A torch device tensor (int8, contiguous): hdsm_dswarm_update_world_raw_device, asynchronous on `stream` — which must be the
+        stream the rounds run on; keep the tensor alive until the stream has passed the edit."""
+        if hasattr(raw_values, "data_ptr"):
+            assert raw_values.is_cuda and raw_values.is_contiguous() and raw_values.dim() == 3 and raw_values.element_size() == 1
+            lo, bdim = np.asarray(lo, dtype=np.int32), np.asarray(tuple(raw_values.shape)[::-1], dtype=np.int32)
+            sp = C.c_void_p(stream.cuda_stream if stream is not None else 0)
+            rc = self.lib.hdsm_dswarm_update_world_raw_device(self.h, C.c_void_p(raw_values.data_ptr()), _p(lo, C.c_int32), _p(bdim, C.c_int32), sp)
+        else:
+            vals, lo, bdim = self._box(raw_values, lo)
+            rc = self.lib.hdsm_dswarm_update_world_raw(self.h, _p(vals, C.c_int8), _p(lo, C.c_int32), _p(bdim, C.c_int32))
+        if rc:
+            raise self._err(rc)
+
+    def download_world(self):
+        """hdsm_dswarm_download_world: the processed device world, int8 [wz][wy][wx]. Synchronises."""
+        if self.shard.world_shape is None:
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "download_world: the shard has no world")
+        world = np.zeros(self.shard.world_shape, np.int8)
+        rc = self.lib.hdsm_dswarm_download_world(self.h, _p(world, C.c_int8))
+        if rc:
+            raise self._err(rc)
+        return world
+
+    def world_stats(self):
+        """hdsm_dswarm_world_stats: map updates applied, voxels they wrote, cache entries dropped, whether a raw world is resident."""
+        out = (C.c_int64 * 4)()
+        rc = self.lib.hdsm_dswarm_world_stats(self.h, out)
+        if rc:
+            raise self._err(rc)
+        return {"updates": int(out[0]), "voxels": int(out[1]), "dropped": int(out[2]), "raw_resident": bool(out[3])}
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
