@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "audit_core.h"
+#include "device_mem.h"
 
 namespace hdsm_audit {
 
@@ -26,14 +27,13 @@ inline int tile_partners(int S) {
   return fit < TILE_PARTNERS ? fit : TILE_PARTNERS;
 }
 
-struct DeviceBufs {  // scratch of the audit of G records and n_local subjects with step_plan S
+struct __attribute__((visibility("hidden"))) DeviceBufs {  // scratch of the audit of G records and n_local subjects with step_plan S
   int G = 0, n_local = 0, S = 0, tile = 0, chunks = 0;
-  double* d_pos = nullptr;             // [G][S + 1][3]
-  Partial* d_part = nullptr;           // [chunks][n_local]
-  hdsm_audit_round* d_round = nullptr; // [n_local]
+  hdsm_mem::DevBuf<double> d_pos;              // [G][S + 1][3]
+  hdsm_mem::DevBuf<Partial> d_part;            // [chunks][n_local]
+  hdsm_mem::DevBuf<hdsm_audit_round> d_round;  // [n_local]
 };
-hipError_t device_alloc(DeviceBufs* b, int G, int n_local, int S);
-void device_free(DeviceBufs* b);
+hipError_t device_alloc(DeviceBufs* b, int G, int n_local, int S);  // (on an error *b is empty again)
 
 // One round on `st`. audit: k_audit_pack, k_audit, then k_audit_track (merge, own track, d_round, and the flight record when d_report
 // is given). hist_row (may be NULL): [n_local][9] receives the 9 doubles at state0 + k * state_stride bytes of every subject.

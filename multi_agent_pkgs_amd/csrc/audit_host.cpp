@@ -2,8 +2,8 @@
 // hdsm_swarm_audit calls too. Pure host C++; the device form (audit_kernels.hip) gives the same bits.
 #include "../../include/hdsm_swarm.h"
 #include "audit_core.h"
+#include "hdsm_internal.h"
 
-// the argument checks shared by hdsm_flight_audit_host / _batch
 extern "C" int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan,
                                         int32_t first, int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world,
                                         const int32_t wdim[3], const double worigin[3], double voxel_size, const hdsm_audit_round* out) {

@@ -14,10 +14,7 @@
 #include "../../include/hdsm_swarm.h"
 #include "audit_core.h"
 #include "audit_device.h"
-
-extern "C" int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan,
-                                        int32_t first, int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world,
-                                        const int32_t wdim[3], const double worigin[3], double voxel_size, const hdsm_audit_round* out);
+#include "hdsm_internal.h"
 
 namespace hdsm_audit {
 namespace {
@@ -89,21 +86,14 @@ __global__ __launch_bounds__(64) void k_audit_track(int n_local, int S, int firs
 }  // namespace
 
 hipError_t device_alloc(DeviceBufs* b, int G, int n_local, int S) {
-  device_free(b);
+  *b = DeviceBufs{};
   b->G = G, b->n_local = n_local, b->S = S, b->tile = tile_partners(S);
   b->chunks = G > 0 ? (G + b->tile - 1) / b->tile : 1;
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(&b->d_pos), ((size_t)G * (S + 1) * 3 + 1) * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->d_part), ((size_t)b->chunks * n_local + 1) * sizeof(Partial));
-  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&b->d_round), ((size_t)n_local + 1) * sizeof(hdsm_audit_round));
-  if (e != hipSuccess) device_free(b);
+  hipError_t e = b->d_pos.alloc((size_t)G * (S + 1) * 3 + 1);
+  if (e == hipSuccess) e = b->d_part.alloc((size_t)b->chunks * n_local + 1);
+  if (e == hipSuccess) e = b->d_round.alloc((size_t)n_local + 1);
+  if (e != hipSuccess) *b = DeviceBufs{};
   return e;
-}
-
-void device_free(DeviceBufs* b) {
-  if (b->d_pos) (void)hipFree(b->d_pos);
-  if (b->d_part) (void)hipFree(b->d_part);
-  if (b->d_round) (void)hipFree(b->d_round);
-  *b = DeviceBufs{};
 }
 
 hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const uint8_t* d_has, int n_hor, int first, const Weights& w,
@@ -113,12 +103,12 @@ hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const 
   const int rec = (n_hor + 1) * 9;
   if (audit) {
     const long long elems = (long long)b.G * (b.S + 1) * 3;
-    hipLaunchKernelGGL(k_audit_pack, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, b.G, b.S, rec, d_plans, b.d_pos);
+    hipLaunchKernelGGL(k_audit_pack, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, b.G, b.S, rec, d_plans, b.d_pos.get());
     hipLaunchKernelGGL(k_audit, dim3((unsigned)((b.n_local + SWEEP_THREADS - 1) / SWEEP_THREADS), (unsigned)b.chunks), dim3(SWEEP_THREADS), 0, st,
-                       b.G, b.n_local, b.S, first, b.tile, w, b.d_pos, d_has, b.d_part);
+                       b.G, b.n_local, b.S, first, b.tile, w, b.d_pos.get(), d_has, b.d_part.get());
   }
   hipLaunchKernelGGL(k_audit_track, dim3((unsigned)((b.n_local + 63) / 64)), dim3(64), 0, st, b.n_local, b.S, first, b.chunks, audit ? 1 : 0, wd,
-                     b.d_pos, d_plans, rec, d_has, b.d_part, b.d_round, d_report, warn2, state0, state_stride, hist_row);
+                     b.d_pos.get(), d_plans, rec, d_has, b.d_part.get(), b.d_round.get(), d_report, warn2, state0, state_stride, hist_row);
   return hipGetLastError();
 }
 
@@ -134,33 +124,28 @@ extern "C" int hdsm_flight_audit_batch(int32_t device, int32_t n_rob, const doub
   if (n_local == 0) return HDSM_OK;
   if (hipSetDevice(device) != hipSuccess) return HDSM_ERR_NO_DEVICE;
   hdsm_audit::DeviceBufs b;
-  double* d_plans = nullptr;
-  uint8_t* d_has = nullptr;
-  int8_t* d_world = nullptr;
-  const size_t pbytes = (size_t)n_rob * (n_hor + 1) * 9 * sizeof(double), wbytes = world ? (size_t)wdim[0] * wdim[1] * wdim[2] : 0;
-  hipError_t e = hdsm_audit::device_alloc(&b, n_rob, n_local, step_plan);
-  auto ok = [&](hipError_t r) {
-    if (e == hipSuccess) e = r;
-  };
-  ok(hipMalloc(reinterpret_cast<void**>(&d_plans), pbytes)), ok(hipMalloc(reinterpret_cast<void**>(&d_has), (size_t)n_rob));
-  if (world) ok(hipMalloc(reinterpret_cast<void**>(&d_world), wbytes));
-  if (e == hipSuccess) {
-    ok(hipMemcpy(d_plans, plans_all, pbytes, hipMemcpyHostToDevice)), ok(hipMemcpy(d_has, has_plan, (size_t)n_rob, hipMemcpyHostToDevice));
-    if (world) ok(hipMemcpy(d_world, world, wbytes, hipMemcpyHostToDevice));
+  hdsm_mem::DevBuf<double> d_plans;
+  hdsm_mem::DevBuf<uint8_t> d_has;
+  hdsm_mem::DevBuf<int8_t> d_world;
+  const size_t pcount = (size_t)n_rob * (n_hor + 1) * 9, wbytes = world ? (size_t)wdim[0] * wdim[1] * wdim[2] : 0;
+  hdsm_mem::FirstError ok;
+  ok(hdsm_audit::device_alloc(&b, n_rob, n_local, step_plan));
+  ok(d_plans.alloc(pcount)), ok(d_has.alloc((size_t)n_rob));
+  if (world) ok(d_world.alloc(wbytes));
+  if (ok.ok()) {
+    ok(hipMemcpy(d_plans.get(), plans_all, pcount * sizeof(double), hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_has.get(), has_plan, (size_t)n_rob, hipMemcpyHostToDevice));
+    if (world) ok(hipMemcpy(d_world.get(), world, wbytes, hipMemcpyHostToDevice));
   }
-  if (e == hipSuccess) {
+  if (ok.ok()) {
     hdsm_audit::World wd{};
-    wd.world = d_world, wd.voxel_size = voxel_size;
+    wd.world = d_world.get(), wd.voxel_size = voxel_size;
     if (world)
       for (int k = 0; k < 3; ++k) wd.wdim[k] = wdim[k], wd.worigin[k] = worigin[k];
-    ok(hdsm_audit::launch(b, true, d_plans, d_has, n_hor, first, hdsm_audit::weights(drone_radius, drone_z_offset), wd, nullptr, 0.0, nullptr, 0,
+    ok(hdsm_audit::launch(b, true, d_plans.get(), d_has.get(), n_hor, first, hdsm_audit::weights(drone_radius, drone_z_offset), wd, nullptr, 0.0, nullptr, 0,
                           nullptr, nullptr));
     ok(hipDeviceSynchronize());
   }
-  if (e == hipSuccess) ok(hipMemcpy(out, b.d_round, (size_t)n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
-  hdsm_audit::device_free(&b);
-  if (d_plans) (void)hipFree(d_plans);
-  if (d_has) (void)hipFree(d_has);
-  if (d_world) (void)hipFree(d_world);
-  return e == hipSuccess ? HDSM_OK : HDSM_ERR_DEVICE;
+  if (ok.ok()) ok(hipMemcpy(out, b.d_round.get(), (size_t)n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
+  return ok.ok() ? HDSM_OK : HDSM_ERR_DEVICE;
 }

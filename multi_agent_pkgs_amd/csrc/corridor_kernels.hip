@@ -14,6 +14,7 @@
 #include "../../include/hdsm_swarm.h"
 #include "corridor_core.h"
 #include "corridor_wave.h"
+#include "device_mem.h"
 
 namespace {
 
@@ -169,33 +170,30 @@ static int batch_impl(bool wave, int32_t device, int32_t n, const int8_t* world,
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(HDSM_ERR_NO_DEVICE, "no such HIP device");
   if (hipSetDevice(device) != hipSuccess) return fail(HDSM_ERR_NO_DEVICE, "hipSetDevice failed");
   const size_t wtot = (size_t)wdim[0] * wdim[1] * wdim[2], N = (size_t)n;
-  void *d_world = nullptr, *d_off = nullptr, *d_ground = nullptr, *d_seed = nullptr, *d_var = nullptr, *d_org = nullptr, *d_rows = nullptr,
-       *d_nrows = nullptr, *d_rc = nullptr, *d_cells = nullptr, *d_scratch = nullptr;
-  hipError_t e = hipSuccess;
-  auto al = [&](void** p, size_t bytes) {
-    if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 1);
-  };
-  al(&d_world, wtot), al(&d_off, N * 12), al(&d_ground, N * 4), al(&d_seed, N * 12), al(&d_var, N * 4), al(&d_org, N * 24);
-  al(&d_rows, N * max_rows * 32), al(&d_nrows, N * 4), al(&d_rc, N * 4), al(&d_cells, N * 4), al(&d_scratch, wave ? 16 : hdsm_poly_octa3d_scratch_bytes(n));
+  hdsm_mem::DevBuf<int8_t> d_world;
+  hdsm_mem::DevBuf<int32_t> d_off, d_ground, d_seed, d_var, d_nrows, d_rc, d_cells;
+  hdsm_mem::DevBuf<double> d_org, d_rows;
+  hdsm_mem::DevBuf<unsigned char> d_scratch;
+  hdsm_mem::FirstError ok;
+  ok(d_world.alloc(wtot)), ok(d_off.alloc(N * 3)), ok(d_ground.alloc(N)), ok(d_seed.alloc(N * 3)), ok(d_var.alloc(N)), ok(d_org.alloc(N * 3));
+  ok(d_rows.alloc(N * max_rows * 4)), ok(d_nrows.alloc(N)), ok(d_rc.alloc(N)), ok(d_cells.alloc(N));
+  ok(d_scratch.alloc(wave ? 16 : hdsm_poly_octa3d_scratch_bytes(n)));
   auto up = [&](void* d, const void* h, size_t bytes) {
-    if (e == hipSuccess) e = hipMemcpy(d, h, bytes, hipMemcpyHostToDevice);
+    if (ok.ok()) ok(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
   };
-  up(d_world, world, wtot), up(d_off, off, N * 12), up(d_ground, ground_k, N * 4), up(d_seed, seed, N * 12), up(d_var, variant, N * 4);
-  up(d_org, origin, N * 24);
+  up(d_world.get(), world, wtot), up(d_off.get(), off, N * 12), up(d_ground.get(), ground_k, N * 4), up(d_seed.get(), seed, N * 12);
+  up(d_var.get(), variant, N * 4), up(d_org.get(), origin, N * 24);
   int rcall = HDSM_OK;
-  if (e == hipSuccess)
-    rcall = launch_batch(wave, device, n, (const int8_t*)d_world, wdim, ldim, (const int32_t*)d_off, (const int32_t*)d_ground,
-                         (const int32_t*)d_seed, (const int32_t*)d_var, (const double*)d_org, n_it, res, (double*)d_rows, max_rows,
-                         (int32_t*)d_nrows, (int32_t*)d_rc, (int32_t*)d_cells, d_scratch, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (ok.ok())
+    rcall = launch_batch(wave, device, n, d_world.get(), wdim, ldim, d_off.get(), d_ground.get(), d_seed.get(), d_var.get(), d_org.get(), n_it, res,
+                         d_rows.get(), max_rows, d_nrows.get(), d_rc.get(), d_cells.get(), d_scratch.get(), nullptr);
+  if (ok.ok()) ok(hipDeviceSynchronize());
   auto down = [&](void* h, const void* d, size_t bytes) {
-    if (e == hipSuccess && h) e = hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost);
+    if (ok.ok() && h) ok(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
   };
-  down(rows, d_rows, N * max_rows * 32), down(n_rows, d_nrows, N * 4), down(rc, d_rc, N * 4), down(cells, d_cells, N * 4);
-  for (void* p : {d_world, d_off, d_ground, d_seed, d_var, d_org, d_rows, d_nrows, d_rc, d_cells, d_scratch})
-    if (p) (void)hipFree(p);
+  down(rows, d_rows.get(), N * max_rows * 32), down(n_rows, d_nrows.get(), N * 4), down(rc, d_rc.get(), N * 4), down(cells, d_cells.get(), N * 4);
   if (rcall) return rcall;
-  if (e != hipSuccess) return fail(HDSM_ERR_DEVICE, std::string("hdsm_poly_octa3d_batch: ") + hipGetErrorString(e));
+  if (!ok.ok()) return fail(HDSM_ERR_DEVICE, std::string("hdsm_poly_octa3d_batch: ") + hipGetErrorString(ok.e));
   return HDSM_OK;
 }
 

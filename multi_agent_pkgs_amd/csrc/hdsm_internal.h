@@ -1,0 +1,40 @@
+// hdsm_internal.h — the entry points that cross translation units of csrc/ without being in include/, each declared ONCE. The file
+// that defines one and every file that calls one include this header, so a signature that drifts does not compile (they are
+// extern "C" — two are called from the tests through ctypes — and a mismatch would still link).
+// The one exception: hdsm_api.hip defines hdsm_internal_defer_done / _record_done without including it (bench.py keys its stored
+// counter records on a hash of that file, so it is not edited for a declaration).
+#pragma once
+#include "../../include/hdsm_swarm.h"
+
+extern "C" {
+
+// (hdsm_api.hip) every device entry point of the solver handle records its "done" event; the device-resident loop defers the
+// records (on = 1) and leaves one at the end of its round
+int hdsm_internal_defer_done(void* handle, int on);
+int hdsm_internal_record_done(void* handle, void* hip_stream);
+
+// (swarm_host.cpp) the host mirror's flight in and out of the device-resident loop:
+// the plain agent states (hdsm_sw::AgentS [n_local]) and the configuration of a shard; every out argument may be NULL
+int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id, hdsm_params* prm,
+                            hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3], double worigin[3]);
+int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local);
+// the path step's round phase and pending agents (and the goals a device loop set between its rounds); due / goals may be NULL
+int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
+int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
+// the clearance radius of the path step (0: off)
+int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
+// the audit's setting and record (report [n_local], may be NULL on export)
+int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report);
+int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report);
+// rounds flown on the device into the planner records: rows [n_rounds][n_local][9]
+int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows);
+
+// (audit_host.cpp) the argument checks shared by hdsm_flight_audit_host / _batch
+int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan, int32_t first,
+                             int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world, const int32_t wdim[3],
+                             const double worigin[3], double voxel_size, const hdsm_audit_round* out);
+// (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
+int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
+                            const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/hdsm.h"
+#include "device_mem.h"
 
 namespace {
 
@@ -510,18 +511,18 @@ int hdsm_map_preprocess(int32_t device, const hdsm_map_config* cfg, int32_t n_gr
     return HDSM_ERR_NO_DEVICE;
   }
   const size_t total = (size_t)dim[0] * dim[1] * dim[2] * n_grids;
-  int8_t *d_in = nullptr, *d_out = nullptr;
-  uint8_t* d_scr = nullptr;
-  hipError_t e = hipMalloc(&d_in, total);
-  if (e == hipSuccess) e = hipMalloc(&d_out, total);
-  if (e == hipSuccess) e = hipMalloc(&d_scr, 2 * total);
+  hdsm_mem::DevBuf<int8_t> d_in, d_out;
+  hdsm_mem::DevBuf<uint8_t> d_scr;
+  hdsm_mem::FirstError ok;
+  ok(d_in.alloc(total));
+  if (ok.ok()) ok(d_out.alloc(total));
+  if (ok.ok()) ok(d_scr.alloc(2 * total));
   int rc = HDSM_OK;
-  if (e == hipSuccess) e = hipMemcpy(d_in, grids_in, total, hipMemcpyHostToDevice);
-  if (e == hipSuccess) rc = run_device(cfg, n_grids, dim, d_in, d_out, d_scr, nullptr);
-  if (e == hipSuccess && rc == HDSM_OK) e = hipMemcpy(grids_out, d_out, total, hipMemcpyDeviceToHost);
-  (void)hipFree(d_in), (void)hipFree(d_out), (void)hipFree(d_scr);
-  if (e != hipSuccess) {
-    g_map_err = hipGetErrorString(e);
+  if (ok.ok()) ok(hipMemcpy(d_in.get(), grids_in, total, hipMemcpyHostToDevice));
+  if (ok.ok()) rc = run_device(cfg, n_grids, dim, d_in.get(), d_out.get(), d_scr.get(), nullptr);
+  if (ok.ok() && rc == HDSM_OK) ok(hipMemcpy(grids_out, d_out.get(), total, hipMemcpyDeviceToHost));
+  if (!ok.ok()) {
+    g_map_err = hipGetErrorString(ok.e);
     return HDSM_ERR_DEVICE;
   }
   return rc;
@@ -577,19 +578,19 @@ int hdsm_map_preprocess_region(int32_t device, const hdsm_map_config* cfg, const
     return HDSM_ERR_NO_DEVICE;
   }
   const size_t total = (size_t)dim[0] * dim[1] * dim[2], scr = hdsm_map_region_scratch_bytes(cfg, dim, lo, bdim);
-  int8_t *d_raw = nullptr, *d_out = nullptr;
-  uint8_t* d_scr = nullptr;
-  hipError_t e = hipMalloc(&d_raw, total);
-  if (e == hipSuccess) e = hipMalloc(&d_out, total);
-  if (e == hipSuccess) e = hipMalloc(&d_scr, scr ? scr : 1);
+  hdsm_mem::DevBuf<int8_t> d_raw, d_out;
+  hdsm_mem::DevBuf<uint8_t> d_scr;
+  hdsm_mem::FirstError ok;
+  ok(d_raw.alloc(total));
+  if (ok.ok()) ok(d_out.alloc(total));
+  if (ok.ok()) ok(d_scr.alloc(scr));
   int rc = HDSM_OK;
-  if (e == hipSuccess) e = hipMemcpy(d_raw, raw_full, total, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_out, out_full, total, hipMemcpyHostToDevice);
-  if (e == hipSuccess) rc = run_region(cfg, dim, d_raw, d_out, lo, bdim, d_scr, nullptr);
-  if (e == hipSuccess && rc == HDSM_OK) e = hipMemcpy(out_full, d_out, total, hipMemcpyDeviceToHost);
-  (void)hipFree(d_raw), (void)hipFree(d_out), (void)hipFree(d_scr);
-  if (e != hipSuccess) {
-    g_map_err = hipGetErrorString(e);
+  if (ok.ok()) ok(hipMemcpy(d_raw.get(), raw_full, total, hipMemcpyHostToDevice));
+  if (ok.ok()) ok(hipMemcpy(d_out.get(), out_full, total, hipMemcpyHostToDevice));
+  if (ok.ok()) rc = run_region(cfg, dim, d_raw.get(), d_out.get(), lo, bdim, d_scr.get(), nullptr);
+  if (ok.ok() && rc == HDSM_OK) ok(hipMemcpy(out_full, d_out.get(), total, hipMemcpyDeviceToHost));
+  if (!ok.ok()) {
+    g_map_err = hipGetErrorString(ok.e);
     return HDSM_ERR_DEVICE;
   }
   return rc;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/hdsm_swarm.h"
+#include "hdsm_internal.h"
 #include "path_core.h"
 
 namespace hdsm_path {
@@ -219,7 +220,6 @@ int plan_dmp_serial(const PathIn& in, const DmpMask& mask, V3* out, int* n_out, 
 
 }  // namespace hdsm_path
 
-// the argument checks and the per-case problem of hdsm_local_path_host / hdsm_local_path_batch
 extern "C" int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                                        const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res,
                                        void* problem) {

@@ -5,11 +5,8 @@
 #include <vector>
 
 #include "../../include/hdsm_swarm.h"
+#include "device_mem.h"
 #include "path_core.h"
-
-extern "C" int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
-                                       const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res,
-                                       void* problem);
 
 namespace {
 
@@ -86,43 +83,37 @@ int run_batch(int32_t device, int32_t n, const int8_t* world, const int32_t wdim
   BatchArgs a{};
   a.res = res, a.pmax = pmax;
   for (int ax = 0; ax < 3; ++ax) a.wdim[ax] = world ? wdim[ax] : 0, a.ldim[ax] = ldim[ax];
-  int8_t* d_world = nullptr;
-  int32_t *d_off = nullptr, *d_gk = nullptr, *d_np = nullptr, *d_st = nullptr, *d_cost = nullptr, *d_raw = nullptr;
-  uint32_t* d_rows = nullptr;
-  double *d_org = nullptr, *d_s = nullptr, *d_g = nullptr, *d_paths = nullptr;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t r) {
-    if (e == hipSuccess) e = r;
-  };
+  hdsm_mem::DevBuf<int8_t> d_world;
+  hdsm_mem::DevBuf<int32_t> d_off, d_gk, d_np, d_st, d_cost, d_raw;
+  hdsm_mem::DevBuf<uint32_t> d_rows;
+  hdsm_mem::DevBuf<double> d_org, d_s, d_g, d_paths;
+  hdsm_mem::FirstError ok;
   const size_t N = (size_t)n;
-  if (world) ok(hipMalloc(&d_world, wbytes));
-  ok(hipMalloc(&d_off, N * 12)), ok(hipMalloc(&d_gk, N * 4)), ok(hipMalloc(&d_np, N * 4)), ok(hipMalloc(&d_st, N * 4));
-  ok(hipMalloc(&d_org, N * 24)), ok(hipMalloc(&d_s, N * 24)), ok(hipMalloc(&d_g, N * 24)), ok(hipMalloc(&d_paths, N * pmax * 24));
-  if (mask) ok(hipMalloc(&d_cost, N * 4)), ok(hipMalloc(&d_raw, N * 4)), ok(hipMalloc(&d_rows, sizeof mask->rows));
-  if (e == hipSuccess) {
-    if (world) ok(hipMemcpy(d_world, world, wbytes, hipMemcpyHostToDevice));
-    ok(hipMemcpy(d_off, off, N * 12, hipMemcpyHostToDevice)), ok(hipMemcpy(d_gk, ground_k, N * 4, hipMemcpyHostToDevice));
-    ok(hipMemcpy(d_org, origin, N * 24, hipMemcpyHostToDevice)), ok(hipMemcpy(d_s, start, N * 24, hipMemcpyHostToDevice));
-    ok(hipMemcpy(d_g, goal, N * 24, hipMemcpyHostToDevice));
-    if (mask) ok(hipMemcpy(d_rows, mask->rows, sizeof mask->rows, hipMemcpyHostToDevice));
+  if (world) ok(d_world.alloc(wbytes));
+  ok(d_off.alloc(N * 3)), ok(d_gk.alloc(N)), ok(d_np.alloc(N)), ok(d_st.alloc(N));
+  ok(d_org.alloc(N * 3)), ok(d_s.alloc(N * 3)), ok(d_g.alloc(N * 3)), ok(d_paths.alloc(N * pmax * 3));
+  if (mask) ok(d_cost.alloc(N)), ok(d_raw.alloc(N)), ok(d_rows.alloc(sizeof mask->rows / sizeof mask->rows[0]));
+  if (ok.ok()) {
+    if (world) ok(hipMemcpy(d_world.get(), world, wbytes, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_off.get(), off, N * 12, hipMemcpyHostToDevice)), ok(hipMemcpy(d_gk.get(), ground_k, N * 4, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_org.get(), origin, N * 24, hipMemcpyHostToDevice)), ok(hipMemcpy(d_s.get(), start, N * 24, hipMemcpyHostToDevice));
+    ok(hipMemcpy(d_g.get(), goal, N * 24, hipMemcpyHostToDevice));
+    if (mask) ok(hipMemcpy(d_rows.get(), mask->rows, sizeof mask->rows, hipMemcpyHostToDevice));
   }
-  if (e == hipSuccess) {
-    a.world = d_world, a.off = d_off, a.ground_k = d_gk, a.origin = d_org, a.start = d_s, a.goal = d_g;
-    a.paths = d_paths, a.n_path = d_np, a.status = d_st;
-    if (mask) hipLaunchKernelGGL(k_dmp_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a, mask->rn, d_rows, d_cost, d_raw);
+  if (ok.ok()) {
+    a.world = d_world.get(), a.off = d_off.get(), a.ground_k = d_gk.get(), a.origin = d_org.get(), a.start = d_s.get(), a.goal = d_g.get();
+    a.paths = d_paths.get(), a.n_path = d_np.get(), a.status = d_st.get();
+    if (mask) hipLaunchKernelGGL(k_dmp_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a, mask->rn, d_rows.get(), d_cost.get(), d_raw.get());
     else hipLaunchKernelGGL(k_path_batch, dim3((unsigned)n), dim3(hdsm_path::THREADS), 0, 0, a);
     ok(hipGetLastError());
     ok(hipDeviceSynchronize());
   }
-  if (e == hipSuccess) {
-    ok(hipMemcpy(paths, d_paths, N * pmax * 24, hipMemcpyDeviceToHost));
-    ok(hipMemcpy(n_path, d_np, N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(status, d_st, N * 4, hipMemcpyDeviceToHost));
-    if (mask) ok(hipMemcpy(cost, d_cost, N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(n_raw, d_raw, N * 4, hipMemcpyDeviceToHost));
+  if (ok.ok()) {
+    ok(hipMemcpy(paths, d_paths.get(), N * pmax * 24, hipMemcpyDeviceToHost));
+    ok(hipMemcpy(n_path, d_np.get(), N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(status, d_st.get(), N * 4, hipMemcpyDeviceToHost));
+    if (mask) ok(hipMemcpy(cost, d_cost.get(), N * 4, hipMemcpyDeviceToHost)), ok(hipMemcpy(n_raw, d_raw.get(), N * 4, hipMemcpyDeviceToHost));
   }
-  void* ptrs[] = {d_world, d_off, d_gk, d_np, d_st, d_org, d_s, d_g, d_paths, d_cost, d_raw, d_rows};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  return e == hipSuccess ? HDSM_OK : HDSM_ERR_DEVICE;
+  return ok.ok() ? HDSM_OK : HDSM_ERR_DEVICE;
 }
 
 }  // namespace

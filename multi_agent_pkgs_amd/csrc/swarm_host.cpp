@@ -19,6 +19,7 @@
 #include "../../include/hdsm_stats.h"
 #include "../../include/hdsm_swarm.h"
 #include "audit_core.h"
+#include "hdsm_internal.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -786,7 +787,6 @@ int hdsm_swarm_flight_report(void* swarm, hdsm_flight_report* report) {
   return HDSM_OK;
 }
 
-// the audit's setting and record in and out of the device-resident loop (report [n_local], may be NULL)
 int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw || !on || !ever || !sep_warn) return HDSM_ERR_BAD_ARG;
@@ -816,7 +816,7 @@ int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows)
   return HDSM_OK;
 }
 
-// ---- hooks of the device-resident loop (swarm_kernels.hip): the plain agent states and the configuration of a shard ----
+// ---- hooks of the device-resident loop (swarm_kernels.hip; declared and described in hdsm_internal.h) ----
 int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id, hdsm_params* prm,
                             hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3], double worigin[3]) {
   Swarm* sw = static_cast<Swarm*>(swarm);
@@ -842,8 +842,7 @@ int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local)
   return HDSM_OK;
 }
 
-// the path step's round phase and pending agents (and the goals of a device loop set between its rounds), in and out of the
-// device-resident loop: the mirror and the device count rounds the same way. due / goals: [n_local] / [n_local][3], may be NULL.
+// (the mirror and the device count rounds the same way; due / goals: [n_local] / [n_local][3])
 int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw) return HDSM_ERR_BAD_ARG;
@@ -854,7 +853,6 @@ int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, u
   return HDSM_OK;
 }
 
-// the clearance radius of the path step (0: off), for the device-resident loop
 int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw || !search_rad) return HDSM_ERR_BAD_ARG;

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdlib>
+#include <memory>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -23,12 +24,10 @@
 #include "../../include/hdsm.h"
 #include "../../include/hdsm_swarm.h"
 #include "audit_device.h"
+#include "device_mem.h"
+#include "hdsm_internal.h"
 #include "path_core.h"
 #include "swarm_core.h"
-
-// (csrc/hdsm_api.hip, internal: see hdsm_dswarm_round)
-extern "C" int hdsm_internal_defer_done(void* handle, int on);
-extern "C" int hdsm_internal_record_done(void* handle, void* hip_stream);
 
 #ifdef CD_PROFILE
 // development builds only: the phase counters of the corridor kernel's decompositions (read and cleared); [12] cycles of the whole
@@ -42,17 +41,6 @@ extern "C" int hdsm_swarm_corridor_profile(unsigned long long out[16]) {
   return HDSM_OK;
 }
 #endif
-
-extern "C" int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id,
-                                       hdsm_params* prm, hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3],
-                                       double worigin[3]);
-extern "C" int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local);
-extern "C" int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
-extern "C" int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
-extern "C" int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
-extern "C" int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report);
-extern "C" int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report);
-extern "C" int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows);
 
 namespace {
 
@@ -576,13 +564,6 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t
     for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.p.out[t / 3][t % 3];
 }
 
-__global__ __launch_bounds__(256) void k_flags(int rec, int n, const double* plans, uint8_t* has) {
-  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k >= n) return;
-  const double v = plans[(size_t)k * rec];
-  has[k] = (v == v) ? 1 : 0;
-}
-
 // ---- map updates in flight (ABI 1.7) ----
 // values [bdim[2]][bdim[1]][bdim[0]] into the box lo .. lo + bdim of a grid [.][ny][nx]: thread <-> up to four voxels of one row
 __global__ __launch_bounds__(256) void k_box_put(const int8_t* __restrict__ vals, int8_t* __restrict__ grid, int nx, int ny, int lx, int ly, int lz,
@@ -618,6 +599,55 @@ __global__ __launch_bounds__(256) void k_cache_invalidate(PolyCache* cache, int 
   atomicAdd(dropped, 1ull);
 }
 
+using hdsm_mem::DevBuf;
+
+// the path step (k_path): period and round phase of the host mirror, the agents due at the next round (hdsm_dswarm_set_goals) and
+// their list on the device, every agent's goal (host copy + device), counters [planned, failed], launches, the timed interval
+struct PathStep {
+  int period = 0;
+  long long round = 0, launches = 0;
+  std::vector<uint8_t> due;
+  std::vector<double> goals;
+  int n_due = 0;
+  DevBuf<int32_t> d_due;
+  DevBuf<double> d_goals;
+  DevBuf<unsigned long long> d_cnt;
+  hdsm_mem::TimedInterval timed;
+  // the clearance mode (hdsm_swarm_set_path_clearance before hdsm_dswarm_create): k_dmp instead of k_path, the mask's rows on the device
+  bool dmp = false;
+  int dmp_rn = 0;
+  DevBuf<uint32_t> d_dmp_rows;
+};
+
+// the flight audit (audit_kernels.hip; opt-in: nothing is allocated or launched while it and the history are off)
+struct Audit {
+  bool on = false, ever = false;
+  long long rounds = 0;  // rounds audited by this dswarm (hdsm_dswarm_last_audit_round needs one)
+  double sep_warn = 1.0;
+  hdsm_audit::DeviceBufs buf;
+  DevBuf<hdsm_flight_report> d_report;
+  hdsm_mem::TimedInterval timed;  // the audit's launches of a round, the history write included
+};
+
+// the state history (opt-in, written by the audit's last kernel): rows [cap][n_local][9]
+struct History {
+  DevBuf<double> d_rows;
+  int cap = 0, n = 0, dropped = 0, delivered = 0;
+};
+
+// map updates in flight (nothing is allocated or launched before the first hdsm_dswarm_update_world* / _set_raw_world): the
+// resident raw grid with the map configuration and the scratch of the region pre-processing, the staging buffer of the
+// host-pointer forms, updates applied, voxels written, and the device's count of cache entries dropped
+struct WorldEdits {
+  DevBuf<int8_t> d_raw;
+  DevBuf<uint8_t> d_map_scr;
+  hdsm_map_config mcfg{};
+  DevBuf<int8_t> d_edit;
+  size_t edit_cap = 0;
+  long long updates = 0, voxels = 0;
+  DevBuf<unsigned long long> d_dropped;
+};
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -625,98 +655,49 @@ struct DSwarm {
   hdsm_swarm_config cfg{};
   hdsm_ref_config rcfg{};
   Cfg c{};
-  AgentS* d_agents = nullptr;
-  PolyCache* d_cache = nullptr;  // [n_local], worlds only (HDSM_POLY_CACHE=0: none)
-  int8_t* d_world = nullptr;
-  double *d_cap = nullptr, *d_path = nullptr, *d_ref_full = nullptr, *d_ref = nullptr, *d_pv = nullptr, *d_state = nullptr, *d_A = nullptr, *d_b = nullptr,
-         *d_traj = nullptr, *d_ctrl = nullptr, *d_obj = nullptr, *d_local = nullptr, *d_plans = nullptr;
-  int32_t *d_npath = nullptr, *d_id = nullptr, *d_npoly = nullptr, *d_nrows = nullptr, *d_status = nullptr, *d_fails = nullptr;
-  uint8_t *d_used = nullptr, *d_has = nullptr;
+  DevBuf<AgentS> d_agents;
+  DevBuf<PolyCache> d_cache;  // [n_local], worlds only (HDSM_POLY_CACHE=0: none)
+  DevBuf<int8_t> d_world;
+  DevBuf<double> d_cap, d_path, d_ref_full, d_ref, d_pv, d_state, d_A, d_b, d_traj, d_ctrl, d_obj, d_local, d_plans;
+  DevBuf<int32_t> d_npath, d_id, d_npoly, d_nrows, d_status, d_fails;
+  DevBuf<uint8_t> d_used, d_has;
   long long rounds = 0;
   // hdsm_dswarm_set_phase_timing: HIP events between the launches of a round (development / bench aid: every record is a barrier
   // packet in front of the next kernel, so a timed round is a few us longer than a plain one — ms_per_round is never taken from it)
   bool phase_timing = false, phase_valid = false;
-  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // the path step (k_path): period and round phase of the host mirror, the agents due at the next round (hdsm_dswarm_set_goals) and
-  // their list on the device, every agent's goal (host copy + device), counters [planned, failed], launches, the timed interval
-  int path_period = 0;
-  long long path_round = 0, path_launches = 0;
-  std::vector<uint8_t> due;
-  std::vector<double> goals;
-  int n_due = 0;
-  int32_t* d_due = nullptr;
-  double* d_goals = nullptr;
-  unsigned long long* d_path_cnt = nullptr;
-  bool path_valid = false;
-  hipEvent_t path_ev[2] = {nullptr, nullptr};
-  // the clearance mode (hdsm_swarm_set_path_clearance before hdsm_dswarm_create): k_dmp instead of k_path, the mask's rows on the device
-  bool dmp = false;
-  int dmp_rn = 0;
-  uint32_t* d_dmp_rows = nullptr;
-  // the flight audit and the state history (audit_kernels.hip; both opt-in: nothing below is allocated or launched while they are off)
-  bool audit_on = false, audit_ever = false, audit_valid = false;
-  long long audit_rounds = 0;  // rounds audited by this dswarm (hdsm_dswarm_last_audit_round needs one)
-  double sep_warn = 1.0;
-  hdsm_audit::DeviceBufs abuf;
-  hdsm_flight_report* d_report = nullptr;
-  hipEvent_t audit_ev[2] = {nullptr, nullptr};
-  double* d_hist = nullptr;
-  int hist_cap = 0, hist_n = 0, hist_dropped = 0, hist_delivered = 0;
-  // map updates in flight (nothing below is allocated or launched before the first hdsm_dswarm_update_world* / _set_raw_world): the
-  // resident raw grid with the map configuration and the scratch of the region pre-processing, the staging buffer of the
-  // host-pointer forms, updates applied, voxels written, and the device's count of cache entries dropped
-  int8_t* d_raw = nullptr;
-  uint8_t* d_map_scr = nullptr;
-  hdsm_map_config mcfg{};
-  int8_t* d_edit = nullptr;
-  size_t edit_cap = 0;
-  long long world_updates = 0, world_voxels = 0;
-  unsigned long long* d_dropped = nullptr;
+  hdsm_mem::DevEvent ev[8];
+  PathStep path;
+  Audit audit;
+  History hist;
+  WorldEdits edits;
 };
+
+// every event a timed round records (hdsm_dswarm_set_phase_timing; _set_audit and _set_history when the timing is already on)
+int timing_events(DSwarm* d) {
+  for (hdsm_mem::DevEvent& e : d->ev) HIP_TRY(e.create());
+  HIP_TRY(d->path.timed.create());
+  HIP_TRY(d->audit.timed.create());
+  return HDSM_OK;
+}
 
 // the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports
 int audit_setup(DSwarm* d, const hdsm_flight_report* init) {
-  if (d->abuf.d_round == nullptr) {
-    if (hdsm_audit::device_alloc(&d->abuf, d->per * d->world, d->n_local, d->c.step_plan) != hipSuccess)
+  Audit& a = d->audit;
+  if (!a.buf.d_round) {
+    if (hdsm_audit::device_alloc(&a.buf, d->per * d->world, d->n_local, d->c.step_plan) != hipSuccess)
       return fail(HDSM_ERR_DEVICE, "flight audit: allocation failed");
   }
-  if (d->d_report == nullptr && (init != nullptr || d->audit_on)) {
+  if (!a.d_report && (init != nullptr || a.on)) {
     std::vector<hdsm_flight_report> rep((size_t)d->n_local);
     for (int k = 0; k < d->n_local; ++k) {
       if (init) rep[k] = init[k];
       else hdsm_audit::empty_report(&rep[k]);
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_report), (rep.size() + 1) * sizeof(hdsm_flight_report)));
-    if (!rep.empty()) HIP_TRY(hipMemcpy(d->d_report, rep.data(), rep.size() * sizeof(hdsm_flight_report), hipMemcpyHostToDevice));
-    d->audit_ever = true;
+    HIP_TRY(a.d_report.alloc(rep.size() + 1));
+    if (!rep.empty()) HIP_TRY(hipMemcpy(a.d_report.get(), rep.data(), rep.size() * sizeof(hdsm_flight_report), hipMemcpyHostToDevice));
+    a.ever = true;
   }
   return HDSM_OK;
-}
-
-template <class T>
-hipError_t dalloc(T** p, size_t count) {
-  hipError_t e = hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T));
-  if (e == hipSuccess) e = hipMemset(*p, 0, (count ? count : 1) * sizeof(T));
-  return e;
-}
-
-void free_all(DSwarm* d) {
-  void* ptrs[] = {d->d_cap, d->d_agents, d->d_cache, d->d_world, d->d_path, d->d_ref_full, d->d_ref, d->d_pv, d->d_state, d->d_A, d->d_b, d->d_traj,
-                  d->d_ctrl, d->d_obj, d->d_local, d->d_plans, d->d_npath, d->d_id, d->d_npoly, d->d_nrows, d->d_status, d->d_fails,
-                  d->d_used, d->d_has, d->d_due, d->d_goals, d->d_path_cnt, d->d_dmp_rows};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (hipEvent_t e : d->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : d->path_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : d->audit_ev)
-    if (e) (void)hipEventDestroy(e);
-  hdsm_audit::device_free(&d->abuf);
-  if (d->d_report) (void)hipFree(d->d_report);
-  if (d->d_hist) (void)hipFree(d->d_hist);
-  for (void* p : {static_cast<void*>(d->d_raw), static_cast<void*>(d->d_map_scr), static_cast<void*>(d->d_edit), static_cast<void*>(d->d_dropped)})
-    if (p) (void)hipFree(p);
 }
 
 // the box lo .. lo + bdim inside the device world? (0 empty, 1 yes, < 0 an error)
@@ -740,28 +721,226 @@ int put_box(DSwarm* d, const int8_t* d_vals, int8_t* grid, const int32_t lo[3], 
 
 // drops the cache entries that could have looked at the written voxels wlo .. wlo + wdim (NULL: every entry), on st, and books the update
 int invalidate(DSwarm* d, const int32_t* wlo, const int32_t* wdim, hipStream_t st) {
-  if (!d->d_dropped) HIP_TRY(dalloc(&d->d_dropped, 1));
+  if (!d->edits.d_dropped) HIP_TRY(d->edits.d_dropped.alloc_zeroed(1));
   if (!d->d_cache || d->n_local == 0) return HDSM_OK;
   const int rad = hdsm_cd::wave_map_radius(d->c.n_it_decomp) + 1;
   const int big = 1 << 29;
   const int l[3] = {wlo ? wlo[0] : -big, wlo ? wlo[1] : -big, wlo ? wlo[2] : -big};
   const int h[3] = {wlo ? wlo[0] + wdim[0] - 1 : big, wlo ? wlo[1] + wdim[1] - 1 : big, wlo ? wlo[2] + wdim[2] - 1 : big};
-  hipLaunchKernelGGL(k_cache_invalidate, dim3((unsigned)((d->n_local * CACHE_POLYS + 255) / 256)), dim3(256), 0, st, d->d_cache, d->n_local, rad, l[0], l[1],
-                     l[2], h[0], h[1], h[2], d->d_dropped);
+  hipLaunchKernelGGL(k_cache_invalidate, dim3((unsigned)((d->n_local * CACHE_POLYS + 255) / 256)), dim3(256), 0, st, d->d_cache.get(), d->n_local, rad, l[0],
+                     l[1], l[2], h[0], h[1], h[2], d->edits.d_dropped.get());
   HIP_TRY(hipGetLastError());
   return HDSM_OK;
 }
 
 // the host values of a box into the staging buffer (the device is idle: the callers have synchronised)
 int stage_box(DSwarm* d, const int8_t* values, const int32_t bdim[3]) {
+  WorldEdits& w = d->edits;
   const size_t bytes = (size_t)bdim[0] * bdim[1] * bdim[2];
-  if (bytes > d->edit_cap) {
-    if (d->d_edit) (void)hipFree(d->d_edit);
-    d->d_edit = nullptr, d->edit_cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_edit), bytes));
-    d->edit_cap = bytes;
+  if (bytes > w.edit_cap) {
+    w.edit_cap = 0;
+    HIP_TRY(w.d_edit.alloc(bytes));
+    w.edit_cap = bytes;
   }
-  HIP_TRY(hipMemcpy(d->d_edit, values, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(w.d_edit.get(), values, bytes, hipMemcpyHostToDevice));
+  return HDSM_OK;
+}
+
+// every buffer a round of n_local agents in a world of hworld's size needs, zero-filled
+hipError_t alloc_round_buffers(DSwarm* d, const int8_t* hworld) {
+  const Cfg& c = d->c;
+  const size_t n = (size_t)d->n_local, L = (size_t)d->per, G = (size_t)d->per * d->world, N = (size_t)c.N, P = (size_t)c.P, RS = (size_t)c.RS,
+               REC = (N + 1) * 9;
+  hdsm_mem::FirstError ok;
+  ok(d->d_agents.alloc_zeroed(n));
+  if (hworld) {
+    ok(d->d_world.alloc_zeroed((size_t)c.wdim[0] * c.wdim[1] * c.wdim[2]));
+    bool cache_on = true;  // development switch (A/B): HDSM_POLY_CACHE=0 grows every polyhedron again
+    if (const char* pcenv = std::getenv("HDSM_POLY_CACHE")) cache_on = !(pcenv[0] == '0' && pcenv[1] == 0);
+    if (cache_on) ok(d->d_cache.alloc_zeroed(n));
+  }
+  ok(d->d_path.alloc_zeroed(n * PTS * 3)), ok(d->d_npath.alloc_zeroed(n)), ok(d->d_ref_full.alloc_zeroed(n * (N + 1) * 6));
+  ok(d->d_ref.alloc_zeroed(n * N * 6)), ok(d->d_cap.alloc_zeroed(n)), ok(d->d_pv.alloc_zeroed(n)), ok(d->d_id.alloc_zeroed(n));
+  ok(d->d_state.alloc_zeroed(n * 9)), ok(d->d_npoly.alloc_zeroed(n)), ok(d->d_nrows.alloc_zeroed(n * P));
+  ok(d->d_A.alloc_zeroed(n * P * RS * 3)), ok(d->d_b.alloc_zeroed(n * P * RS)), ok(d->d_traj.alloc_zeroed(L * REC));
+  ok(d->d_ctrl.alloc_zeroed(L * N * 3)), ok(d->d_obj.alloc_zeroed(L)), ok(d->d_used.alloc_zeroed(L * P)), ok(d->d_status.alloc_zeroed(L));
+  ok(d->d_local.alloc_zeroed(L * REC)), ok(d->d_plans.alloc_zeroed(G * REC)), ok(d->d_has.alloc_zeroed(G)), ok(d->d_fails.alloc_zeroed(1));
+  ok(d->path.d_due.alloc_zeroed(n)), ok(d->path.d_goals.alloc_zeroed(n * 3)), ok(d->path.d_cnt.alloc_zeroed(2));
+  return ok.e;
+}
+
+// The mirror's flight becomes the device's (hdsm_dswarm_create, after alloc_round_buffers): the path step's phase and pending agents,
+// the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the audit's setting and record.
+int take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
+  const size_t n = (size_t)d.n_local;
+  PathStep& p = d.path;
+  const auto refused = [](int rc) { return fail(rc, "hdsm_dswarm_create: export failed"); };
+  p.due.assign(n, 0), p.goals.assign(n * 3, 0.0);
+  int32_t period = 0;
+  int64_t round = 0;
+  if (int rc = hdsm_swarm_export_path_state(swarm, &period, &round, p.due.data())) return refused(rc);
+  p.period = period, p.round = round;
+  double rad = 0;
+  if (int rc = hdsm_swarm_export_path_clearance(swarm, &rad)) return refused(rc);
+  if (rad != 0) {
+    hdsm_path::DmpMask mask{};
+    if (!hdsm_path::dmp_build_mask(rad, d.cfg.voxel_size, &mask)) return refused(HDSM_ERR_BAD_ARG);
+    p.dmp = true, p.dmp_rn = mask.rn;
+    HIP_TRY(p.d_dmp_rows.alloc_zeroed(sizeof mask.rows / sizeof mask.rows[0]));
+    HIP_TRY(hipMemcpy(p.d_dmp_rows.get(), mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
+  }
+  if (n) {
+    std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
+    if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
+    if (int rc = hdsm_swarm_export_state(swarm, tmp.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return refused(rc);
+    HIP_TRY(hipMemcpy(d.d_agents.get(), tmp.get(), n * sizeof(AgentS), hipMemcpyHostToDevice));
+    // the agent ids of the shard (a contiguous block), the goals, and the agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
+    std::vector<int32_t> ids(n, 0), idx;
+    for (size_t k = 0; k < n; ++k) {
+      for (int q = 0; q < 3; ++q) p.goals[3 * k + q] = tmp[k].goal[q];
+      ids[k] = d.first + (int)k;
+      if (p.due[k]) idx.push_back((int32_t)k);
+    }
+    p.n_due = (int)idx.size();
+    HIP_TRY(hipMemcpy(d.d_id.get(), ids.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  if (hworld) HIP_TRY(hipMemcpy(d.d_world.get(), hworld, (size_t)d.c.wdim[0] * d.c.wdim[1] * d.c.wdim[2], hipMemcpyHostToDevice));
+  d.c.world = d.d_world.get();
+  int32_t on = 0, ever = 0;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
+  if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, nullptr)) return refused(rc);
+  if (ever) {
+    std::vector<hdsm_flight_report> rep(n);
+    if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, rep.data())) return refused(rc);
+    d.audit.on = on != 0;
+    if (int rc = audit_setup(&d, rep.data())) return rc;
+  }
+  return HDSM_OK;
+}
+
+// The device's flight back into the mirror (hdsm_dswarm_download; the device is idle): the agent states, the path step's phase,
+// pending agents and goals, the audit's setting and record.
+int hand_back(DSwarm& d, void* swarm) {
+  const size_t n = (size_t)d.n_local;
+  std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
+  if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
+  int rc = hipMemcpy(tmp.get(), d.d_agents.get(), n * sizeof(AgentS), hipMemcpyDeviceToHost) == hipSuccess
+               ? hdsm_swarm_import_state(swarm, tmp.get(), d.n_local)
+               : HDSM_ERR_DEVICE;
+  if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d.path.period, d.path.round, d.path.due.data(), d.path.goals.data());
+  if (rc == HDSM_OK && d.audit.ever) {
+    std::vector<hdsm_flight_report> rep(n);
+    if (hipMemcpy(rep.data(), d.audit.d_report.get(), n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
+    else rc = hdsm_swarm_import_audit(swarm, d.audit.on ? 1 : 0, d.audit.sep_warn, rep.data());
+  }
+  return rc ? fail(rc, "state download failed") : HDSM_OK;
+}
+
+// ---- the phases of hdsm_dswarm_round, in the order of the header comment; every one issues on st and returns at its first error ----
+#define PHASE_MARK(k) \
+  do {                \
+    if (d.phase_timing) HIP_TRY(hipEventRecord(d.ev[k].get(), st)); \
+  } while (0)
+
+// the path step (UpdatePath, AC:261-454) at the start of the round, before the corridor: every agent in rounds of the period,
+// else the agents whose goal changed; no launch when nobody is due
+int path_step(DSwarm& d, hipStream_t st) {
+  PathStep& p = d.path;
+  const bool all = p.period > 0 && p.round % p.period == 0;
+  const int n_plan = all ? d.n_local : p.n_due;
+  p.timed.valid = false;
+  if (n_plan > 0) {
+    if (d.phase_timing) HIP_TRY(p.timed.record_start(st));
+    if (p.dmp)
+      hipLaunchKernelGGL(k_dmp, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d.c, all ? nullptr : p.d_due.get(), d.d_agents.get(),
+                         p.d_goals.get(), p.d_cnt.get(), p.dmp_rn, p.d_dmp_rows.get());
+    else
+      hipLaunchKernelGGL(k_path, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d.c, all ? nullptr : p.d_due.get(), d.d_agents.get(),
+                         p.d_goals.get(), p.d_cnt.get());
+    HIP_TRY(hipGetLastError());
+    if (d.phase_timing) HIP_TRY(p.timed.record_stop(st));
+    ++p.launches;
+  }
+  p.n_due = 0;
+  std::fill(p.due.begin(), p.due.end(), (uint8_t)0);
+  ++p.round;
+  return HDSM_OK;
+}
+
+// k_corridor, k_vel_cap, the reference, k_keep_free and the solve (marks 0 to 4)
+int corridor_to_solve(DSwarm& d, hipStream_t st) {
+  const int n = d.n_local, G = d.per * d.world;
+  PHASE_MARK(0);
+  if (n == 0) {
+    for (int k = 1; k <= 4; ++k) PHASE_MARK(k);
+    return HDSM_OK;
+  }
+  hipLaunchKernelGGL(k_corridor, dim3((unsigned)n), dim3(64), d.c.has_world ? hdsm_cd::wave_lds_bytes(hdsm_cd::wave_map_radius(d.c.n_it_decomp)) : 0, st, d.c,
+                     n, d.d_agents.get(), d.d_path.get(), d.d_npath.get(), d.d_id.get(), d.d_state.get(), d.d_npoly.get(), d.d_nrows.get(), d.d_A.get(),
+                     d.d_b.get(), d.d_cache.get());
+  HIP_TRY(hipGetLastError());
+  PHASE_MARK(1);
+  if (d.c.has_world) {
+    hipLaunchKernelGGL(k_vel_cap, dim3((unsigned)n), dim3(64), 0, st, d.c, d.rcfg, n, d.d_agents.get(), d.d_path.get(), d.d_npath.get(), d.d_cap.get());
+    HIP_TRY(hipGetLastError());
+  }
+  PHASE_MARK(2);
+  int rc = hdsm_reference_device(d.solver, &d.rcfg, n, G, d.d_id.get(), d.d_path.get(), d.d_npath.get(), PTS, d.c.has_world ? d.d_cap.get() : nullptr,
+                                 d.d_plans.get(), d.d_has.get(), d.d_ref_full.get(), d.d_ref.get(), d.d_pv.get(), st);
+  if (rc) return fail(rc, std::string("hdsm_reference_device: ") + hdsm_last_error());
+  PHASE_MARK(3);
+  if (d.c.has_world) {
+    hipLaunchKernelGGL(k_keep_free, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, d.c, n, d.d_agents.get(), d.d_ref_full.get(), d.d_ref.get(),
+                       d.d_pv.get());
+    HIP_TRY(hipGetLastError());
+  }
+  PHASE_MARK(4);
+  rc = hdsm_replan_device(d.solver, n, G, d.d_id.get(), d.d_state.get(), d.d_ref.get(), d.d_npoly.get(), d.d_nrows.get(), d.d_A.get(), d.d_b.get(),
+                          d.d_plans.get(), d.d_has.get(), d.d_traj.get(), d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), d.d_obj.get(), st);
+  if (rc) return fail(rc, std::string("hdsm_replan_device: ") + hdsm_last_error());
+  return HDSM_OK;
+}
+
+// k_commit and the exchange (marks 5 to 7). One rank: the solve of this round is behind us on the stream, so the records go
+// straight into the plans buffer — slot k = agent k — and the flags with them; several ranks: into the send buffer of the ONE all-gather
+int commit_and_exchange(DSwarm& d, void* comm, hipStream_t st) {
+  PHASE_MARK(5);
+  const bool direct = d.world == 1;
+  hipLaunchKernelGGL(k_commit, dim3((unsigned)(d.per > 0 ? d.per : 1)), dim3(64), 0, st, d.c, d.n_local, d.per, d.d_agents.get(), d.d_traj.get(),
+                     d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), direct ? d.d_plans.get() : d.d_local.get(), d.d_fails.get(),
+                     direct ? d.d_has.get() : nullptr, d.d_ref_full.get(), d.d_pv.get());
+  HIP_TRY(hipGetLastError());
+  PHASE_MARK(6);
+  if (!direct) {
+    const int rc = hdsm_exchange_device(comm, d.per, d.d_local.get(), d.d_plans.get(), d.d_has.get(), st);
+    if (rc) return fail(rc, std::string("hdsm_exchange_device: ") + hdsm_last_error());
+  }
+  PHASE_MARK(7);
+  return HDSM_OK;
+}
+#undef PHASE_MARK
+
+// the flight audit and the history row, on this round's records of all agents (only when one of them is on)
+int audit_and_history(DSwarm& d, hipStream_t st) {
+  Audit& a = d.audit;
+  History& h = d.hist;
+  const int n = d.n_local;
+  a.timed.valid = false;
+  if (h.cap > 0 && h.n == h.cap) ++h.dropped;
+  const bool hist = h.cap > 0 && h.n < h.cap;
+  if ((a.on || hist) && n > 0) {
+    if (d.phase_timing) HIP_TRY(a.timed.record_start(st));
+    hdsm_audit::World wd{};
+    wd.world = d.c.has_world ? d.d_world.get() : nullptr, wd.voxel_size = d.c.voxel_size;
+    for (int k = 0; k < 3; ++k) wd.wdim[k] = d.c.wdim[k], wd.worigin[k] = d.c.worigin[k];
+    HIP_TRY(hdsm_audit::launch(a.buf, a.on, d.d_plans.get(), d.d_has.get(), d.c.N, d.first, hdsm_audit::weights(d.prm.drone_radius, d.prm.drone_z_offset),
+                               wd, a.d_report.get(), a.sep_warn * a.sep_warn, &d.d_agents.get()[0].state_curr[0], sizeof(AgentS),
+                               hist ? h.d_rows.get() + (size_t)h.n * n * 9 : nullptr, st));
+    if (d.phase_timing) HIP_TRY(a.timed.record_stop(st));
+    if (a.on) ++a.rounds;
+  }
+  if (hist) ++h.n;
   return HDSM_OK;
 }
 
@@ -779,15 +958,9 @@ int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   HIP_TRY(hipSetDevice(d->device));
-  if (on) {
-    for (hipEvent_t& e : d->ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    for (hipEvent_t& e : d->path_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-    for (hipEvent_t& e : d->audit_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-  }
-  d->phase_timing = on != 0, d->phase_valid = false, d->path_valid = false, d->audit_valid = false;
+  if (on)
+    if (int rc = timing_events(d)) return rc;
+  d->phase_timing = on != 0, d->phase_valid = false, d->path.timed.valid = false, d->audit.timed.valid = false;
   return HDSM_OK;
 }
 
@@ -804,8 +977,8 @@ int hdsm_dswarm_cache_stats(void* dswarm, int64_t out[4]) {
   out[3] = 1;
   // (only the four counters of every entry travel: one strided 2-D copy)
   std::vector<int32_t> cnt((size_t)d->n_local * 4);
-  HIP_TRY(hipMemcpy2D(cnt.data(), 16, reinterpret_cast<const char*>(d->d_cache) + offsetof(PolyCache, asked), sizeof(PolyCache), 16, (size_t)d->n_local,
-                      hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy2D(cnt.data(), 16, reinterpret_cast<const char*>(d->d_cache.get()) + offsetof(PolyCache, asked), sizeof(PolyCache), 16,
+                      (size_t)d->n_local, hipMemcpyDeviceToHost));
   for (int k = 0; k < d->n_local; ++k) out[0] += cnt[4 * (size_t)k], out[1] += cnt[4 * (size_t)k + 1], out[2] += cnt[4 * (size_t)k + 2];
   return HDSM_OK;
 }
@@ -815,8 +988,8 @@ int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]) {
   if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
   if (!d->phase_valid) return fail(HDSM_ERR_BAD_ARG, "no round has run with hdsm_dswarm_set_phase_timing on");
   HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipEventSynchronize(d->ev[7]));
-  for (int k = 0; k < 7; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], d->ev[k], d->ev[k + 1]));
+  HIP_TRY(hipEventSynchronize(d->ev[7].get()));
+  for (int k = 0; k < 7; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], d->ev[k].get(), d->ev[k + 1].get()));
   return HDSM_OK;
 }
 
@@ -827,10 +1000,9 @@ int hdsm_dswarm_last_path_ms(void* dswarm, float* ms) {
   if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
   if (!d->phase_valid) return fail(HDSM_ERR_BAD_ARG, "no round has run with hdsm_dswarm_set_phase_timing on");
   *ms = 0.0f;
-  if (!d->path_valid) return HDSM_OK;
+  if (!d->path.timed.valid) return HDSM_OK;
   HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipEventSynchronize(d->path_ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms, d->path_ev[0], d->path_ev[1]));
+  HIP_TRY(d->path.timed.ms(ms));
   return HDSM_OK;
 }
 
@@ -842,19 +1014,20 @@ int hdsm_dswarm_set_goals(void* dswarm, const double* goals) {
   if (d->n_local == 0) return HDSM_OK;
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
+  PathStep& p = d->path;
   for (int k = 0; k < d->n_local; ++k) {
-    double* g = &d->goals[3 * (size_t)k];
+    double* g = &p.goals[3 * (size_t)k];
     const double* ng = goals + 3 * (size_t)k;
     if (g[0] == ng[0] && g[1] == ng[1] && g[2] == ng[2]) continue;
     g[0] = ng[0], g[1] = ng[1], g[2] = ng[2];
-    d->due[k] = 1;
+    p.due[k] = 1;
   }
   std::vector<int32_t> idx;
   for (int k = 0; k < d->n_local; ++k)
-    if (d->due[k]) idx.push_back(k);
-  d->n_due = (int)idx.size();
-  HIP_TRY(hipMemcpy(d->d_goals, d->goals.data(), d->goals.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (d->n_due) HIP_TRY(hipMemcpy(d->d_due, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (p.due[k]) idx.push_back(k);
+  p.n_due = (int)idx.size();
+  HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), p.goals.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   return HDSM_OK;
 }
 
@@ -866,30 +1039,24 @@ int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]) {
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long cnt[2] = {0, 0};
-  HIP_TRY(hipMemcpy(cnt, d->d_path_cnt, sizeof cnt, hipMemcpyDeviceToHost));
-  out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path_launches;
+  HIP_TRY(hipMemcpy(cnt, d->path.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
+  out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path.launches;
   return HDSM_OK;
 }
 
 int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_size, void** dswarm) {
   if (!swarm || !solver || !dswarm || world_size < 1) return fail(HDSM_ERR_BAD_ARG, "null argument");
   *dswarm = nullptr;
-  DSwarm* d = new (std::nothrow) DSwarm;
+  std::unique_ptr<DSwarm> d(new (std::nothrow) DSwarm);
   if (!d) return fail(HDSM_ERR_DEVICE, "out of host memory");
   d->solver = solver, d->device = device, d->world = world_size;
   const int8_t* hworld = nullptr;
   int32_t wdim[3] = {0, 0, 0};
   double worigin[3] = {0, 0, 0};
-  int rc = hdsm_swarm_export_state(swarm, nullptr, &d->n_local, &d->n_rob, &d->first, &d->prm, &d->cfg, &hworld, wdim, worigin);
-  if (rc) {
-    delete d;
+  if (int rc = hdsm_swarm_export_state(swarm, nullptr, &d->n_local, &d->n_rob, &d->first, &d->prm, &d->cfg, &hworld, wdim, worigin))
     return fail(rc, "hdsm_swarm_export_state");
-  }
   d->per = (d->n_rob + world_size - 1) / world_size;
-  if (d->n_local > d->per) {
-    delete d;
-    return fail(HDSM_ERR_BAD_ARG, "the shard is larger than ceil(n_rob / world_size)");
-  }
+  if (d->n_local > d->per) return fail(HDSM_ERR_BAD_ARG, "the shard is larger than ceil(n_rob / world_size)");
   // Layout contract of the device loop (hdsm_swarm.h): the plans buffer holds agent a's record at slot a — the all-gather puts
   // rank r's block at r * per, a single rank copies its block to slot 0 — and the solver finds an agent's OWN plan (and skips
   // its own record in the sweeps) by agent id. So the shard must be the block of a rank of the ceil(n_rob / world_size) split.
@@ -897,11 +1064,9 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
   // produces — is a valid block; its rank comes from the communicator, not from first_id / per.)
   const bool empty_tail = d->n_local == 0 && d->first == d->n_rob;
   if (d->per > 0 && !empty_tail &&
-      (d->first % d->per != 0 || (d->n_local < d->per && d->first + d->n_local != d->n_rob) || (world_size == 1 && d->first != 0))) {
-    delete d;
+      (d->first % d->per != 0 || (d->n_local < d->per && d->first + d->n_local != d->n_rob) || (world_size == 1 && d->first != 0)))
     return fail(HDSM_ERR_BAD_ARG, "the shard is not a block of the ceil(n_rob / world_size) split: first_id must be rank * per, a short "
                                   "shard must be the last one (and first_id 0 with world_size 1)");
-  }
   d->rcfg = {d->cfg.path_vel_min, d->cfg.path_vel_max, d->cfg.sens_dist, d->cfg.sens_pot, d->cfg.sens_other_agents, d->cfg.path_vel_dec};
   Cfg& c = d->c;
   c.N = d->prm.n_hor, c.P = d->prm.poly_hor, c.RS = d->prm.max_rows_static, c.step_plan = d->cfg.step_plan;
@@ -912,89 +1077,11 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
     if ((e[0] == '0' || e[0] == '1') && e[1] == 0) c.fast_walk = e[0] == '1';
   }
   for (int k = 0; k < 3; ++k) c.grid_range[k] = d->cfg.grid_range[k], c.wdim[k] = wdim[k], c.worigin[k] = worigin[k];
-  if (hipSetDevice(device) != hipSuccess) {
-    delete d;
-    return fail(HDSM_ERR_NO_DEVICE, "hipSetDevice failed");
-  }
-  const size_t n = (size_t)d->n_local, L = (size_t)d->per, G = (size_t)d->per * world_size, N = (size_t)c.N, P = (size_t)c.P, RS = (size_t)c.RS,
-               REC = (N + 1) * 9;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t r) {
-    if (e == hipSuccess) e = r;
-  };
-  ok(dalloc(&d->d_agents, n));
-  if (hworld) {
-    ok(dalloc(&d->d_world, (size_t)wdim[0] * wdim[1] * wdim[2]));
-    bool cache_on = true;  // development switch (A/B): HDSM_POLY_CACHE=0 grows every polyhedron again
-    if (const char* pcenv = std::getenv("HDSM_POLY_CACHE")) cache_on = !(pcenv[0] == '0' && pcenv[1] == 0);
-    if (cache_on) ok(dalloc(&d->d_cache, n));
-  }
-  ok(dalloc(&d->d_path, n * PTS * 3)), ok(dalloc(&d->d_npath, n)), ok(dalloc(&d->d_ref_full, n * (N + 1) * 6)), ok(dalloc(&d->d_ref, n * N * 6));
-  ok(dalloc(&d->d_cap, n)), ok(dalloc(&d->d_pv, n)), ok(dalloc(&d->d_id, n)), ok(dalloc(&d->d_state, n * 9)), ok(dalloc(&d->d_npoly, n)), ok(dalloc(&d->d_nrows, n * P));
-  ok(dalloc(&d->d_A, n * P * RS * 3)), ok(dalloc(&d->d_b, n * P * RS)), ok(dalloc(&d->d_traj, L * REC)), ok(dalloc(&d->d_ctrl, L * N * 3));
-  ok(dalloc(&d->d_obj, L)), ok(dalloc(&d->d_used, L * P)), ok(dalloc(&d->d_status, L)), ok(dalloc(&d->d_local, L * REC));
-  ok(dalloc(&d->d_plans, G * REC)), ok(dalloc(&d->d_has, G)), ok(dalloc(&d->d_fails, 1));
-  ok(dalloc(&d->d_due, n)), ok(dalloc(&d->d_goals, n * 3)), ok(dalloc(&d->d_path_cnt, 2));
-  d->due.assign(n, 0), d->goals.assign(n * 3, 0.0);
-  if (rc == HDSM_OK) {
-    int32_t period = 0;
-    int64_t round = 0;
-    rc = hdsm_swarm_export_path_state(swarm, &period, &round, d->due.data());
-    d->path_period = period, d->path_round = round;
-  }
-  if (rc == HDSM_OK) {
-    double rad = 0;
-    rc = hdsm_swarm_export_path_clearance(swarm, &rad);
-    if (rc == HDSM_OK && rad != 0) {
-      hdsm_path::DmpMask mask{};
-      if (!hdsm_path::dmp_build_mask(rad, d->cfg.voxel_size, &mask)) rc = HDSM_ERR_BAD_ARG;
-      d->dmp = true, d->dmp_rn = mask.rn;
-      ok(dalloc(&d->d_dmp_rows, sizeof mask.rows / sizeof mask.rows[0]));
-      if (e == hipSuccess) ok(hipMemcpy(d->d_dmp_rows, mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
-    }
-  }
-  if (e == hipSuccess && n) {
-    AgentS* tmp = static_cast<AgentS*>(std::malloc(n * sizeof(AgentS)));
-    if (!tmp) e = hipErrorOutOfMemory;
-    else {
-      rc = hdsm_swarm_export_state(swarm, tmp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-      if (rc == HDSM_OK) e = hipMemcpy(d->d_agents, tmp, n * sizeof(AgentS), hipMemcpyHostToDevice);
-      for (size_t k = 0; k < n; ++k)
-        for (int q = 0; q < 3; ++q) d->goals[3 * k + q] = tmp[k].goal[q];
-      std::free(tmp);
-    }
-  }
-  if (e == hipSuccess && n) {  // agent ids of the shard (contiguous block)
-    std::string ids(n * 4, '\0');
-    for (size_t k = 0; k < n; ++k) reinterpret_cast<int32_t*>(&ids[0])[k] = d->first + (int)k;
-    e = hipMemcpy(d->d_id, ids.data(), n * 4, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && n) e = hipMemcpy(d->d_goals, d->goals.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess && n) {  // agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
-    std::vector<int32_t> idx;
-    for (size_t k = 0; k < n; ++k)
-      if (d->due[k]) idx.push_back((int32_t)k);
-    d->n_due = (int)idx.size();
-    if (d->n_due) e = hipMemcpy(d->d_due, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && hworld) e = hipMemcpy(d->d_world, hworld, (size_t)wdim[0] * wdim[1] * wdim[2], hipMemcpyHostToDevice);
-  c.world = d->d_world;
-  if (e == hipSuccess && rc == HDSM_OK) {  // the audit's setting and record of the mirror (a flight taken over keeps its record)
-    int32_t on = 0, ever = 0;
-    rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d->sep_warn, nullptr);
-    if (rc == HDSM_OK && ever) {
-      std::vector<hdsm_flight_report> rep(n);
-      rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d->sep_warn, rep.data());
-      d->audit_on = on != 0;
-      if (rc == HDSM_OK) rc = audit_setup(d, rep.data());
-    }
-  }
-  if (e != hipSuccess || rc) {
-    free_all(d);
-    delete d;
-    return fail(rc ? rc : HDSM_ERR_DEVICE, std::string("hdsm_dswarm_create: ") + (rc ? "export failed" : hipGetErrorString(e)));
-  }
-  *dswarm = d;
+  if (hipSetDevice(device) != hipSuccess) return fail(HDSM_ERR_NO_DEVICE, "hipSetDevice failed");
+  const hipError_t e = alloc_round_buffers(d.get(), hworld);
+  if (e != hipSuccess) return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_create: ") + hipGetErrorString(e));
+  if (int rc = take_over(*d, swarm, hworld)) return rc;
+  *dswarm = d.release();
   return HDSM_OK;
 }
 
@@ -1003,7 +1090,6 @@ void hdsm_dswarm_destroy(void* dswarm) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   (void)hipDeviceSynchronize();
-  free_all(d);
   delete d;
 }
 
@@ -1020,8 +1106,6 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
   }
   HIP_TRY(hipSetDevice(d->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  const int n = d->n_local, G = d->per * d->world, rec = (d->c.N + 1) * 9;
-  const unsigned gb = (unsigned)((n + 63) / 64);
   // The solver handle's "done" event (what a later call on another stream waits for) is recorded once, when the round has been
   // issued, instead of after each of its entry points: every record is a barrier packet in front of the next kernel (5-6 us each).
   struct DoneOnce {
@@ -1033,96 +1117,11 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
       (void)hdsm_internal_record_done(solver, st);
     }
   } done_once(d->solver, st);
-  const bool timing = d->phase_timing;
-#define PHASE_MARK(k) \
-  do {                \
-    if (timing) HIP_TRY(hipEventRecord(d->ev[k], st)); \
-  } while (0)
-  // the path step (UpdatePath, AC:261-454) at the start of the round, before the corridor: every agent in rounds of the period,
-  // else the agents whose goal changed; no launch when nobody is due
-  {
-    const bool all = d->path_period > 0 && d->path_round % d->path_period == 0;
-    const int n_plan = all ? n : d->n_due;
-    d->path_valid = false;
-    if (n_plan > 0) {
-      if (timing) HIP_TRY(hipEventRecord(d->path_ev[0], st));
-      if (d->dmp)
-        hipLaunchKernelGGL(k_dmp, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
-                           d->d_path_cnt, d->dmp_rn, d->d_dmp_rows);
-      else
-        hipLaunchKernelGGL(k_path, dim3((unsigned)n_plan), dim3(hdsm_path::THREADS), 0, st, d->c, all ? nullptr : d->d_due, d->d_agents, d->d_goals,
-                           d->d_path_cnt);
-      HIP_TRY(hipGetLastError());
-      if (timing) {
-        HIP_TRY(hipEventRecord(d->path_ev[1], st));
-        d->path_valid = true;
-      }
-      ++d->path_launches;
-    }
-    d->n_due = 0;
-    std::fill(d->due.begin(), d->due.end(), (uint8_t)0);
-    ++d->path_round;
-  }
-  PHASE_MARK(0);
-  if (n > 0) {
-    hipLaunchKernelGGL(k_corridor, dim3((unsigned)n), dim3(64), d->c.has_world ? hdsm_cd::wave_lds_bytes(hdsm_cd::wave_map_radius(d->c.n_it_decomp)) : 0, st, d->c, n, d->d_agents, d->d_path, d->d_npath, d->d_id, d->d_state,
-                       d->d_npoly, d->d_nrows, d->d_A, d->d_b, d->d_cache);
-    HIP_TRY(hipGetLastError());
-    PHASE_MARK(1);
-    if (d->c.has_world) {
-      hipLaunchKernelGGL(k_vel_cap, dim3((unsigned)n), dim3(64), 0, st, d->c, d->rcfg, n, d->d_agents, d->d_path, d->d_npath, d->d_cap);
-      HIP_TRY(hipGetLastError());
-    }
-    PHASE_MARK(2);
-    int rc = hdsm_reference_device(d->solver, &d->rcfg, n, G, d->d_id, d->d_path, d->d_npath, PTS, d->c.has_world ? d->d_cap : nullptr,
-                                   d->d_plans, d->d_has, d->d_ref_full, d->d_ref, d->d_pv, st);
-    if (rc) return fail(rc, std::string("hdsm_reference_device: ") + hdsm_last_error());
-    PHASE_MARK(3);
-    if (d->c.has_world) {
-      hipLaunchKernelGGL(k_keep_free, dim3(gb), dim3(64), 0, st, d->c, n, d->d_agents, d->d_ref_full, d->d_ref, d->d_pv);
-      HIP_TRY(hipGetLastError());
-    }
-    PHASE_MARK(4);
-    rc = hdsm_replan_device(d->solver, n, G, d->d_id, d->d_state, d->d_ref, d->d_npoly, d->d_nrows, d->d_A, d->d_b, d->d_plans, d->d_has,
-                            d->d_traj, d->d_ctrl, d->d_used, d->d_status, d->d_obj, st);
-    if (rc) return fail(rc, std::string("hdsm_replan_device: ") + hdsm_last_error());
-  } else {
-    for (int k = 1; k <= 4; ++k) PHASE_MARK(k);
-  }
-  PHASE_MARK(5);
-  // (one rank: the solve of this round is behind us on the stream, so the records go straight into the plans buffer — slot k =
-  // agent k — and the flags with them; several ranks: into the send buffer of the ONE all-gather)
-  const bool direct = d->world == 1;
-  hipLaunchKernelGGL(k_commit, dim3((unsigned)(d->per > 0 ? d->per : 1)), dim3(64), 0, st, d->c, n, d->per, d->d_agents, d->d_traj, d->d_ctrl, d->d_used, d->d_status,
-                     direct ? d->d_plans : d->d_local, d->d_fails, direct ? d->d_has : nullptr, d->d_ref_full, d->d_pv);
-  HIP_TRY(hipGetLastError());
-  PHASE_MARK(6);
-  if (!direct) {
-    const int rc = hdsm_exchange_device(comm, d->per, d->d_local, d->d_plans, d->d_has, st);
-    if (rc) return fail(rc, std::string("hdsm_exchange_device: ") + hdsm_last_error());
-  }
-  PHASE_MARK(7);
-#undef PHASE_MARK
-  // the flight audit and the history row, on this round's records of all agents (only when one of them is on)
-  d->audit_valid = false;
-  if (d->hist_cap > 0 && d->hist_n == d->hist_cap) ++d->hist_dropped;
-  const bool hist = d->hist_cap > 0 && d->hist_n < d->hist_cap;
-  if ((d->audit_on || hist) && n > 0) {
-    if (timing) HIP_TRY(hipEventRecord(d->audit_ev[0], st));
-    hdsm_audit::World wd{};
-    wd.world = d->c.has_world ? d->d_world : nullptr, wd.voxel_size = d->c.voxel_size;
-    for (int k = 0; k < 3; ++k) wd.wdim[k] = d->c.wdim[k], wd.worigin[k] = d->c.worigin[k];
-    HIP_TRY(hdsm_audit::launch(d->abuf, d->audit_on, d->d_plans, d->d_has, d->c.N, d->first, hdsm_audit::weights(d->prm.drone_radius, d->prm.drone_z_offset),
-                               wd, d->d_report, d->sep_warn * d->sep_warn, &d->d_agents[0].state_curr[0], sizeof(AgentS),
-                               hist ? d->d_hist + (size_t)d->hist_n * n * 9 : nullptr, st));
-    if (timing) {
-      HIP_TRY(hipEventRecord(d->audit_ev[1], st));
-      d->audit_valid = true;
-    }
-    if (d->audit_on) ++d->audit_rounds;
-  }
-  if (hist) ++d->hist_n;
-  if (timing) d->phase_valid = true;
+  if (int rc = path_step(*d, st)) return rc;
+  if (int rc = corridor_to_solve(*d, st)) return rc;
+  if (int rc = commit_and_exchange(*d, comm, st)) return rc;
+  if (int rc = audit_and_history(*d, st)) return rc;
+  if (d->phase_timing) d->phase_valid = true;
   ++d->rounds;
   return HDSM_OK;
 }
@@ -1133,9 +1132,9 @@ int hdsm_dswarm_upload_plans(void* dswarm, const double* plans_all, const uint8_
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9, have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;
-  HIP_TRY(hipMemset(d->d_has, 0, G));
-  HIP_TRY(hipMemcpy(d->d_plans, plans_all, have * rec * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d->d_has, has_plan, have, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d->d_has.get(), 0, G));
+  HIP_TRY(hipMemcpy(d->d_plans.get(), plans_all, have * rec * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d->d_has.get(), has_plan, have, hipMemcpyHostToDevice));
   return HDSM_OK;
 }
 
@@ -1145,31 +1144,18 @@ int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* 
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t n = (size_t)d->n_local, G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
-  if (swarm && n) {
-    AgentS* tmp = static_cast<AgentS*>(std::malloc(n * sizeof(AgentS)));
-    if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
-    hipError_t e = hipMemcpy(tmp, d->d_agents, n * sizeof(AgentS), hipMemcpyDeviceToHost);
-    int rc = e == hipSuccess ? hdsm_swarm_import_state(swarm, tmp, d->n_local) : HDSM_ERR_DEVICE;
-    std::free(tmp);
-    if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d->path_period, d->path_round, d->due.data(), d->goals.data());
-    if (rc == HDSM_OK && d->audit_ever) {
-      std::vector<hdsm_flight_report> rep(n);
-      if (hipMemcpy(rep.data(), d->d_report, n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
-      else rc = hdsm_swarm_import_audit(swarm, d->audit_on ? 1 : 0, d->sep_warn, rep.data());
-    }
-    if (rc) return fail(rc, "state download failed");
-  }
+  if (swarm && n)
+    if (int rc = hand_back(*d, swarm)) return rc;
   if (plans_all) {
-    HIP_TRY(hipMemcpy(plans_all, d->d_plans, G * rec * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(plans_all, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < G; ++k)
       if (plans_all[k * rec] != plans_all[k * rec]) plans_all[k * rec] = 0.0;  // the sentinel is for the wire only
   }
-  if (has_plan) HIP_TRY(hipMemcpy(has_plan, d->d_has, G, hipMemcpyDeviceToHost));
-  if (status && n) HIP_TRY(hipMemcpy(status, d->d_status, n * 4, hipMemcpyDeviceToHost));
-  if (failed_total) HIP_TRY(hipMemcpy(failed_total, d->d_fails, 4, hipMemcpyDeviceToHost));
+  if (has_plan) HIP_TRY(hipMemcpy(has_plan, d->d_has.get(), G, hipMemcpyDeviceToHost));
+  if (status && n) HIP_TRY(hipMemcpy(status, d->d_status.get(), n * 4, hipMemcpyDeviceToHost));
+  if (failed_total) HIP_TRY(hipMemcpy(failed_total, d->d_fails.get(), 4, hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
-
 
 // ---- the flight audit and the state history of the device loop (audit_kernels.hip) ----
 int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn) {
@@ -1178,13 +1164,11 @@ int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn) {
   if (!(sep_warn > 0)) return fail(HDSM_ERR_BAD_ARG, "sep_warn must be positive");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  d->audit_on = on != 0, d->sep_warn = sep_warn;
+  d->audit.on = on != 0, d->audit.sep_warn = sep_warn;
   if (on) {
-    const int rc = audit_setup(d, nullptr);
-    if (rc) return rc;
+    if (int rc = audit_setup(d, nullptr)) return rc;
     if (d->phase_timing)
-      for (hipEvent_t& e : d->audit_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+      if (int rc = timing_events(d)) return rc;
   }
   return HDSM_OK;
 }
@@ -1192,20 +1176,20 @@ int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn) {
 int hdsm_dswarm_flight_report(void* dswarm, hdsm_flight_report* report) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || (d->n_local && !report)) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->audit_ever) return fail(HDSM_ERR_BAD_ARG, "the flight audit was never switched on");
+  if (!d->audit.ever) return fail(HDSM_ERR_BAD_ARG, "the flight audit was never switched on");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (d->n_local) HIP_TRY(hipMemcpy(report, d->d_report, (size_t)d->n_local * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost));
+  if (d->n_local) HIP_TRY(hipMemcpy(report, d->audit.d_report.get(), (size_t)d->n_local * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 
 int hdsm_dswarm_last_audit_round(void* dswarm, hdsm_audit_round* out) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || (d->n_local && !out)) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->audit_on || d->audit_rounds == 0) return fail(HDSM_ERR_BAD_ARG, "no round has been audited (hdsm_dswarm_set_audit)");
+  if (!d->audit.on || d->audit.rounds == 0) return fail(HDSM_ERR_BAD_ARG, "no round has been audited (hdsm_dswarm_set_audit)");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (d->n_local) HIP_TRY(hipMemcpy(out, d->abuf.d_round, (size_t)d->n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
+  if (d->n_local) HIP_TRY(hipMemcpy(out, d->audit.buf.d_round.get(), (size_t)d->n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 
@@ -1215,10 +1199,9 @@ int hdsm_dswarm_last_audit_ms(void* dswarm, float* ms) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
   *ms = 0.0f;
-  if (!d->audit_valid) return HDSM_OK;
+  if (!d->audit.timed.valid) return HDSM_OK;
   HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipEventSynchronize(d->audit_ev[1]));
-  HIP_TRY(hipEventElapsedTime(ms, d->audit_ev[0], d->audit_ev[1]));
+  HIP_TRY(d->audit.timed.ms(ms));
   return HDSM_OK;
 }
 
@@ -1227,16 +1210,15 @@ int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds) {
   if (!d || capacity_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "bad argument");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (d->d_hist) (void)hipFree(d->d_hist);
-  d->d_hist = nullptr, d->hist_cap = 0, d->hist_n = d->hist_dropped = d->hist_delivered = 0;
+  History& h = d->hist;
+  h.d_rows.reset();
+  h.cap = 0, h.n = h.dropped = h.delivered = 0;
   if (capacity_rounds > 0) {
-    const int rc = audit_setup(d, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_hist), ((size_t)capacity_rounds * d->n_local * 9 + 1) * sizeof(double)));
-    d->hist_cap = capacity_rounds;
+    if (int rc = audit_setup(d, nullptr)) return rc;
+    HIP_TRY(h.d_rows.alloc((size_t)capacity_rounds * d->n_local * 9 + 1));
+    h.cap = capacity_rounds;
     if (d->phase_timing)
-      for (hipEvent_t& e : d->audit_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+      if (int rc = timing_events(d)) return rc;
   }
   return HDSM_OK;
 }
@@ -1244,22 +1226,23 @@ int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds) {
 int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_t max_rounds, int32_t* n_rounds, int32_t* dropped) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || max_rounds < 0 || (hist == nullptr && max_rounds > 0)) return fail(HDSM_ERR_BAD_ARG, "bad argument");
-  if (d->hist_cap == 0) return fail(HDSM_ERR_BAD_ARG, "the history is off (hdsm_dswarm_set_history)");
+  History& h = d->hist;
+  if (h.cap == 0) return fail(HDSM_ERR_BAD_ARG, "the history is off (hdsm_dswarm_set_history)");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t row = (size_t)d->n_local * 9;
-  const int n_copy = d->hist_n < max_rounds ? d->hist_n : max_rounds;
-  if (n_copy > 0 && row) HIP_TRY(hipMemcpy(hist, d->d_hist, (size_t)n_copy * row * sizeof(double), hipMemcpyDeviceToHost));
-  if (swarm && d->hist_n > d->hist_delivered) {  // every recorded round reaches the mirror's planner records once
-    const int m = d->hist_n - d->hist_delivered;
+  const int n_copy = h.n < max_rounds ? h.n : max_rounds;
+  if (n_copy > 0 && row) HIP_TRY(hipMemcpy(hist, h.d_rows.get(), (size_t)n_copy * row * sizeof(double), hipMemcpyDeviceToHost));
+  if (swarm && h.n > h.delivered) {  // every recorded round reaches the mirror's planner records once
+    const int m = h.n - h.delivered;
     std::vector<double> rows((size_t)m * row);
-    if (row) HIP_TRY(hipMemcpy(rows.data(), d->d_hist + (size_t)d->hist_delivered * row, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (row) HIP_TRY(hipMemcpy(rows.data(), h.d_rows.get() + (size_t)h.delivered * row, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
     const int rc = hdsm_swarm_append_history(swarm, m, rows.data());
     if (rc) return fail(rc, "hdsm_swarm_append_history");
-    d->hist_delivered = d->hist_n;
+    h.delivered = h.n;
   }
-  if (n_rounds) *n_rounds = d->hist_n;
-  if (dropped) *dropped = d->hist_dropped;
+  if (n_rounds) *n_rounds = h.n;
+  if (dropped) *dropped = h.dropped;
   return HDSM_OK;
 }
 
@@ -1272,10 +1255,10 @@ int hdsm_dswarm_update_world(void* dswarm, const int8_t* values, const int32_t l
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = stage_box(d, values, bdim)) return rc;
-  if (int rc = put_box(d, d->d_edit, d->d_world, lo, bdim, nullptr)) return rc;
+  if (int rc = put_box(d, d->edits.d_edit.get(), d->d_world.get(), lo, bdim, nullptr)) return rc;
   if (int rc = invalidate(d, lo, bdim, nullptr)) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  ++d->world_updates, d->world_voxels += (long long)bdim[0] * bdim[1] * bdim[2];
+  ++d->edits.updates, d->edits.voxels += (long long)bdim[0] * bdim[1] * bdim[2];
   return HDSM_OK;
 }
 
@@ -1292,17 +1275,22 @@ int hdsm_dswarm_set_raw_world(void* dswarm, const hdsm_map_config* map_cfg, cons
   if (scr == 0) return fail(HDSM_ERR_BAD_ARG, std::string("map configuration: ") + hdsm_map_last_error());
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (!d->d_raw) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_raw), vox));
-  if (!d->d_map_scr) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->d_map_scr), scr));
-  HIP_TRY(hipMemcpy(d->d_raw, raw_full, vox, hipMemcpyHostToDevice));
+  WorldEdits& w = d->edits;
+  {  // out of the dswarm until the new grid is in it: an allocation or a copy that fails leaves no raw world resident
+    DevBuf<int8_t> raw = std::move(w.d_raw);
+    DevBuf<uint8_t> map_scr = std::move(w.d_map_scr);
+    if (!raw) HIP_TRY(raw.alloc(vox));
+    if (!map_scr) HIP_TRY(map_scr.alloc(scr));
+    HIP_TRY(hipMemcpy(raw.get(), raw_full, vox, hipMemcpyHostToDevice));
+    w.d_raw = std::move(raw), w.d_map_scr = std::move(map_scr);
+  }
   // (the arguments were checked above: what can still fail is a launch, and then the device world is no longer the old one —
   // the cache is emptied on that way out too)
-  const int rc = hdsm_map_preprocess_device(d->device, map_cfg, 1, d->c.wdim, d->d_raw, d->d_world, d->d_map_scr, nullptr);
-  if (rc == HDSM_OK) d->mcfg = *map_cfg;
+  const int rc = hdsm_map_preprocess_device(d->device, map_cfg, 1, d->c.wdim, w.d_raw.get(), d->d_world.get(), w.d_map_scr.get(), nullptr);
+  if (rc == HDSM_OK) w.mcfg = *map_cfg;
   const int rc2 = invalidate(d, nullptr, nullptr, nullptr);
   if (rc) {
-    (void)hipFree(d->d_raw);  // (no raw world is resident: the raw update calls keep refusing)
-    d->d_raw = nullptr;
+    w.d_raw.reset();  // (no raw world is resident: the raw update calls keep refusing)
     return fail(rc, std::string("hdsm_map_preprocess_device: ") + hdsm_map_last_error());
   }
   if (rc2) return rc2;
@@ -1314,18 +1302,19 @@ int hdsm_dswarm_update_world_raw_device(void* dswarm, const int8_t* d_raw_values
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   const int k = world_box(d, lo, bdim);
   if (k < 0) return k;
-  if (!d->d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
+  WorldEdits& w = d->edits;
+  if (!w.d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
   if (k == 0) return HDSM_OK;
   if (!d_raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
   HIP_TRY(hipSetDevice(d->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
   int32_t wlo[3], wdim[3];
-  if (int rc = hdsm_map_region_extent(&d->mcfg, d->c.wdim, lo, bdim, wlo, wdim, nullptr, nullptr)) return fail(rc, hdsm_map_last_error());
-  if (int rc = put_box(d, d_raw_values, d->d_raw, lo, bdim, st)) return rc;
-  if (int rc = hdsm_map_preprocess_region_device(d->device, &d->mcfg, d->c.wdim, d->d_raw, d->d_world, lo, bdim, d->d_map_scr, st))
+  if (int rc = hdsm_map_region_extent(&w.mcfg, d->c.wdim, lo, bdim, wlo, wdim, nullptr, nullptr)) return fail(rc, hdsm_map_last_error());
+  if (int rc = put_box(d, d_raw_values, w.d_raw.get(), lo, bdim, st)) return rc;
+  if (int rc = hdsm_map_preprocess_region_device(d->device, &w.mcfg, d->c.wdim, w.d_raw.get(), d->d_world.get(), lo, bdim, w.d_map_scr.get(), st))
     return fail(rc, std::string("hdsm_map_preprocess_region_device: ") + hdsm_map_last_error());
   if (int rc = invalidate(d, wlo, wdim, st)) return rc;
-  ++d->world_updates, d->world_voxels += (long long)wdim[0] * wdim[1] * wdim[2];
+  ++w.updates, w.voxels += (long long)wdim[0] * wdim[1] * wdim[2];
   return HDSM_OK;
 }
 
@@ -1333,13 +1322,13 @@ int hdsm_dswarm_update_world_raw(void* dswarm, const int8_t* raw_values, const i
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   const int k = world_box(d, lo, bdim);
   if (k < 0) return k;
-  if (!d->d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
+  if (!d->edits.d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
   if (k == 0) return HDSM_OK;
   if (!raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   if (int rc = stage_box(d, raw_values, bdim)) return rc;
-  if (int rc = hdsm_dswarm_update_world_raw_device(dswarm, d->d_edit, lo, bdim, nullptr)) return rc;
+  if (int rc = hdsm_dswarm_update_world_raw_device(dswarm, d->edits.d_edit.get(), lo, bdim, nullptr)) return rc;
   HIP_TRY(hipDeviceSynchronize());
   return HDSM_OK;
 }
@@ -1350,19 +1339,19 @@ int hdsm_dswarm_download_world(void* dswarm, int8_t* world) {
   if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world");
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(world, d->d_world, (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2], hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(world, d->d_world.get(), (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2], hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 
 int hdsm_dswarm_world_stats(void* dswarm, int64_t out[4]) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = d->world_updates, out[1] = d->world_voxels, out[2] = 0, out[3] = d->d_raw ? 1 : 0;
-  if (!d->d_dropped) return HDSM_OK;
+  out[0] = d->edits.updates, out[1] = d->edits.voxels, out[2] = 0, out[3] = d->edits.d_raw ? 1 : 0;
+  if (!d->edits.d_dropped) return HDSM_OK;
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long n = 0;
-  HIP_TRY(hipMemcpy(&n, d->d_dropped, sizeof n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&n, d->edits.d_dropped.get(), sizeof n, hipMemcpyDeviceToHost));
   out[2] = (int64_t)n;
   return HDSM_OK;
 }

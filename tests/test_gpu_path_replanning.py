@@ -56,13 +56,16 @@ def _forest_pair(hdsm, n_rob, period, seed=21):  # noqa: F811
     return make(), make()
 
 
+PLAN_TOL = 1e-7   # plans of two flights that plan the same: the solver's staging order is not deterministic
+
+
 def _compare(host, dsw, r):
     out = host.step()
     dsw.round()
     plans, has, status, failed = dsw.download(states=False)
     assert (has == host.has_plan).all(), r
     assert (status == out["status"]).all(), (r, status.tolist(), out["status"].tolist())
-    assert np.abs(plans - host.plans_all).max() < 1e-7, (r, float(np.abs(plans - host.plans_all).max()))
+    assert np.abs(plans - host.plans_all).max() < PLAN_TOL, (r, float(np.abs(plans - host.plans_all).max()))
 
 
 @pytest.mark.gpu

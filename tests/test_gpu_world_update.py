@@ -8,7 +8,7 @@ import test_world_update as wu
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import default_map_config
 from test_gpu_configs import hdsm  # noqa: F401  (the module's fixture)
-from test_gpu_path_replanning import _compare, _forest_pair
+from test_gpu_path_replanning import PLAN_TOL, _compare, _forest_pair
 from test_kernel_resources import _kernel_descriptors
 
 LOOK = (42 + 5) // 6 + 2 + 1   # wave_map_radius(n_it_decomp = 42) and the voxel of margin: what an invalidation looks at round a seed
@@ -280,6 +280,58 @@ def test_takeover_after_edits(hdsm):  # noqa: F811
     for r in range(10, 15):
         _compare(host, dsw2, r)
     dsw2.close()
+
+
+@pytest.mark.gpu
+def test_device_swarm_lifecycle_with_every_option_on(hdsm):  # noqa: F811
+    """Create / close three times in one process with every opt-in group of the device loop allocated: phase timing, the audit, a
+    history of 4 rounds, a resident raw world. Each flight starts from the same untouched shard (nothing is downloaded into it),
+    flies three rounds, takes one raw edit that writes a 2 x 2 column of the values already there, flies one more round, and is read
+    out and closed before the next is made. The three flights agree — statuses and flags exactly, plans, every field of the flight
+    record and the history rows to the tolerance of _compare — and each reports seven finite phase times, one update, a resident raw world.
+    The three flights share one solver handle, which keeps every instance's last optimal working set as the seed of its next solve
+    (hdsm_params.warm_start). Seeded with the sets of another flight's fourth round, round 2 of this flight ends for some agents in a
+    different optimum of equal cost (every status is "proven optimal" either way): measured on the MI355X, flights 1 and 2 were then
+    1.06 / 0.415 / 0.287 from flight 0 in the plans of rounds 2 / 3 / 4 (1.7e-13 in round 1), with and without the options, before and
+    after DSwarm owned its memory by type; with the working sets forgotten before each flight, or with a fresh handle per flight, all
+    four rounds agree bit for bit. So each flight starts from the same solver state too: reset_warm_start() before it is created."""
+    from multi_agent_pkgs_amd import swarm
+    (_, _), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    raw, _, _ = _world_of(48)
+    assert raw.shape == (67, 240, 240) and raw.dtype == np.int8
+    cfg = default_map_config(**MAP_CFG)
+    lo = [100, 120, 0]
+    column = raw[:, lo[1]:lo[1] + 2, lo[0]:lo[0] + 2].copy()
+    flights = []
+    for f in range(3):
+        sol_d.reset_warm_start()
+        dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
+        dsw.set_phase_timing()
+        dsw.set_audit()
+        dsw.set_history(4)
+        dsw.set_raw_world(cfg, raw)
+        for r in range(3):
+            dsw.round()
+        dsw.update_world_raw(column, lo)
+        dsw.round()
+        plans, has, status, _ = dsw.download(states=False)
+        out = dict(plans=plans, has=has, status=status, report=dsw.flight_report(), hist=dsw.history(mirror=False), phase=dsw.phase_ms(),
+                   path_ms=dsw.last_path_ms(), audit_ms=dsw.last_audit_ms(), world=dsw.world_stats())
+        dsw.close()
+        assert len(out["phase"]) == 7 and np.isfinite(list(out["phase"].values())).all(), (f, out["phase"])
+        assert np.isfinite([out["path_ms"], out["audit_ms"]]).all(), (f, out["path_ms"], out["audit_ms"])
+        assert out["world"]["updates"] == 1 and out["world"]["raw_resident"], (f, out["world"])
+        assert out["hist"][0].shape == (4, 48, 9) and out["hist"][1] == 0, f
+        flights.append(out)
+    first = flights[0]
+    for f, out in enumerate(flights[1:], 1):
+        assert (out["status"] == first["status"]).all() and (out["has"] == first["has"]).all(), f
+        gap = lambda a, b: float(np.where(a == b, 0.0, np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))).max())  # (inf == inf: 0)
+        apart = {"plans": gap(out["plans"], first["plans"]), "hist": gap(out["hist"][0], first["hist"][0])}
+        for name in first["report"].dtype.names:
+            apart["report." + name] = gap(out["report"][name], first["report"][name])
+        print("flight", f, "apart from flight 0:", apart)
+        assert max(apart.values()) < PLAN_TOL, (f, apart)
 
 
 def test_world_update_kernels_use_no_scratch(tmp_path):
