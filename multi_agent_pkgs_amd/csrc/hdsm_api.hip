@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -21,10 +22,14 @@
 #include "../../include/hdsm.h"
 #include "hdsm_consts.h"
 #include "hdsm_core.h"
+#include "hdsm_handle.h"
+#include "hdsm_internal.h"
 #include "hdsm_level1.h"
 #include "hdsm_shapes.h"
 
 namespace {
+
+using hdsm_handle::Handle;
 
 thread_local std::string g_err;
 
@@ -729,76 +734,6 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   }
 }
 
-struct Handle {
-  int device = 0;
-  int max_inst = 0, n_rob_max = 0;
-  int N = 0, P = 0, RS = 0, n = 0;
-  int threads = 256, cus = 256;
-  int bounds_min = 256;       // swarms of at least this many agents get the sphere prefilter (HDSM_BOUNDS_MIN)
-  int duo_min = 0;            // batches of at least this many instances run two workgroups per CU (HDSM_DUO_MIN; set at create: CUs + 1)
-  int tri_min = 0;            // ... and of at least this many three 128-thread workgroups per CU (HDSM_TRI_MIN; 2 x CUs + 1, 0 = never)
-  int quad_min = 0;           // ... and of at least this many four per CU, small LDS layout (HDSM_QUAD_MIN; 3 x CUs + 1, 0 = never)
-  // subtree splitting (launch_split): 0 never, 1 always, 2 automatic (when the previous launch saw a deep tree)
-  int split_mode = 2, split_budget = 0, split_ttl = 0;  // split_budget 0: by batch size, see launch()
-  int rec_cap = 2048, rows_cap = 0, items_cap = 0, sub_slots_n = 0, pool_cap = 0, item_budget = 32, item_min = 0, poll_sleep = 2;  // hand-over records, staged rows per record, queue length, persistent workgroups of pass 2
-  int32_t* h_ovf_flag = nullptr;    // pinned host word: an instance ended on a staging overflow (Args::ovf_flag), and its device alias
-  int32_t* d_ovf_flag = nullptr;
-  int rescue_ttl = 0;               // launches left that carry the rescue pass
-  bool last_small = false;          // the last launch used a kernel shape with a reduced staging area
-  hdsm::Args last_args;             // ... and its arguments (the host-buffer path adds the rescue pass at once)
-  int32_t* h_tree_flag = nullptr;   // pinned host word the kernels raise (Args::tree_flag), and its device alias
-  int32_t* d_tree_flag = nullptr;
-  hdsm::SplitRec* d_recs = nullptr;  // hand-over records of pass 1 and their staged rows (Args::recs, rec_cand, rec_mw, rec_src)
-  double* d_rec_cand = nullptr;
-  long long* d_rec_mw = nullptr;
-  int32_t *d_rec_src = nullptr, *d_rec_count = nullptr, *d_items = nullptr;
-  int32_t* d_slot_busy = nullptr;    // [pool_cap] snapshot-scratch slots of pass 2 taken (Args::slot_busy)
-  int32_t *h_item_total = nullptr, *d_item_total = nullptr;  // pinned host word: items queued by the last split launch (the merge writes it)
-  int32_t *d_split = nullptr, *d_sub_stats = nullptr, *d_sub_warm = nullptr, *d_sub_status = nullptr;
-  unsigned long long* d_inc = nullptr;
-  int32_t* d_node_pool = nullptr;  // [max_inst] nodes the sub-blocks of an instance may still open (Args::node_pool)
-  double *d_sub_traj = nullptr, *d_sub_ctrl = nullptr, *d_sub_obj = nullptr, *d_sub_scratch = nullptr;
-  uint8_t* d_sub_used = nullptr;
-  bool sub_ready = false;
-  void* h_out = nullptr;      // pinned staging of hdsm_replan's outputs (grow-only)
-  size_t h_out_cap = 0;
-  double* d_bounds = nullptr; // [n_rob_max][4]
-  double* d_setup = nullptr;  // [max_inst][KROWS] the set-up map of every instance of a launch (Args::setup)
-  int setup_mfma = 1;         // 0 (HDSM_SETUP_MFMA=0): every instance applies the map itself (the form of rounds 1-4)
-  double* d_pos = nullptr;    // [n_rob_max][N][3] packed positions (pre-pass)
-  double* d_rpos = nullptr;   // [n_rob_max][N + 1][3] packed positions of steps 0..N (k_ref_pack)
-  double* d_rsph = nullptr;   // [n_rob_max][4] their spheres
-  int32_t* d_order = nullptr; // [max_inst][2] launch order: (instance, its agent id) per workgroup (k_launch_order)
-  int order_min = 0;          // batches of at least this many instances are launched most-expensive-first (0 = never)
-  uint8_t* d_zero = nullptr;  // n_rob_max zero bytes (has_plan of level 1)
-  hipEvent_t ev_done = nullptr;  // recorded after every launch: orders launches that arrive on different streams
-  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;  // hdsm_set_kernel_timing: around the solver kernel alone (after the pre-pass)
-  bool time_kernel = false, timed = false;
-  bool launched = false;
-  struct Buf {                // grow-only device scratch of the host-pointer entry points
-    void* p = nullptr;
-    size_t cap = 0;
-  } b_planes, b_common, b_ncommon, b_path, b_cap, b_full, b_pv, b_np;
-  hdsm_params prm{};
-  hdsm::Consts* d_consts = nullptr;
-  double* d_scratch = nullptr;
-  int64_t scratch_stride = 0;
-  int32_t* d_stats = nullptr;  // 8 * max_inst: iterations, nodes, sweeps, staged rows, sphere records, pairs, flags, launch-order key
-  long long* d_prof = nullptr; // 24 * max_inst (HDSM_PROFILE builds)
-  int32_t* d_warm = nullptr;   // (MAXNV + 2) * max_inst: previous optimal working sets (params.warm_start)
-  // staging for the host-pointer entry points
-  int32_t *d_agent = nullptr, *d_npoly = nullptr, *d_nrows = nullptr, *d_status = nullptr;
-  double *d_state = nullptr, *d_ref = nullptr, *d_A = nullptr, *d_b = nullptr, *d_plans = nullptr;
-  double *d_traj = nullptr, *d_ctrl = nullptr, *d_obj = nullptr;
-  uint8_t *d_has = nullptr, *d_used = nullptr;
-  hipStream_t stream = nullptr;
-  hipStream_t last_stream = nullptr;
-  const double* prepass_for = nullptr;  // device loop: the plans buffer k_ref_pack has just packed for the solve as well (launch() skips its pre-pass once)
-  int prepass_n_rob = 0, prepass_n_inst = 0;
-  bool prepass_ordered = false;
-  bool defer_done = false;  // the device-resident loop records ev_done once per round (hdsm_internal_record_done), not once per call
-};
-
 // THREE workgroups of 128 threads (two wavefronts: the iterating one and one helper) per CU, for batches that outnumber the
 // resident slots of the two-per-CU kernel. A launch lasts as long as its slowest workgroup CHAIN: with 1024 instances on 512
 // slots an instance that was predicted cheap and turns out long starts late and sets the kernel time (measured: mean span
@@ -857,7 +792,7 @@ constexpr bool LDS_FIT_CHECK = false;
 #else
 constexpr bool LDS_FIT_CHECK = true;
 #endif
-// (per_cu is what ensure_sub counts as resident pass-2 workgroups per CU: the state of a one-per-CU kernel, with 64 threads too, is
+// (per_cu is what SplitState::alloc counts as resident pass-2 workgroups per CU: the state of a one-per-CU kernel, with 64 threads too, is
 // held to ONE by being more than half of a CU's 160 KB)
 #define HDSM_SHAPE_LAUNCH(name, kernel, nv, cmax, small, threads, per_cu)                                                               \
   static_assert(!LDS_FIT_CHECK || per_cu * sizeof(hdsm::Solver<nv, cmax, small>::S) <= 160 * 1024, #name ": per_cu instances must fit the LDS of one CU"); \
@@ -870,7 +805,7 @@ const ShapeLaunch SHAPE_LAUNCH[hdsm::NUM_SHAPES] = {HDSM_SOLVER_SHAPES(HDSM_SHAP
 
 int launch_shape(Handle* h, hdsm::Shape s, const hdsm::Args& a, hipStream_t st, int blocks) {
   const ShapeLaunch& l = SHAPE_LAUNCH[s];
-  hipLaunchKernelGGL(l.kern, dim3(blocks), dim3(l.threads), l.shm, st, h->d_consts, a);
+  hipLaunchKernelGGL(l.kern, dim3(blocks), dim3(l.threads), l.shm, st, h->d_consts.get(), a);
   HIP_TRY(hipGetLastError());
   return HDSM_OK;
 }
@@ -945,8 +880,6 @@ __global__ __launch_bounds__(64) void k_split_merge(int N, int P, hdsm::Args a, 
   hdsm::split_merge(N, P, a, b, (int)blockIdx.x, (int)threadIdx.x, 64);
 }
 
-hipError_t ensure_sub(Handle* h, hdsm::Shape items);
-
 // the one-per-CU kernel (largest staging area) over the batch of `a`; only instances flagged HDSM_FLAG_STAGING_OVERFLOW work
 int launch_rescue(Handle* h, const hdsm::Args& a, hipStream_t st) {
   hdsm::Args r = a;
@@ -955,62 +888,85 @@ int launch_rescue(Handle* h, const hdsm::Args& a, hipStream_t st) {
   return launch_shape(h, hdsm::pick_shape(shape_knobs(h), r.n_inst, hdsm::PASS_RESCUE), r, st, r.n_inst);
 }
 
+// The handle's device state (snapshots, warm-start sets, prefilter records, staging buffers) is shared by all its calls: one that
+// arrives on another stream than the previous launch waits for it. (Who launches on `st` also names it as last_stream; who only
+// stages into the handle's buffers does not.)
+hipError_t join_stream(Handle* h, hipStream_t st) {
+  return h->launched && st != h->last_stream ? hipStreamWaitEvent(st, h->ev_done.get(), 0) : hipSuccess;
+}
+
+// ... and this is the point it waits for: the end of what a device entry point enqueued
+hipError_t mark_done(Handle* h, hipStream_t st) {
+  if (!h->defer_done)
+    if (const hipError_t e = hipEventRecord(h->ev_done.get(), st)) return e;
+  h->launched = true;
+  return hipSuccess;
+}
+
+// the eight statistics of a launch, `stride` entries each, in one block
+void stat_views(hdsm::Args& a, int32_t* base, size_t stride) {
+  a.st_iters = base, a.st_nodes = base + stride, a.st_sweeps = base + 2 * stride, a.st_cand = base + 3 * stride;
+  a.st_sph = base + 4 * stride, a.st_pairs = base + 5 * stride;
+  a.st_flags = reinterpret_cast<uint32_t*>(base + 6 * stride), a.st_key = base + 7 * stride;
+}
+
+// stream-ordered copies of a host-pointer entry point: nothing to do for zero bytes, and nothing more after the first error
+struct Copies {
+  hipStream_t st;
+  hdsm_mem::FirstError err;
+  void operator()(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (err.ok() && bytes) err(hipMemcpyAsync(dst, src, bytes, kind, st));
+  }
+};
+
 int launch(Handle* h, hdsm::Args a, hipStream_t st) {
-  a.scratch = h->d_scratch;
+  hdsm_handle::SplitState& sub = h->sub;
+  hdsm_handle::Prepass& pp = h->pre;
+  a.scratch = h->d_scratch.get();
   a.scratch_stride = h->scratch_stride;
-  a.st_iters = h->d_stats;
-  a.st_nodes = h->d_stats + h->max_inst;
-  a.st_sweeps = h->d_stats + 2 * h->max_inst;
-  a.st_cand = h->d_stats + 3 * h->max_inst;
-  a.st_sph = h->d_stats + 4 * h->max_inst;
-  a.st_pairs = h->d_stats + 5 * h->max_inst;
-  a.st_flags = reinterpret_cast<uint32_t*>(h->d_stats + 6 * h->max_inst);
-  a.st_key = h->d_stats + 7 * h->max_inst;
-  a.prof = h->d_prof;
-  a.warm = (h->prm.warm_start && a.l1_rows == nullptr) ? h->d_warm : nullptr;
-  // the handle's device state (snapshots, warm-start sets, prefilter records) is shared by all launches: a launch that
-  // arrives on another stream than the previous one waits for it
-  if (h->launched && st != h->last_stream) HIP_TRY(hipStreamWaitEvent(st, h->ev_done, 0));
+  stat_views(a, h->d_stats.get(), (size_t)h->max_inst);
+  a.prof = h->d_prof.get();
+  a.warm = (h->prm.warm_start && a.l1_rows == nullptr) ? h->d_warm.get() : nullptr;
+  HIP_TRY(join_stream(h, st));
   h->last_stream = st;
   a.bounds = nullptr, a.pos = nullptr, a.order = nullptr;
   const bool ordered = a.warm != nullptr && h->order_min > 0 && a.n_inst >= h->order_min;
-  if (ordered) a.order = h->d_order;
-  const bool packed = h->defer_done && a.l1_rows == nullptr && h->prepass_for == a.plans && h->prepass_n_rob == a.n_rob &&
-                      h->prepass_n_inst == a.n_inst && h->prepass_ordered == ordered;
-  h->prepass_for = nullptr;  // (good for one solve: the plans change with the commit that follows it)
+  if (ordered) a.order = pp.d_order.get();
+  const bool packed = h->defer_done && a.l1_rows == nullptr && pp.plans == a.plans && pp.n_rob == a.n_rob && pp.n_inst == a.n_inst && pp.ordered == ordered;
+  pp.plans = nullptr;  // (good for one solve: the plans change with the commit that follows it)
   // the set-up map of every instance as one product on the matrix cores (k_plan_prepass, setup_map_tile): rides on the pre-pass launch
   SetupMapArgs sm{};
   a.setup = nullptr;
-  if (a.l1_rows == nullptr && h->setup_mfma && h->d_setup != nullptr) {
-    sm.c = h->d_consts, sm.state = a.state, sm.ref = a.ref, sm.out = h->d_setup, sm.n_inst = a.n_inst, sm.N = h->N, sm.nk = 3 * h->n + 12;
+  if (a.l1_rows == nullptr && h->setup_mfma) {
+    sm.c = h->d_consts.get(), sm.state = a.state, sm.ref = a.ref, sm.out = pp.d_setup.get(), sm.n_inst = a.n_inst, sm.N = h->N, sm.nk = 3 * h->n + 12;
     sm.row_tiles = (sm.nk + 15) / 16;
-    a.setup = h->d_setup;
+    a.setup = pp.d_setup.get();
   }
   const int sm_blocks = sm.out != nullptr ? (sm.row_tiles * ((a.n_inst + 15) / 16) + 3) / 4 : 0;
   if (packed) {
-    a.pos = h->d_pos;
-    a.bounds = a.n_rob >= h->bounds_min ? h->d_bounds : nullptr;
+    a.pos = pp.d_pos.get();
+    a.bounds = a.n_rob >= h->bounds_min ? pp.d_bounds.get() : nullptr;
     if (sm_blocks > 0) {  // (the device-resident loop packs the plans elsewhere: the tiles alone)
       sm.first_block = 0;
-      hipLaunchKernelGGL(k_plan_prepass, dim3(sm_blocks), dim3(256), 0, st, h->N, 0, a.plans, a.has_plan, h->d_pos, nullptr, 0, a.st_key, a.agent_id, nullptr, sm);
+      hipLaunchKernelGGL(k_plan_prepass, dim3(sm_blocks), dim3(256), 0, st, h->N, 0, a.plans, a.has_plan, pp.d_pos.get(), nullptr, 0, a.st_key, a.agent_id, nullptr, sm);
       HIP_TRY(hipGetLastError());
     }
   } else if (a.l1_rows == nullptr) {
-    const bool pre = a.n_rob >= h->bounds_min;
+    double* const bounds = a.n_rob >= h->bounds_min ? pp.d_bounds.get() : nullptr;
     sm.first_block = (a.n_rob + 15) / 16 + (ordered ? 1 : 0);
     hipLaunchKernelGGL(k_plan_prepass, dim3(sm.first_block + sm_blocks), dim3(256), 0, st, h->N, a.n_rob, a.plans, a.has_plan,
-                       h->d_pos, pre ? h->d_bounds : nullptr, a.n_inst, a.st_key, a.agent_id, ordered ? h->d_order : nullptr, sm);
+                       pp.d_pos.get(), bounds, a.n_inst, a.st_key, a.agent_id, ordered ? pp.d_order.get() : nullptr, sm);
     HIP_TRY(hipGetLastError());
-    a.pos = h->d_pos;
-    a.bounds = pre ? h->d_bounds : nullptr;
+    a.pos = pp.d_pos.get();
+    a.bounds = bounds;
   } else if (ordered) {
-    hipLaunchKernelGGL(k_launch_order, dim3(1), dim3(256), 0, st, a.n_inst, a.st_key, a.agent_id, h->d_order);
+    hipLaunchKernelGGL(k_launch_order, dim3(1), dim3(256), 0, st, a.n_inst, a.st_key, a.agent_id, pp.d_order.get());
     HIP_TRY(hipGetLastError());
   }
   // one workgroup per agent-replan. The active-set iteration runs on wave 0 (factorisation in its registers);
   // with 256 threads the other three waves of the CU share the sweeps, the set-up and the leaf test.
   int rc;
-  if (h->time_kernel) HIP_TRY(hipEventRecord(h->ev_k0, st));
+  if (h->time_kernel) HIP_TRY(h->kernel_time.record_start(st));
   // `small`: a shape of this launch shares a CU (per_cu > 1), i.e. has a reduced staging area. It follows the shapes actually
   // launched, not the thresholds: with HDSM_DUO_MIN=0 and HDSM_QUAD_MIN / HDSM_TRI_MIN set by hand the two can disagree.
   bool small = false;
@@ -1021,8 +977,8 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
     return launch_shape(h, s, x, st, blocks);
   };
   a.warm_out = a.warm;
-  a.tree_flag = h->d_tree_flag;
-  a.ovf_flag = h->d_ovf_flag, a.rescue = 0;
+  a.tree_flag = h->tree_flag.dev();
+  a.ovf_flag = h->ovf_flag.dev(), a.rescue = 0;
   // nodes after which an instance is handed over: small batches leave most CUs idle, so sub-blocks are free; in a batch that
   // fills the GPU every handed-over instance costs poly_hor set-ups and sweeps on busy CUs, so only the deep trees go
   // (measured on MI355X with the hand-over records of round 5 — a hand-over costs about one node, no search is repeated: cfg 3, 256
@@ -1041,53 +997,55 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   // does not depend on numerical noise), pruning against the best objective any of them has found (one atomicMin per
   // incumbent); (3) a merge that keeps the best answer. Same answers as the one-kernel form: the search is exact either way.
   bool split = h->split_mode == 1;
-  if (h->split_mode == 2 && h->h_tree_flag != nullptr) {
+  if (h->split_mode == 2) {
     // The word is raised by kernels that may still be running when the next launch is enqueued (callers that queue dozens of
     // rounds back to back see it dozens of launches late), so a sighting keeps the split form on for the next 256 launches:
     // deep trees persist over rounds, and a split launch in which nothing is handed over costs three near-empty kernels.
-    if (*h->h_tree_flag != 0) *h->h_tree_flag = 0, h->split_ttl = 256;
+    if (*h->tree_flag.host() != 0) *h->tree_flag.host() = 0, h->split_ttl = 256;
     if (h->split_ttl > 0) split = true, --h->split_ttl;
   }
   // pass 2 of a split launch: persistent workgroups, as many as fit the GPU at once (per_cu of the shape per CU)
   const hdsm::Shape items = hdsm::pick_shape(knobs, 0, hdsm::PASS_ITEMS);
-  if (split && !h->sub_ready) split = ensure_sub(h, items) == hipSuccess;
+  if (split && !sub.ready() && sub.alloc(*h, items) != hipSuccess) {  // (allocated by the first split launch)
+    (void)hipGetLastError();  // nothing of it is left, the error is cleared: the handle goes on without split launches
+    h->split_mode = 0, split = false;
+  }
   if (!split) {
     rc = solve(a, a.n_inst);
   } else {
-    a.split_budget = budget, a.split_info = h->d_split, a.tree_mark = 0;  // (a.tree_flag stays: k_split_merge raises it for trees that are still deep)
-    a.recs = h->d_recs, a.rec_cand = h->d_rec_cand, a.rec_mw = h->d_rec_mw, a.rec_src = h->d_rec_src, a.rec_count = h->d_rec_count, a.items = h->d_items;
-    a.rec_cap = h->rec_cap, a.rows_cap = h->rows_cap, a.items_cap = h->items_cap, a.inc_bits = nullptr, a.node_pool = nullptr, a.item_status = h->d_sub_status;
+    a.split_budget = budget, a.split_info = sub.d_split.get(), a.tree_mark = 0;  // (a.tree_flag stays: k_split_merge raises it for trees that are still deep)
+    a.recs = sub.d_recs.get(), a.rec_cand = sub.d_rec_cand.get(), a.rec_mw = sub.d_rec_mw.get(), a.rec_src = sub.d_rec_src.get();
+    a.rec_count = sub.d_rec_count.get(), a.items = sub.d_items.get(), a.item_status = sub.d_sub_status.get();
+    a.rec_cap = h->rec_cap, a.rows_cap = sub.rows_cap, a.items_cap = sub.items_cap, a.inc_bits = nullptr, a.node_pool = nullptr;
     // the node budget is the INSTANCE's: every item starts with a small share of what pass 1 left of it and hands the unused part
     // back to the instance's pool when it finishes; an item that has used its share draws from that pool (NODE_CHUNK at a time)
     const int total_nodes = h->prm.max_nodes > 0 ? h->prm.max_nodes : 2000;
     const int left_nodes = total_nodes - budget > 64 ? total_nodes - budget : 64;
     const int node_cap = left_nodes / 128 > 0 ? left_nodes / 128 : 1;
     a.nodes_pool0 = left_nodes, a.node_cap = node_cap;
-    HIP_TRY(hipMemsetAsync(h->d_rec_count, 0, 8 * sizeof(int32_t), st));
-    HIP_TRY(hipMemsetAsync(h->d_slot_busy, 0, (size_t)h->pool_cap * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(sub.d_rec_count.get(), 0, 8 * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(sub.d_slot_busy.get(), 0, (size_t)sub.pool_cap * sizeof(int32_t), st));
     hdsm::Args a1 = a;
-    a1.inc_bits = h->d_inc, a1.node_pool = h->d_node_pool;  // (pass 1 only WRITES them, at a hand-over: its own search runs on Consts::max_nodes)
+    a1.inc_bits = sub.d_inc.get(), a1.node_pool = sub.d_node_pool.get();  // (pass 1 only WRITES them, at a hand-over: its own search runs on Consts::max_nodes)
     rc = solve(a1, a.n_inst);
     if (rc) return rc;
     hdsm::Args b = a;
-    b.item_mode = 1, b.order = nullptr, b.inc_bits = h->d_inc, b.node_pool = h->d_node_pool, b.tree_flag = nullptr;
-    b.traj = h->d_sub_traj, b.ctrl = h->d_sub_ctrl, b.used = h->d_sub_used, b.status = h->d_sub_status, b.obj = h->d_sub_obj;
-    b.scratch = h->d_sub_scratch, b.warm_out = h->d_sub_warm, b.prof = nullptr, b.pool_cap = h->pool_cap, b.slot_busy = h->d_slot_busy, b.item_total = h->d_item_total;
+    b.item_mode = 1, b.order = nullptr, b.inc_bits = sub.d_inc.get(), b.node_pool = sub.d_node_pool.get(), b.tree_flag = nullptr;
+    b.traj = sub.d_sub_traj.get(), b.ctrl = sub.d_sub_ctrl.get(), b.used = sub.d_sub_used.get(), b.status = sub.d_sub_status.get(), b.obj = sub.d_sub_obj.get();
+    b.scratch = sub.d_sub_scratch.get(), b.warm_out = sub.d_sub_warm.get(), b.prof = nullptr, b.pool_cap = sub.pool_cap, b.slot_busy = sub.d_slot_busy.get();
+    b.item_total = h->item_total.dev();
     b.split_budget = h->item_budget;  // an item whose subtree outgrows this many nodes hands over again (0: never)
     // ... or, while workgroups are waiting for items, this many: 2 in a batch that leaves CUs idle (cfg 3: 0.84 ms against 1.14 without),
     // 16 in one that fills the GPU (every look at the queue is two device-scope reads per node: cfg 5 8.15 ms with 2 - 4, 7.5 with >= 8)
     b.split_min = h->item_min > 0 ? h->item_min : (roomy ? 2 : 8);
     b.poll_sleep = h->poll_sleep;
-    int32_t* ss = h->d_sub_stats;
-    const size_t GI = (size_t)h->items_cap;
-    b.st_iters = ss, b.st_nodes = ss + GI, b.st_sweeps = ss + 2 * GI, b.st_cand = ss + 3 * GI, b.st_sph = ss + 4 * GI, b.st_pairs = ss + 5 * GI;
-    b.st_flags = reinterpret_cast<uint32_t*>(ss + 6 * GI), b.st_key = ss + 7 * GI;
+    stat_views(b, sub.d_sub_stats.get(), (size_t)sub.items_cap);
     small = small || hdsm::SHAPES[items].per_cu > 1;
     // the grid: an upper bound of the items of this launch — four times what the last split launch queued (the merge leaves the
     // count in pinned host memory), at least 4096; a launch that outgrows it leaves items pending and their instances end as LIMIT
     int grid = 4096;
-    if (h->h_item_total != nullptr && 4 * *h->h_item_total > grid) grid = 4 * *h->h_item_total;
-    if (grid > h->items_cap) grid = h->items_cap;
+    if (4 * *h->item_total.host() > grid) grid = 4 * *h->item_total.host();
+    if (grid > sub.items_cap) grid = sub.items_cap;
     rc = launch_shape(h, items, b, st, grid);
     if (rc) return rc;
     hipLaunchKernelGGL(k_split_merge, dim3(a.n_inst), dim3(64), 0, st, h->N, h->P, a, b);
@@ -1100,105 +1058,22 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   // launches, every launch that used such a kernel is followed by a rescue pass — the one-per-CU kernel over the batch, in
   // which only the instances that carry the flag are solved again (the host-buffer entry point adds it at once, see hdsm_replan).
   h->last_small = small, h->last_args = a;
-  if (small && h->h_ovf_flag != nullptr) {
-    if (*h->h_ovf_flag != 0) *h->h_ovf_flag = 0, h->rescue_ttl = 256;
+  if (small) {
+    if (*h->ovf_flag.host() != 0) *h->ovf_flag.host() = 0, h->rescue_ttl = 256;
     if (h->rescue_ttl > 0) {
       --h->rescue_ttl;
       rc = launch_rescue(h, a, st);
       if (rc) return rc;
     }
   }
-  if (h->time_kernel) {
-    HIP_TRY(hipEventRecord(h->ev_k1, st));
-    h->timed = true;
-  }
-  if (!h->defer_done) HIP_TRY(hipEventRecord(h->ev_done, st));
-  h->launched = true;
+  if (h->time_kernel) HIP_TRY(h->kernel_time.record_stop(st));
+  HIP_TRY(mark_done(h, st));
   return HDSM_OK;
-}
-
-template <class T>
-hipError_t dmalloc(T** p, size_t count) {
-  return hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T));
-}
-
-// grow-only scratch: reallocated (after draining the handle's stream) only when a call needs more than any before
-hipError_t ensure(Handle* h, Handle::Buf& b, size_t bytes) {
-  if (bytes <= b.cap) return hipSuccess;
-  hipError_t e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return e;
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr, b.cap = 0;
-  e = hipMalloc(&b.p, bytes);
-  if (e == hipSuccess) b.cap = bytes;
-  return e;
 }
 
 int64_t scratch_stride_for(int n) {
   return n <= hdsm::SPLIT_N_MAX ? (int64_t)hdsm::Solver<32, hdsm::CMAX30>::SNAP_STRIDE * hdsm::MAXH
                  : (int64_t)hdsm::Solver<48, hdsm::CMAX48>::SNAP_STRIDE * hdsm::MAXH;
-}
-
-// state of the split launches, allocated on the first one: the hand-over records of pass 1 with their staged rows, the item queue,
-// outputs / statistics / guesses per item, snapshot scratch for the persistent workgroups of pass 2
-hipError_t ensure_sub(Handle* h, hdsm::Shape items) {
-  const size_t N = (size_t)h->N;
-  // (resident workgroups of pass 2 per CU: per_cu of its shape, see the LDS checks at SHAPE_LAUNCH)
-  h->sub_slots_n = hdsm::SHAPES[items].per_cu * h->cus;
-  h->rows_cap = hdsm::SHAPES[items].cmax;
-  // (rec_cap — records: one per instance that hands its search over + one per item that hands over again — set by hdsm_create)
-  h->items_cap = h->rec_cap * 16 < 4096 ? 4096 : h->rec_cap * 16;
-  // snapshot scratch of pass 2: one slot per workgroup that can be resident + one per record (an item that hands over again leaves
-  // its slot to its record for the rest of the launch)
-  h->pool_cap = h->sub_slots_n + h->rec_cap;
-  const size_t G = (size_t)h->items_cap, R = (size_t)h->rec_cap;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t r) {
-    if (e == hipSuccess) e = r;
-  };
-  ok(dmalloc(&h->d_recs, R)), ok(dmalloc(&h->d_rec_cand, R * h->rows_cap * 4)), ok(dmalloc(&h->d_rec_mw, R * h->rows_cap)), ok(dmalloc(&h->d_rec_src, R * h->rows_cap));
-  ok(dmalloc(&h->d_rec_count, 8 + R)), ok(dmalloc(&h->d_items, G)), ok(dmalloc(&h->d_slot_busy, (size_t)h->pool_cap));
-  ok(dmalloc(&h->d_split, 2 * (size_t)h->max_inst)), ok(dmalloc(&h->d_inc, (size_t)h->max_inst)), ok(dmalloc(&h->d_node_pool, (size_t)h->max_inst));
-  ok(dmalloc(&h->d_sub_stats, 8 * G)), ok(dmalloc(&h->d_sub_warm, (hdsm::MAXNV + 2) * G)), ok(dmalloc(&h->d_sub_status, G));
-  ok(dmalloc(&h->d_sub_traj, G * (N + 1) * 9)), ok(dmalloc(&h->d_sub_ctrl, G * N * 3)), ok(dmalloc(&h->d_sub_obj, G)), ok(dmalloc(&h->d_sub_used, G * h->P));
-  ok(dmalloc(&h->d_sub_scratch, (size_t)h->pool_cap * (size_t)h->scratch_stride));
-  if (e == hipSuccess) e = hipMemset(h->d_split, 0, 2 * (size_t)h->max_inst * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemset(h->d_rec_count, 0, 8 * sizeof(int32_t));
-  h->sub_ready = e == hipSuccess;
-  if (!h->sub_ready) {  // partial failure: give back what was allocated, clear the pending error — the handle goes on without split launches
-    void** sub[] = {(void**)&h->d_recs, (void**)&h->d_rec_cand, (void**)&h->d_rec_mw, (void**)&h->d_rec_src, (void**)&h->d_rec_count, (void**)&h->d_items, (void**)&h->d_slot_busy,
-                    (void**)&h->d_split, (void**)&h->d_inc, (void**)&h->d_node_pool, (void**)&h->d_sub_stats,
-                    (void**)&h->d_sub_warm, (void**)&h->d_sub_status, (void**)&h->d_sub_traj, (void**)&h->d_sub_ctrl, (void**)&h->d_sub_obj,
-                    (void**)&h->d_sub_used, (void**)&h->d_sub_scratch};
-    for (void** p : sub) {
-      if (*p) (void)hipFree(*p);
-      *p = nullptr;
-    }
-    (void)hipGetLastError();
-    h->split_mode = 0;
-  }
-  return e;
-}
-
-void free_all(Handle* h) {
-  void* sub[] = {h->d_recs, h->d_rec_cand, h->d_rec_mw, h->d_rec_src, h->d_rec_count, h->d_items, h->d_slot_busy, h->d_split, h->d_inc, h->d_node_pool, h->d_sub_stats, h->d_sub_warm,
-                 h->d_sub_status, h->d_sub_traj, h->d_sub_ctrl, h->d_sub_obj, h->d_sub_used, h->d_sub_scratch};
-  for (void* p : sub)
-    if (p) (void)hipFree(p);
-  if (h->h_tree_flag) (void)hipHostFree(h->h_tree_flag);
-  if (h->h_item_total) (void)hipHostFree(h->h_item_total);
-  if (h->h_ovf_flag) (void)hipHostFree(h->h_ovf_flag);
-  if (h->h_out) (void)hipHostFree(h->h_out);
-  void* ptrs[] = {h->d_warm, h->d_prof, h->d_consts, h->d_scratch, h->d_stats, h->d_agent, h->d_npoly, h->d_nrows, h->d_status,
-                  h->d_state,  h->d_ref,     h->d_A,     h->d_b,     h->d_plans, h->d_bounds, h->d_setup, h->d_traj,  h->d_ctrl,
-                  h->d_obj,    h->d_has,     h->d_used,  h->d_pos,   h->d_rpos,  h->d_rsph,  h->d_zero,  h->d_order, h->b_planes.p, h->b_common.p,
-                  h->b_ncommon.p, h->b_path.p, h->b_cap.p, h->b_full.p, h->b_pv.p, h->b_np.p};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (h->ev_done) (void)hipEventDestroy(h->ev_done);
-  if (h->ev_k0) (void)hipEventDestroy(h->ev_k0);
-  if (h->ev_k1) (void)hipEventDestroy(h->ev_k1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
 }
 
 int check_common(Handle* h, int n_inst, int n_rob) {
@@ -1248,19 +1123,12 @@ int hdsm_create(const hdsm_params* params, int32_t max_instances, int32_t n_rob_
   if (device < 0 || device >= ndev) return set_err(HDSM_ERR_NO_DEVICE, "device ordinal out of range");
   HIP_TRY(hipSetDevice(device));
 
-  hdsm::Consts* hc = new (std::nothrow) hdsm::Consts;
+  std::unique_ptr<hdsm::Consts> hc(new (std::nothrow) hdsm::Consts);
   if (!hc) return set_err(HDSM_ERR_DEVICE, "out of host memory");
   const char* msg = nullptr;
-  int rc = hdsm::build_consts(params, hc, &msg);
-  if (rc) {
-    delete hc;
-    return set_err(rc, msg ? msg : "bad params");
-  }
-  Handle* h = new (std::nothrow) Handle;
-  if (!h) {
-    delete hc;
-    return set_err(HDSM_ERR_DEVICE, "out of host memory");
-  }
+  if (int rc = hdsm::build_consts(params, hc.get(), &msg)) return set_err(rc, msg ? msg : "bad params");
+  std::unique_ptr<Handle> h(new (std::nothrow) Handle);
+  if (!h) return set_err(HDSM_ERR_DEVICE, "out of host memory");
   h->device = device, h->max_inst = max_instances, h->n_rob_max = n_rob_max, h->prm = *params;
   h->N = hc->N, h->P = hc->P, h->RS = hc->RS, h->n = hc->n;
   // execution knobs: hdsm_params, then the environment (scripts); out-of-range values are ignored
@@ -1308,75 +1176,13 @@ int hdsm_create(const hdsm_params* params, int32_t max_instances, int32_t n_rob_
     if (hc->time_ticks < 1) hc->time_ticks = 1;
   }
   h->scratch_stride = scratch_stride_for(h->n);
-  const size_t I = (size_t)max_instances, N = (size_t)h->N, P = (size_t)h->P, RS = (size_t)h->RS;
-  hipError_t e = hipSuccess;
-  auto ok = [&](hipError_t r) {
-    if (e == hipSuccess) e = r;
-  };
+  hdsm_mem::FirstError ok;
   for (const ShapeLaunch& l : SHAPE_LAUNCH)  // (the instance state of most shapes is more than the default 64 KB of dynamic LDS)
     ok(hipFuncSetAttribute(reinterpret_cast<const void*>(l.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.shm));
-  ok(dmalloc(&h->d_consts, 1));
-  ok(dmalloc(&h->d_scratch, I * (size_t)h->scratch_stride));
-  ok(dmalloc(&h->d_stats, 8 * I));
-  ok(dmalloc(&h->d_warm, (hdsm::MAXNV + 2) * I));
-#if defined(HDSM_PROFILE) || defined(HDSM_TIMELINE)
-  ok(dmalloc(&h->d_prof, 32 * I));
-#endif
-  ok(dmalloc(&h->d_agent, I));
-  ok(dmalloc(&h->d_npoly, I));
-  ok(dmalloc(&h->d_nrows, I * P));
-  ok(dmalloc(&h->d_status, I));
-  ok(dmalloc(&h->d_state, I * 9));
-  ok(dmalloc(&h->d_ref, I * N * 6));
-  ok(dmalloc(&h->d_A, I * P * RS * 3));
-  ok(dmalloc(&h->d_b, I * P * RS));
-  ok(dmalloc(&h->d_plans, (size_t)n_rob_max * (N + 1) * 9));
-  ok(dmalloc(&h->d_bounds, (size_t)n_rob_max * 4));
-  ok(dmalloc(&h->d_setup, I * hdsm::KROWS));
-  ok(dmalloc(&h->d_pos, (size_t)n_rob_max * N * 3));
-  ok(dmalloc(&h->d_rpos, (size_t)n_rob_max * (N + 1) * 3));
-  ok(dmalloc(&h->d_rsph, (size_t)n_rob_max * 4));
-  ok(dmalloc(&h->d_zero, (size_t)n_rob_max));
-  ok(dmalloc(&h->d_order, 2 * I));
-  ok(dmalloc(&h->d_traj, I * (N + 1) * 9));
-  ok(dmalloc(&h->d_ctrl, I * N * 3));
-  ok(dmalloc(&h->d_obj, I));
-  ok(dmalloc(&h->d_has, (size_t)n_rob_max));
-  ok(dmalloc(&h->d_used, I * P));
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_ovf_flag), sizeof(int32_t), hipHostMallocMapped);
-  if (e == hipSuccess) {
-    *h->h_ovf_flag = 0;
-    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_ovf_flag), h->h_ovf_flag, 0);
-  }
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_tree_flag), sizeof(int32_t), hipHostMallocMapped);
-  if (e == hipSuccess) {
-    *h->h_tree_flag = 0;
-    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_tree_flag), h->h_tree_flag, 0);
-  }
-  if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_item_total), sizeof(int32_t), hipHostMallocMapped);
-  if (e == hipSuccess) {
-    *h->h_item_total = 0;
-    e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->d_item_total), h->h_item_total, 0);
-  }
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMemcpy(h->d_consts, hc, sizeof *hc, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev_k0);
-  if (e == hipSuccess) e = hipEventCreate(&h->ev_k1);
-  if (e == hipSuccess) e = hipMemset(h->d_stats, 0, 8 * I * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMemset(h->d_zero, 0, (size_t)n_rob_max);
-  // (the fetch kernel of hdsm_replan uploads only the rows of the static polyhedra that exist: the rest stays finite)
-  if (e == hipSuccess) e = hipMemset(h->d_A, 0, I * P * RS * 3 * sizeof(double));
-  if (e == hipSuccess) e = hipMemset(h->d_b, 0, I * P * RS * sizeof(double));
-  if (e == hipSuccess) e = hipMemset(h->d_plans, 0, (size_t)n_rob_max * (N + 1) * 9 * sizeof(double));
-  if (e == hipSuccess) e = hipMemset(h->d_warm, 0, (hdsm::MAXNV + 2) * I * sizeof(int32_t));
-  delete hc;
-  if (e != hipSuccess) {
-    free_all(h);
-    delete h;
-    return set_err(HDSM_ERR_DEVICE, std::string("hdsm_create: ") + hipGetErrorString(e));
-  }
-  *handle = h;
+  if (ok.ok()) ok(h->alloc_fixed());
+  if (ok.ok()) ok(hipMemcpy(h->d_consts.get(), hc.get(), sizeof *hc, hipMemcpyHostToDevice));
+  if (!ok.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_create: ") + hipGetErrorString(ok.e));
+  *handle = h.release();
   return HDSM_OK;
 }
 
@@ -1385,7 +1191,6 @@ void hdsm_destroy(void* handle) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  free_all(h);
   delete h;
 }
 
@@ -1490,10 +1295,11 @@ int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agen
     return set_err(HDSM_ERR_BAD_ARG, "null array argument");
   HIP_TRY(hipSetDevice(h->device));
   const size_t I = (size_t)n_inst, N = (size_t)h->N, P = (size_t)h->P, RS = (size_t)h->RS;
-  hipStream_t st = h->stream;
+  hdsm_handle::HostStaging& s = h->stage;
+  hipStream_t st = h->stream.get();
   const auto H2D = hipMemcpyHostToDevice;
   const auto D2H = hipMemcpyDeviceToHost;
-  if (h->launched && st != h->last_stream) HIP_TRY(hipStreamWaitEvent(st, h->ev_done, 0));
+  HIP_TRY(join_stream(h, st));
   bool in_mapped = true;
   {
     const void* hp[9] = {agent_id, state_curr, traj_ref, n_poly, n_rows_static, A_static, b_static, plans_all, has_plan};
@@ -1508,31 +1314,31 @@ int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agen
       f.agent_id = static_cast<const int32_t*>(dp[0]), f.state = static_cast<const double*>(dp[1]), f.ref = static_cast<const double*>(dp[2]);
       f.n_poly = static_cast<const int32_t*>(dp[3]), f.n_rows = static_cast<const int32_t*>(dp[4]), f.A = static_cast<const double*>(dp[5]);
       f.b = static_cast<const double*>(dp[6]), f.plans = static_cast<const double*>(dp[7]), f.has = static_cast<const uint8_t*>(dp[8]);
-      f.d_agent = h->d_agent, f.d_state = h->d_state, f.d_ref = h->d_ref, f.d_npoly = h->d_npoly, f.d_nrows = h->d_nrows;
-      f.d_A = h->d_A, f.d_b = h->d_b, f.d_plans = h->d_plans, f.d_has = h->d_has;
+      f.d_agent = s.d_agent.get(), f.d_state = s.d_state.get(), f.d_ref = s.d_ref.get(), f.d_npoly = s.d_npoly.get(), f.d_nrows = s.d_nrows.get();
+      f.d_A = s.d_A.get(), f.d_b = s.d_b.get(), f.d_plans = s.d_plans.get(), f.d_has = s.d_has.get();
       hipLaunchKernelGGL(k_fetch, dim3((unsigned)(n_inst + f.plan_blocks)), dim3(256), 0, st, f);
       HIP_TRY(hipGetLastError());
     }
   }
   if (!in_mapped) {
-    HIP_TRY(hipMemcpyAsync(h->d_agent, agent_id, I * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_state, state_curr, I * 9 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_ref, traj_ref, I * N * 6 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_npoly, n_poly, I * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_nrows, n_rows_static, I * P * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_A, A_static, I * P * RS * 3 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_b, b_static, I * P * RS * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_plans, plans_all, (size_t)n_rob * (N + 1) * 9 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(h->d_has, has_plan, (size_t)n_rob, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_agent.get(), agent_id, I * 4, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_state.get(), state_curr, I * 9 * 8, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_ref.get(), traj_ref, I * N * 6 * 8, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_npoly.get(), n_poly, I * 4, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_nrows.get(), n_rows_static, I * P * 4, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_A.get(), A_static, I * P * RS * 3 * 8, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_b.get(), b_static, I * P * RS * 8, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_plans.get(), plans_all, (size_t)n_rob * (N + 1) * 9 * 8, H2D, st));
+    HIP_TRY(hipMemcpyAsync(s.d_has.get(), has_plan, (size_t)n_rob, H2D, st));
   }
-  int rc = hdsm_replan_device(handle, n_inst, n_rob, h->d_agent, h->d_state, h->d_ref, h->d_npoly, h->d_nrows,
-                              h->d_A, h->d_b, h->d_plans, h->d_has, h->d_traj, h->d_ctrl, h->d_used,
-                              h->d_status, h->d_obj, st);
+  int rc = hdsm_replan_device(handle, n_inst, n_rob, s.d_agent.get(), s.d_state.get(), s.d_ref.get(), s.d_npoly.get(), s.d_nrows.get(),
+                              s.d_A.get(), s.d_b.get(), s.d_plans.get(), s.d_has.get(), s.d_traj.get(), s.d_ctrl.get(), s.d_used.get(),
+                              s.d_status.get(), s.d_obj.get(), st);
   if (rc) return rc;
-  if (h->last_small && h->h_ovf_flag != nullptr && h->rescue_ttl == 0) {  // (a launch that already carried the rescue pass needs no second one)
+  if (h->last_small && h->rescue_ttl == 0) {  // (a launch that already carried the rescue pass needs no second one)
     HIP_TRY(hipStreamSynchronize(st));
-    if (*h->h_ovf_flag != 0) {  // an instance ran out of staging rows in a shared-CU kernel: solve it again now, with the large area
-      *h->h_ovf_flag = 0, h->rescue_ttl = 256;
+    if (*h->ovf_flag.host() != 0) {  // an instance ran out of staging rows in a shared-CU kernel: solve it again now, with the large area
+      *h->ovf_flag.host() = 0, h->rescue_ttl = 256;
       rc = launch_rescue(h, h->last_args, st);
       if (rc) return rc;
     }
@@ -1550,29 +1356,23 @@ int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agen
     if (!mapped) dp[0] = nullptr;
   }
   if (dp[0] != nullptr) {
-    hipLaunchKernelGGL(k_deliver, dim3((unsigned)((I + 3) / 4)), dim3(256), 0, st, n_inst, (int)trj, (int)ctl, (int)P, h->d_traj, h->d_ctrl, h->d_obj,
-                       h->d_status, h->d_used, static_cast<double*>(dp[0]), static_cast<double*>(dp[1]), static_cast<double*>(dp[2]),
+    hipLaunchKernelGGL(k_deliver, dim3((unsigned)((I + 3) / 4)), dim3(256), 0, st, n_inst, (int)trj, (int)ctl, (int)P, s.d_traj.get(), s.d_ctrl.get(), s.d_obj.get(),
+                       s.d_status.get(), s.d_used.get(), static_cast<double*>(dp[0]), static_cast<double*>(dp[1]), static_cast<double*>(dp[2]),
                        static_cast<int32_t*>(dp[3]), static_cast<uint8_t*>(dp[4]));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
   } else {
-    const size_t need = I * (trj * 8 + ctl * 8 + 8 + 4 + P);
-    if (need > h->h_out_cap) {
-      if (h->h_out) (void)hipHostFree(h->h_out);
-      h->h_out = nullptr, h->h_out_cap = 0;
-      HIP_TRY(hipHostMalloc(&h->h_out, need, hipHostMallocDefault));
-      h->h_out_cap = need;
-    }
-    double* o_traj = static_cast<double*>(h->h_out);
+    HIP_TRY(s.out.ensure(I * (trj * 8 + ctl * 8 + 8 + 4 + P)));
+    double* o_traj = static_cast<double*>(s.out.get());
     double* o_ctrl = o_traj + I * trj;
     double* o_obj = o_ctrl + I * ctl;
     int32_t* o_status = reinterpret_cast<int32_t*>(o_obj + I);
     uint8_t* o_used = reinterpret_cast<uint8_t*>(o_status + I);
-    HIP_TRY(hipMemcpyAsync(o_traj, h->d_traj, I * trj * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_ctrl, h->d_ctrl, I * ctl * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_obj, h->d_obj, I * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_status, h->d_status, I * 4, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_used, h->d_used, I * P, D2H, st));
+    HIP_TRY(hipMemcpyAsync(o_traj, s.d_traj.get(), I * trj * 8, D2H, st));
+    HIP_TRY(hipMemcpyAsync(o_ctrl, s.d_ctrl.get(), I * ctl * 8, D2H, st));
+    HIP_TRY(hipMemcpyAsync(o_obj, s.d_obj.get(), I * 8, D2H, st));
+    HIP_TRY(hipMemcpyAsync(o_status, s.d_status.get(), I * 4, D2H, st));
+    HIP_TRY(hipMemcpyAsync(o_used, s.d_used.get(), I * P, D2H, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (size_t k = 0; k < I; ++k) {
       status[k] = o_status[k];
@@ -1598,25 +1398,25 @@ int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t*
   HIP_TRY(hipSetDevice(h->device));
   const size_t I = (size_t)n_inst, N = (size_t)h->N;
   const size_t total = I * N * (size_t)n_rob * 4;
-  HIP_TRY(ensure(h, h->b_planes, total * sizeof(double)));
-  double* d_planes = static_cast<double*>(h->b_planes.p);
-  hipStream_t st = h->stream;
-  if (h->launched && st != h->last_stream) HIP_TRY(hipStreamWaitEvent(st, h->ev_done, 0));  // staging buffers are shared
-  hipError_t e = hipMemcpyAsync(h->d_agent, agent_id, I * 4, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->d_state, state_curr, I * 9 * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(h->d_plans, plans_all, (size_t)n_rob * (N + 1) * 9 * 8, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->d_has, has_plan, (size_t)n_rob, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
+  hdsm_handle::HostStaging& s = h->stage;
+  hipStream_t st = h->stream.get();
+  HIP_TRY(s.planes.ensure(total, st));
+  HIP_TRY(join_stream(h, st));  // staging buffers are shared
+  Copies cp{st};
+  cp(s.d_agent.get(), agent_id, I * 4, hipMemcpyHostToDevice);
+  cp(s.d_state.get(), state_curr, I * 9 * 8, hipMemcpyHostToDevice);
+  cp(s.d_plans.get(), plans_all, (size_t)n_rob * (N + 1) * 9 * 8, hipMemcpyHostToDevice);
+  cp(s.d_has.get(), has_plan, (size_t)n_rob, hipMemcpyHostToDevice);
+  if (cp.err.ok()) {
     const int64_t items = (int64_t)(total / 4);
     const int blocks = (int)((items + 255) / 256 > 4096 ? 4096 : (items + 255) / 256);
-    hipLaunchKernelGGL(k_tasc_planes, dim3(blocks), dim3(256), 0, st, h->d_consts, n_inst, n_rob, h->d_agent,
-                       h->d_state, h->d_plans, h->d_has, d_planes);
-    e = hipGetLastError();
+    hipLaunchKernelGGL(k_tasc_planes, dim3(blocks), dim3(256), 0, st, h->d_consts.get(), n_inst, n_rob, s.d_agent.get(),
+                       s.d_state.get(), s.d_plans.get(), s.d_has.get(), s.planes.get());
+    cp.err(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(planes, d_planes, total * 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_tasc_planes: ") + hipGetErrorString(e));
+  cp(planes, s.planes.get(), total * 8, hipMemcpyDeviceToHost);
+  if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
+  if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_tasc_planes: ") + hipGetErrorString(cp.err.e));
   return HDSM_OK;
 }
 
@@ -1634,7 +1434,8 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
   a.n_inst = n_inst, a.n_rob = n_rob, a.pmax = pmax, a.N = h->N, a.dt = h->prm.dt, a.cfg = *cfg;
   a.agent_id = agent_id, a.path = path, a.n_path = n_path, a.vel_cap = vel_cap, a.plans = plans_all;
   a.has_plan = has_plan, a.ref_full = ref_full, a.ref = ref, a.path_vel = path_vel;
-  a.rpos = h->d_rpos, a.rsph = h->d_rsph;
+  hdsm_handle::Prepass& pp = h->pre;
+  a.rpos = pp.d_rpos.get(), a.rsph = pp.d_rsph.get();
   for (int i = 0; i <= hdsm::MAXH; ++i) {
     double occ = 100 * std::pow(cfg->sens_other_agents, (double)i);  // AC:1791-1795
     occ = occ < 0 ? 0 : (occ > 100 ? 100 : occ);
@@ -1642,24 +1443,23 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
   }
   // d_rpos / d_rsph are scratch of the HANDLE: a call that arrives on another stream than the previous launch waits for it
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  if (h->launched && st != h->last_stream) HIP_TRY(hipStreamWaitEvent(st, h->ev_done, 0));
+  HIP_TRY(join_stream(h, st));
   h->last_stream = st;
   {
     // device-resident loop (defer_done: one stream, the solve of this round follows on the same plans): the pre-pass rides along
     const bool with_pre = h->defer_done;
     const bool ordered = with_pre && h->prm.warm_start && h->order_min > 0 && n_inst >= h->order_min;
     const bool pre = n_rob >= h->bounds_min;
-    hipLaunchKernelGGL(k_ref_pack, dim3((n_rob + 15) / 16 + (ordered ? 1 : 0)), dim3(256), 0, st, h->N, n_rob, plans_all, has_plan, h->d_rpos, h->d_rsph,
-                       with_pre ? h->d_pos : nullptr, with_pre && pre ? h->d_bounds : nullptr, n_inst, h->d_stats + 7 * h->max_inst, agent_id,
-                       ordered ? h->d_order : nullptr);
-    h->prepass_for = with_pre ? plans_all : nullptr, h->prepass_n_rob = n_rob, h->prepass_n_inst = n_inst, h->prepass_ordered = ordered;
+    hipLaunchKernelGGL(k_ref_pack, dim3((n_rob + 15) / 16 + (ordered ? 1 : 0)), dim3(256), 0, st, h->N, n_rob, plans_all, has_plan, pp.d_rpos.get(), pp.d_rsph.get(),
+                       with_pre ? pp.d_pos.get() : nullptr, with_pre && pre ? pp.d_bounds.get() : nullptr, n_inst, h->d_stats.get() + 7 * h->max_inst, agent_id,
+                       ordered ? pp.d_order.get() : nullptr);
+    pp.plans = with_pre ? plans_all : nullptr, pp.n_rob = n_rob, pp.n_inst = n_inst, pp.ordered = ordered;
   }
   HIP_TRY(hipGetLastError());
   if (n_inst >= 256) hipLaunchKernelGGL(k_reference<64>, dim3(n_inst), dim3(64), 0, st, a);
   else hipLaunchKernelGGL(k_reference<256>, dim3(n_inst), dim3(256), 0, st, a);
   HIP_TRY(hipGetLastError());
-  if (!h->defer_done) HIP_TRY(hipEventRecord(h->ev_done, st));
-  h->launched = true;
+  HIP_TRY(mark_done(h, st));
   return HDSM_OK;
 }
 
@@ -1675,36 +1475,32 @@ int hdsm_reference(void* handle, const hdsm_ref_config* cfg, int32_t n_inst, int
     if (n_path[k] < 1 || n_path[k] > pmax) return set_err(HDSM_ERR_BAD_ARG, "n_path[k] must be in [1, pmax]");
   HIP_TRY(hipSetDevice(h->device));
   const size_t I = (size_t)n_inst, N = (size_t)h->N;
-  hipStream_t st = h->stream;
-  hipError_t e = ensure(h, h->b_path, I * pmax * 3 * sizeof(double));
-  if (e == hipSuccess) e = ensure(h, h->b_cap, I * sizeof(double));
-  if (e == hipSuccess) e = ensure(h, h->b_full, I * (N + 1) * 6 * sizeof(double));
-  if (e == hipSuccess) e = ensure(h, h->b_pv, I * sizeof(double));
-  if (e == hipSuccess) e = ensure(h, h->b_np, I * sizeof(int32_t));
+  hdsm_handle::HostStaging& s = h->stage;
+  hipStream_t st = h->stream.get();
+  hipError_t e = s.path.ensure(I * pmax * 3, st);
+  if (e == hipSuccess) e = s.cap.ensure(I, st);
+  if (e == hipSuccess) e = s.full.ensure(I * (N + 1) * 6, st);
+  if (e == hipSuccess) e = s.pv.ensure(I, st);
+  if (e == hipSuccess) e = s.np.ensure(I, st);
   if (e != hipSuccess) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_reference: ") + hipGetErrorString(e));
-  double *d_path = static_cast<double*>(h->b_path.p), *d_cap = static_cast<double*>(h->b_cap.p),
-         *d_full = static_cast<double*>(h->b_full.p), *d_pv = static_cast<double*>(h->b_pv.p);
-  int32_t* d_np = static_cast<int32_t*>(h->b_np.p);
-  if (h->launched && st != h->last_stream) HIP_TRY(hipStreamWaitEvent(st, h->ev_done, 0));
-  auto cp = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, kind, st);
-  };
-  cp(d_path, path, I * pmax * 3 * 8, hipMemcpyHostToDevice);
-  cp(d_np, n_path, I * 4, hipMemcpyHostToDevice);
-  if (vel_cap) cp(d_cap, vel_cap, I * 8, hipMemcpyHostToDevice);
-  cp(h->d_agent, agent_id, I * 4, hipMemcpyHostToDevice);
-  cp(h->d_plans, plans_all, (size_t)n_rob * (N + 1) * 9 * 8, hipMemcpyHostToDevice);
-  cp(h->d_has, has_plan, (size_t)n_rob, hipMemcpyHostToDevice);
+  HIP_TRY(join_stream(h, st));
+  Copies cp{st};
+  cp(s.path.get(), path, I * pmax * 3 * 8, hipMemcpyHostToDevice);
+  cp(s.np.get(), n_path, I * 4, hipMemcpyHostToDevice);
+  if (vel_cap) cp(s.cap.get(), vel_cap, I * 8, hipMemcpyHostToDevice);
+  cp(s.d_agent.get(), agent_id, I * 4, hipMemcpyHostToDevice);
+  cp(s.d_plans.get(), plans_all, (size_t)n_rob * (N + 1) * 9 * 8, hipMemcpyHostToDevice);
+  cp(s.d_has.get(), has_plan, (size_t)n_rob, hipMemcpyHostToDevice);
   int rc = HDSM_OK;
-  if (e == hipSuccess)
-    rc = hdsm_reference_device(handle, cfg, n_inst, n_rob, h->d_agent, d_path, d_np, pmax, vel_cap ? d_cap : nullptr,
-                               h->d_plans, h->d_has, d_full, ref ? h->d_ref : nullptr, d_pv, st);
-  cp(ref_full, d_full, I * (N + 1) * 6 * 8, hipMemcpyDeviceToHost);
-  if (ref) cp(ref, h->d_ref, I * N * 6 * 8, hipMemcpyDeviceToHost);
-  cp(path_vel, d_pv, I * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (cp.err.ok())
+    rc = hdsm_reference_device(handle, cfg, n_inst, n_rob, s.d_agent.get(), s.path.get(), s.np.get(), pmax, vel_cap ? s.cap.get() : nullptr,
+                               s.d_plans.get(), s.d_has.get(), s.full.get(), ref ? s.d_ref.get() : nullptr, s.pv.get(), st);
+  cp(ref_full, s.full.get(), I * (N + 1) * 6 * 8, hipMemcpyDeviceToHost);
+  if (ref) cp(ref, s.d_ref.get(), I * N * 6 * 8, hipMemcpyDeviceToHost);
+  cp(path_vel, s.pv.get(), I * 8, hipMemcpyDeviceToHost);
+  if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
   if (rc) return rc;
-  if (e != hipSuccess) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_reference: ") + hipGetErrorString(e));
+  if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_reference: ") + hipGetErrorString(cp.err.e));
   return HDSM_OK;
 }
 
@@ -1713,7 +1509,7 @@ int hdsm_reset_warm_start(void* handle) {
   if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemset(h->d_warm, 0, (size_t)(hdsm::MAXNV + 2) * h->max_inst * sizeof(int32_t)));
+  HIP_TRY(hipMemset(h->d_warm.get(), 0, (size_t)(hdsm::MAXNV + 2) * h->max_inst * sizeof(int32_t)));
   return HDSM_OK;
 }
 
@@ -1729,7 +1525,7 @@ extern "C" int hdsm_internal_defer_done(void* handle, int on) {
 extern "C" int hdsm_internal_record_done(void* handle, void* hip_stream) {
   Handle* h = static_cast<Handle*>(handle);
   if (!h) return HDSM_ERR_BAD_ARG;
-  HIP_TRY(hipEventRecord(h->ev_done, static_cast<hipStream_t>(hip_stream)));
+  HIP_TRY(hipEventRecord(h->ev_done.get(), static_cast<hipStream_t>(hip_stream)));
   return HDSM_OK;
 }
 
@@ -1737,17 +1533,16 @@ int hdsm_set_kernel_timing(void* handle, int32_t on) {
   Handle* h = static_cast<Handle*>(handle);
   if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
   h->time_kernel = on != 0;
-  if (!h->time_kernel) h->timed = false;
+  if (!h->time_kernel) h->kernel_time.valid = false;
   return HDSM_OK;
 }
 
 int hdsm_last_kernel_ms(void* handle, float* ms) {
   Handle* h = static_cast<Handle*>(handle);
   if (!h || !ms) return set_err(HDSM_ERR_BAD_ARG, "null argument");
-  if (!h->timed) return set_err(HDSM_ERR_BAD_ARG, "no launch since hdsm_set_kernel_timing(handle, 1)");
+  if (!h->kernel_time.valid) return set_err(HDSM_ERR_BAD_ARG, "no launch since hdsm_set_kernel_timing(handle, 1)");
   HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipEventSynchronize(h->ev_k1));
-  HIP_TRY(hipEventElapsedTime(ms, h->ev_k0, h->ev_k1));
+  HIP_TRY(h->kernel_time.ms(ms));
   return HDSM_OK;
 }
 
@@ -1760,7 +1555,7 @@ int hdsm_last_stats(void* handle, int32_t n_inst, int32_t* qp_iters, int32_t* no
 #ifdef HDSM_TIMELINE
   {  // development aid: the launch seen from the instances (100 MHz clock): span, the slowest instance, late starters
     std::vector<long long> pr((size_t)n_inst * 32);
-    HIP_TRY(hipMemcpy(pr.data(), h->d_prof, pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
     long long t0 = pr[0], t1 = pr[1];
     int worst = 0, last = 0;
     double busy = 0;
@@ -1793,7 +1588,7 @@ int hdsm_last_stats(void* handle, int32_t n_inst, int32_t* qp_iters, int32_t* no
 #ifdef HDSM_PROFILE
   {  // development aid: phase cycle counters of the slowest instance and the batch mean
     std::vector<long long> pr((size_t)n_inst * 32);
-    HIP_TRY(hipMemcpy(pr.data(), h->d_prof, pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
     int worst = 0;
     double mean[32] = {0};
     for (int k = 0; k < n_inst; ++k) {
@@ -1819,7 +1614,7 @@ int hdsm_last_stats(void* handle, int32_t n_inst, int32_t* qp_iters, int32_t* no
   int32_t* dst[4] = {qp_iters, nodes, sweeps, cand};
   for (int k = 0; k < 4; ++k)
     if (dst[k])
-      HIP_TRY(hipMemcpy(dst[k], h->d_stats + (size_t)k * h->max_inst, (size_t)n_inst * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(dst[k], h->d_stats.get() + (size_t)k * h->max_inst, (size_t)n_inst * 4, hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 
@@ -1838,48 +1633,45 @@ int hdsm_solve(void* handle, int32_t n_inst, int32_t r_max, const double* state_
     return set_err(rc, msg ? msg : "bad level-1 input");
   HIP_TRY(hipSetDevice(h->device));
   const size_t I = (size_t)n_inst, N = (size_t)h->N, P = (size_t)h->P, RS = (size_t)h->RS;
-  hipStream_t st = h->stream;
-  HIP_TRY(ensure(h, h->b_common, sp.common.size() * sizeof(double)));
-  hipError_t e = ensure(h, h->b_ncommon, sp.n_common.size() * sizeof(int32_t));
-  double* d_common = static_cast<double*>(h->b_common.p);
-  int32_t* d_ncommon = static_cast<int32_t*>(h->b_ncommon.p);
-  if (e == hipSuccess && h->launched && st != h->last_stream) e = hipStreamWaitEvent(st, h->ev_done, 0);
+  hdsm_handle::HostStaging& s = h->stage;
+  hipStream_t st = h->stream.get();
+  HIP_TRY(s.common.ensure(sp.common.size(), st));
+  Copies cp{st};
+  cp.err(s.ncommon.ensure(sp.n_common.size(), st));
+  if (cp.err.ok()) cp.err(join_stream(h, st));
   const auto H2D = hipMemcpyHostToDevice;
   const auto D2H = hipMemcpyDeviceToHost;
   std::vector<int32_t> ids(I, -1);
-  auto cp = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, src, bytes, kind, st);
-  };
-  cp(d_common, sp.common.data(), sp.common.size() * 8, H2D);
-  cp(d_ncommon, sp.n_common.data(), sp.n_common.size() * 4, H2D);
-  cp(h->d_agent, ids.data(), I * 4, H2D);
-  cp(h->d_state, state_curr, I * 9 * 8, H2D);
-  cp(h->d_ref, traj_ref, I * N * 6 * 8, H2D);
-  cp(h->d_npoly, sp.n_poly.data(), I * 4, H2D);
-  cp(h->d_nrows, sp.n_rows_static.data(), I * P * 4, H2D);
-  cp(h->d_A, sp.A_static.data(), I * P * RS * 3 * 8, H2D);
-  cp(h->d_b, sp.b_static.data(), I * P * RS * 8, H2D);
-  cp(h->d_traj, traj_out, I * (N + 1) * 9 * 8, H2D);
-  cp(h->d_ctrl, ctrl_out, I * N * 3 * 8, H2D);
-  cp(h->d_used, poly_used, I * P, H2D);
-  cp(h->d_obj, obj, I * 8, H2D);
+  cp(s.common.get(), sp.common.data(), sp.common.size() * 8, H2D);
+  cp(s.ncommon.get(), sp.n_common.data(), sp.n_common.size() * 4, H2D);
+  cp(s.d_agent.get(), ids.data(), I * 4, H2D);
+  cp(s.d_state.get(), state_curr, I * 9 * 8, H2D);
+  cp(s.d_ref.get(), traj_ref, I * N * 6 * 8, H2D);
+  cp(s.d_npoly.get(), sp.n_poly.data(), I * 4, H2D);
+  cp(s.d_nrows.get(), sp.n_rows_static.data(), I * P * 4, H2D);
+  cp(s.d_A.get(), sp.A_static.data(), I * P * RS * 3 * 8, H2D);
+  cp(s.d_b.get(), sp.b_static.data(), I * P * RS * 8, H2D);
+  cp(s.d_traj.get(), traj_out, I * (N + 1) * 9 * 8, H2D);
+  cp(s.d_ctrl.get(), ctrl_out, I * N * 3 * 8, H2D);
+  cp(s.d_used.get(), poly_used, I * P, H2D);
+  cp(s.d_obj.get(), obj, I * 8, H2D);
   int rc = HDSM_OK;
-  if (e == hipSuccess) {
+  if (cp.err.ok()) {
     hdsm::Args a{};
-    a.n_inst = n_inst, a.n_rob = 0, a.agent_id = h->d_agent, a.state = h->d_state, a.ref = h->d_ref;
-    a.n_poly = h->d_npoly, a.n_rows = h->d_nrows, a.A = h->d_A, a.b = h->d_b, a.plans = h->d_plans;
-    a.has_plan = h->d_zero, a.traj = h->d_traj, a.ctrl = h->d_ctrl, a.used = h->d_used, a.status = h->d_status;
-    a.obj = h->d_obj, a.l1_rows = d_common, a.l1_nrows = d_ncommon, a.l1_rmax = sp.rc_max;
+    a.n_inst = n_inst, a.n_rob = 0, a.agent_id = s.d_agent.get(), a.state = s.d_state.get(), a.ref = s.d_ref.get();
+    a.n_poly = s.d_npoly.get(), a.n_rows = s.d_nrows.get(), a.A = s.d_A.get(), a.b = s.d_b.get(), a.plans = s.d_plans.get();
+    a.has_plan = h->d_zero.get(), a.traj = s.d_traj.get(), a.ctrl = s.d_ctrl.get(), a.used = s.d_used.get(), a.status = s.d_status.get();
+    a.obj = s.d_obj.get(), a.l1_rows = s.common.get(), a.l1_nrows = s.ncommon.get(), a.l1_rmax = sp.rc_max;
     rc = launch(h, a, st);
   }
-  cp(traj_out, h->d_traj, I * (N + 1) * 9 * 8, D2H);
-  cp(ctrl_out, h->d_ctrl, I * N * 3 * 8, D2H);
-  cp(poly_used, h->d_used, I * P, D2H);
-  cp(status, h->d_status, I * 4, D2H);
-  cp(obj, h->d_obj, I * 8, D2H);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  cp(traj_out, s.d_traj.get(), I * (N + 1) * 9 * 8, D2H);
+  cp(ctrl_out, s.d_ctrl.get(), I * N * 3 * 8, D2H);
+  cp(poly_used, s.d_used.get(), I * P, D2H);
+  cp(status, s.d_status.get(), I * 4, D2H);
+  cp(obj, s.d_obj.get(), I * 8, D2H);
+  if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
   if (rc) return rc;
-  if (e != hipSuccess) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_solve: ") + hipGetErrorString(e));
+  if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_solve: ") + hipGetErrorString(cp.err.e));
   return HDSM_OK;
 }
 
@@ -1891,7 +1683,7 @@ int hdsm_last_sweep_stats(void* handle, int32_t n_inst, int32_t* sphere_records,
   void* dst[3] = {sphere_records, pairs, flags};
   for (int k = 0; k < 3; ++k)
     if (dst[k])
-      HIP_TRY(hipMemcpy(dst[k], h->d_stats + (size_t)(4 + k) * h->max_inst, (size_t)n_inst * 4, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(dst[k], h->d_stats.get() + (size_t)(4 + k) * h->max_inst, (size_t)n_inst * 4, hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 

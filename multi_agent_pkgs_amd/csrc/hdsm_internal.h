@@ -1,8 +1,6 @@
 // hdsm_internal.h — the entry points that cross translation units of csrc/ without being in include/, each declared ONCE. The file
 // that defines one and every file that calls one include this header, so a signature that drifts does not compile (they are
 // extern "C" — two are called from the tests through ctypes — and a mismatch would still link).
-// The one exception: hdsm_api.hip defines hdsm_internal_defer_done / _record_done without including it (bench.py keys its stored
-// counter records on a hash of that file, so it is not edited for a declaration).
 #pragma once
 #include "../../include/hdsm_swarm.h"
 

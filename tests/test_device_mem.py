@@ -1,4 +1,4 @@
-"""csrc/device_mem.h (DevBuf, DevEvent, TimedInterval, FirstError) on the CPU: tests/device_mem_check.cpp is a stand-alone program
+"""csrc/device_mem.h (the owners) and csrc/hdsm_handle.h (the solver handle built from them) on the CPU: tests/device_mem_check.cpp is a stand-alone program
 that includes the header with its host seam (HDSM_DEVICE_MEM_HOST: malloc'ed blocks, a count of the live ones, a knob that fails
 the k-th allocation) and asserts the ownership rules itself; it is built here with the address and undefined-behaviour sanitizers
 and must exit 0. Nothing of it is loaded into Python and nothing of the HIP runtime is linked."""

@@ -630,3 +630,48 @@ def test_an_array_that_runs_past_its_registered_range_never_reaches_the_fetch_ke
         for a in pinned:
             hdsm.host_unregister(a)
     assert (got["status"] == plain["status"]).all() and np.abs(got["traj"][ok] - plain["traj"][ok]).max() < 1e-9
+
+
+def test_one_handle_through_lazy_state_and_growing_scratch_matches_fresh_handles(hdsm, monkeypatch):
+    """The handle owns its device memory by type (csrc/hdsm_handle.h); what the host program of tests/test_device_mem.py cannot see
+    is whether the right pointers still reach the right kernels once the lazily allocated split state has appeared and the grow-only
+    scratch of the host-pointer entry points has been reallocated mid-life. One handle serves small calls, then calls that outgrow
+    every scratch block and the pinned output block, then a small call again; each answer is compared with the same call on a handle
+    of its own. reference and tasc_planes use no atomics: bit-equal. Then the handle, with every optional part present, is destroyed."""
+    monkeypatch.setenv("HDSM_SPLIT", "1")  # (read by hdsm_create: the first launch allocates the split state)
+    prm = agile_params(10, max_rows_static=18, warm_start=False)
+    sn = problems.swarm_snapshot(prm, 16, seed=3)
+    cfg = agile_ref_config()
+    path = np.zeros((16, 3, 3))
+    path[:, 0] = np.asarray(sn["state"])[:, :3]
+    path[:, 1] = path[:, 0] + [2.0, 0.5, 0.0]
+    path[:, 2] = path[:, 1] + [1.0, -1.0, 0.5]
+    n_path = np.full(16, 3, np.int32)
+    n_path[::3] = 2
+    cap = np.linspace(1.0, 4.0, 16)
+
+    def replan(sol, n):
+        return sol.replan(*[sn[k][:n] for k in ARG_KEYS[:7]], sn["plans"], sn["has_plan"])
+
+    def reference(sol, n):
+        return sol.reference(cfg, sn["agent_id"][:n], path[:n], n_path[:n], sn["plans"], sn["has_plan"], vel_cap=cap[:n])
+
+    def planes(sol, n):
+        return sol.tasc_planes(sn["agent_id"][:n], sn["state"][:n], sn["plans"], sn["has_plan"])
+
+    calls = [(replan, 4), (reference, 4), (planes, 4), (reference, 16), (planes, 16), (replan, 16), (replan, 4)]
+    sol = hdsm.Solver(prm, 16, 16)
+    for step, (call, n) in enumerate(calls):
+        got, want = call(sol, n), call(hdsm.Solver(prm, 16, 16), n)
+        if call is replan:
+            assert (got["status"] == want["status"]).all(), step
+            ok = want["status"] != 2
+            assert ok.any() and np.abs(got["traj"] - want["traj"])[ok].max() < 1e-7, step
+        elif call is reference:
+            assert all(np.array_equal(g, w) for g, w in zip(got, want)), step
+            assert np.abs(got[0]).max() > 0 and (got[2] > 0).all()
+        else:
+            assert np.array_equal(got, want) and np.abs(got).max() > 0, step
+    sol.close()
+    again = replan(hdsm.Solver(prm, 16, 16), 4)  # (`want`: the last call of the list, on its fresh handle)
+    assert (again["status"] == want["status"]).all()
