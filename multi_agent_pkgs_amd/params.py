@@ -1,4 +1,4 @@
-"""ctypes mirror of `hdsm_params` (include/hdsm.h) and the reference's shipped configurations.
+"""ctypes mirrors of `hdsm_params` and the three config structs (include/) and the reference's shipped configurations.
 
 The field values of :func:`agile_params` are the ROS parameters of
 ``multi_agent_planner/config/agent_agile_config.yaml`` of the reference, turned into solver bounds the way
@@ -123,3 +123,14 @@ class MapConfig(C.Structure):
 
 def default_map_config(voxel_size=0.3, inflation_dist=0.3, potential_dist=1.5, potential_pow=4):
     return MapConfig(voxel_size, inflation_dist, potential_dist, potential_pow, 0)
+
+
+class SwarmConfig(C.Structure):
+    """hdsm_swarm_config (include/hdsm_swarm.h); swarm.default_swarm_config() fills it with the library's defaults."""
+    _fields_ = [
+        ("path_vel_min", C.c_double), ("path_vel_max", C.c_double), ("sens_dist", C.c_double),
+        ("sens_pot", C.c_double), ("sens_other_agents", C.c_double), ("path_vel_dec", C.c_double),
+        ("thresh_dist", C.c_double), ("voxel_size", C.c_double), ("grid_range", C.c_double * 3),
+        ("grid_z_min", C.c_double), ("n_it_decomp", C.c_int32), ("step_plan", C.c_int32),
+        ("use_cvx_new", C.c_int32), ("reserved0", C.c_int32),
+    ]

@@ -6,6 +6,7 @@ the hot path; they cannot be imported here — `launch_ros` is absent — and mu
   circle_scenario          multi_agent_planner/launch/multi_agent_planner_circle.launch.py:25-44
   lattice_scenario         multi_agent_planner/launch/multi_agent_planner_long.launch.py:24-42 (a line of agents along y),
                            generalised to a y-z lattice for 4096 agents (cfg 5)
+  lane_forest_scenario     that lattice with pillars between its lanes: a forest the straight paths are collision-free in
   pillar_forest            env_builder/src/environment_builder.cpp:189-231 (AddObstacles) with the parameters of
                            env_builder/config/env_default_config.yaml:9-13, voxelised by voxel_grid.cpp:314-332
   forest_wall_forest       env_builder/scripts/generate_random_grid.py:57-115 (+ shapes.py Wall / Cylinder / RandomVolume),
@@ -44,6 +45,41 @@ def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.
     starts = np.array([[x0, y0 + pitch * i, z0 + pitch * j] for j in range(n_z) for i in range(n_y)], dtype=np.float64)
     goals = starts + [length, 0.0, 0.0]
     return starts, goals
+
+
+def lane_forest_scenario(n_y, n_z=1, pitch=2.01, length=96.01, y0=5.0, z0=1.5, voxel=0.3, seed=0,
+                         density=0.1, inflate=0.3, pillar_radius=0.05, jitter=0.3):
+    """A forest the straight paths of a line formation are collision-free in (f3, the path planner, is not built).
+
+    Agents: the line formation of multi_agent_planner_long.launch.py:36-42 generalised to a y-z lattice (SURVEY.md
+    section 8d, cfg 5): start = (0, y0 + pitch i, z0 + pitch j), goal = start + (length, 0, 0). Obstacles: full-height
+    pillars of env_long_config.yaml's kind (radius 0.05 m, inflated by 0.3 m as the map builder does) in the two
+    forest bands x in [3, 33] and [63, 93], `density` pillars per m^2 — but placed within `jitter` of the mid-lines
+    BETWEEN the lanes, so that every lane centre keeps >= 0.2 m to the nearest occupied voxel (the shipped forest is
+    random in y and relies on JPS to route around it). Own seeded PRNG.
+    Returns starts [n][3], goals [n][3], occupancy int8 [nz][ny][nx], origin (3,)."""
+    rng = np.random.default_rng(seed)
+    starts = np.array([[0.0, y0 + pitch * i, z0 + pitch * j] for j in range(n_z) for i in range(n_y)])
+    goals = starts + [length, 0.0, 0.0]
+    origin = np.array([-3.0, 0.0, 0.0])
+    hi = np.array([length + 6.0, y0 + pitch * n_y + 5.0, z0 + pitch * n_z + 3.0])
+    dims = np.ceil((hi - origin) / voxel).astype(int)
+    occ = np.zeros((dims[2], dims[1], dims[0]), np.int8)
+    mids = y0 + pitch * (np.arange(-1, n_y) + 0.5)
+    r = pillar_radius + inflate
+    xc = (np.arange(dims[0]) + 0.5) * voxel + origin[0]
+    yc = (np.arange(dims[1]) + 0.5) * voxel + origin[1]
+    for x_lo, x_hi in ((3.0, 33.0), (63.0, 93.0)):
+        for ym0 in mids:
+            for px in rng.uniform(x_lo, x_hi, rng.poisson(density * (x_hi - x_lo) * pitch)):
+                ym = ym0 + rng.uniform(-jitter, jitter)
+                ix = np.nonzero(np.abs(xc - px) <= r)[0]
+                iy = np.nonzero(np.abs(yc - ym) <= r)[0]
+                for a in ix:
+                    for b in iy:
+                        if (xc[a] - px) ** 2 + (yc[b] - ym) ** 2 <= r * r:
+                            occ[:, b, a] = 100
+    return starts, goals, occ, origin
 
 
 def _add_obstacle(occ, center_local, size, vox=VOX):

@@ -603,8 +603,6 @@ def test_an_array_that_runs_past_its_registered_range_never_reaches_the_fetch_ke
                status=np.full(64, -1, dtype=np.int32), obj=np.zeros(64))
     import ctypes as C
     lib = hdsm.load()
-    lib.hdsm_host_register.argtypes = [C.c_void_p, C.c_size_t]
-    lib.hdsm_host_unregister.argtypes = [C.c_void_p]
     halves = [a for a in args + list(out.values()) if a.nbytes >= 8192]   # (whole pages: half of the array is at least a page)
     assert len(halves) >= 4
     for a in halves:
@@ -675,3 +673,37 @@ def test_one_handle_through_lazy_state_and_growing_scratch_matches_fresh_handles
     sol.close()
     again = replan(hdsm.Solver(prm, 16, 16), 4)  # (`want`: the last call of the list, on its fresh handle)
     assert (again["status"] == want["status"]).all()
+
+
+def test_replan_device_refuses_a_tensor_of_another_dtype_before_the_launch(hdsm):
+    """The binding takes every signature from the headers: `state` as a float32 tensor where hdsm.h says `const double*` is refused
+    by ctypes before the library is entered (nothing is launched), and the handle then serves the right tensors with the answers
+    hdsm_replan gives for host arrays. A capacity error of the same handle carries the library's own text."""
+    import ctypes
+    import torch
+    prm = agile_params(10, max_rows_static=18)
+    sn = problems.swarm_snapshot(prm, 2, seed=7)
+    args = [np.ascontiguousarray(sn[k]) for k in ARG_KEYS]
+    dev = torch.device("cuda", 0)
+    dt = dict(agent_id=torch.int32, state=torch.float64, ref=torch.float64, n_poly=torch.int32, n_rows=torch.int32,
+              A=torch.float64, b=torch.float64, plans=torch.float64, has_plan=torch.uint8)
+    d = {k: torch.from_numpy(a).to(dev).to(dt[k]).contiguous() for k, a in zip(ARG_KEYS, args)}
+    o = dict(traj=torch.zeros((2, 11, 9), dtype=torch.float64, device=dev), ctrl=torch.zeros((2, 10, 3), dtype=torch.float64, device=dev),
+             used=torch.zeros((2, 4), dtype=torch.uint8, device=dev), status=torch.full((2,), -1, dtype=torch.int32, device=dev),
+             obj=torch.zeros(2, dtype=torch.float64, device=dev))
+    sol = hdsm.Solver(prm, 2, 2)
+    with pytest.raises(ctypes.ArgumentError):
+        sol.replan_device(*[d[k].float() if k == "state" else d[k] for k in ARG_KEYS], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"])
+    torch.cuda.synchronize()
+    assert (o["status"].cpu().numpy() == -1).all() and float(o["traj"].abs().max()) == 0.0
+    sol.replan_device(*[d[k] for k in ARG_KEYS], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"])
+    torch.cuda.synchronize()
+    sol.reset_warm_start()
+    want = sol.replan(*args)
+    assert (o["status"].cpu().numpy() == want["status"]).all()
+    ok = want["status"] != 2
+    assert ok.any() and np.abs(o["traj"].cpu().numpy() - want["traj"])[ok].max() < 1e-7
+    big = problems.swarm_snapshot(prm, 4, seed=7)
+    with pytest.raises(hdsm.HdsmError) as e:
+        sol.replan(*[big[k] for k in ARG_KEYS])
+    assert e.value.code == hdsm.HDSM_ERR_CAPACITY and str(e.value) == "hdsm error -4: n_inst exceeds max_instances of the handle"

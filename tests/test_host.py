@@ -308,7 +308,6 @@ def test_shutdown_statistics_files_and_report(tmp_path):
     com_latency_<id>.csv one line per OTHER agent (AC:2049-2059); the report is what the reference prints to std::cout
     (default ostream formatting = %g)."""
     L = lib.load()
-    L.hdsm_stats_create.restype = C.c_void_p
     st = C.c_void_p(L.hdsm_stats_create(2, 4))
     vals = {0: [1.5, 0.25, 3.0], 1: [0.0, 0.0], 2: [12.3456789, 0.001], 3: [20.0], 4: [21.5], 5: [100.125, 7.0]}
     for kind, vs in vals.items():

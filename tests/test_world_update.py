@@ -233,11 +233,9 @@ def test_argument_errors():
         with pytest.raises(lib.HdsmError) as e:
             lib.map_region_extent(cfg, (40, 37, 23), lo, bd)
         assert e.value.code == lib.HDSM_ERR_BAD_ARG and "box" in str(e.value)
-        L.hdsm_map_region_scratch_bytes.restype = C.c_size_t
         assert L.hdsm_map_region_scratch_bytes(C.byref(cfg), lib._p(i32((40, 37, 23)), C.c_int32), lib._p(i32(lo), C.c_int32), lib._p(i32(bd), C.c_int32)) == 0
     with pytest.raises(lib.HdsmError):
         lib.map_region_extent(default_map_config(potential_dist=3.5), (40, 37, 23), [0, 0, 0], [1, 1, 1])   # rn2 = 12 > 9
-    L.hdsm_map_region_scratch_bytes.restype = C.c_size_t
     full = L.hdsm_map_region_scratch_bytes(C.byref(cfg), lib._p(i32((40, 37, 23)), C.c_int32), lib._p(i32([0, 0, 0]), C.c_int32), lib._p(i32((40, 37, 23)), C.c_int32))
     assert full == 4 * 40 * 37 * 23
     # the region pre-processing refuses the same boxes before it looks for a device
