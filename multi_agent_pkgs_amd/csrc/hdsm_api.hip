@@ -2,14 +2,10 @@
 //
 // One workgroup solves one agent-replan (hdsm_core.h); the launch is a plain 1-D grid of n_inst blocks.
 // There is no CPU path in this library: without a HIP device hdsm_create() fails.
+// The other entry points of include/hdsm.h: reference_kernels.hip (row f1), exchange_kernels.hip (RCCL), replan_host.hip (hdsm_replan).
 #include <hip/hip_runtime.h>
 
-#include <atomic>
-#include <mutex>
-
 #include <cfloat>
-#include <rccl/rccl.h>
-
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -22,30 +18,24 @@
 #include "../../include/hdsm.h"
 #include "hdsm_consts.h"
 #include "hdsm_core.h"
+#include "hdsm_entry.h"
 #include "hdsm_handle.h"
 #include "hdsm_internal.h"
 #include "hdsm_level1.h"
 #include "hdsm_shapes.h"
+#include "plan_pack.h"
+
+using namespace hdsm_entry;
 
 namespace {
-
-using hdsm_handle::Handle;
-
-thread_local std::string g_err;
-
-int set_err(int code, const std::string& msg) {
+thread_local std::string g_err;  // the one error text of the hdsm_ family (hdsm_last_error)
+}
+int hdsm_entry::set_err(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIP_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) {                                                                             \
-      (void)hipGetLastError(); /* reported here: the next call must not trip over it again */            \
-      return set_err(HDSM_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));               \
-    }                                                                                                   \
-  } while (0)
+namespace {
 
 // What a workgroup works on. Ordinary launch: block b -> instance order[b] (or b). Pass 2 of a split launch (a.item_mode): the
 // workgroups are PERSISTENT — each draws items from the queue pass 1 filled (Args::items: one open child of an open level of a
@@ -156,14 +146,6 @@ __global__ __launch_bounds__(NT, 2) void k_replan_duo(const hdsm::Consts* __rest
   run_block<Sol>(reinterpret_cast<typename Sol::S*>(smem), cp, a);
 }
 
-// Pre-pass of every level-2 launch, one thread per agent of the swarm:
-//   pos[n_rob][N][3]   positions of steps 1..N of every published plan, packed: the sweeps of the replan kernel read 24 B
-//                      per (neighbour, step) instead of striding through 72-B state records (zeros for agents without a plan);
-//   bounds[n_rob][4]   (only for swarms of at least bounds_min agents) centre of the bounding box of those positions and the
-//                      radius of the sphere around it that holds them (radius -1 = no plan): the sweeps use it to skip
-//                      whole neighbours (hdsm_wave_gi.h, sweep_planes).
-__device__ void launch_order_block(int n_inst, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id, int32_t* __restrict__ order);
-
 // The set-up map of ALL instances of a launch as ONE dense product on the matrix cores. Everything an instance needs before its first
 // iteration — x_eq, x0, the gradient at u = 0, the residual of the terminal equalities and their multipliers — is linear in
 // v = (state_curr, traj_ref) (Consts::KT, built once by hdsm_create from the Hessian factor): OUT[row][inst] = sum_j KT[j][row] v[inst][j],
@@ -213,6 +195,12 @@ __device__ void setup_map_tile(const SetupMapArgs& m, int tile) {
   }
 }
 
+// Pre-pass of every level-2 launch, one thread per agent of the swarm:
+//   pos[n_rob][N][3]   positions of steps 1..N of every published plan, packed: the sweeps of the replan kernel read 24 B
+//                      per (neighbour, step) instead of striding through 72-B state records (zeros for agents without a plan);
+//   bounds[n_rob][4]   (only for swarms of at least bounds_min agents) centre of the bounding box of those positions and the
+//                      radius of the sphere around it that holds them (radius -1 = no plan): the sweeps use it to skip
+//                      whole neighbours (hdsm_wave_gi.h, sweep_planes).
 __global__ __launch_bounds__(256) void k_plan_prepass(int N, int n_rob, const double* __restrict__ plans,
                                                       const uint8_t* __restrict__ has_plan, double* __restrict__ pos,
                                                       double* __restrict__ bounds, int n_order, const int32_t* __restrict__ key_prev,
@@ -243,95 +231,11 @@ __global__ __launch_bounds__(256) void k_plan_prepass(int N, int n_rob, const do
     pk[0] = p[0], pk[1] = p[1], pk[2] = p[2];
   }
   if (!bounds) return;
-  double lo[3], hi[3];
-  for (int ax = 0; ax < 3; ++ax) lo[ax] = on ? p[ax] : 1e300, hi[ax] = on ? p[ax] : -1e300;
-  for (int off = 8; off > 0; off >>= 1)
-    for (int ax = 0; ax < 3; ++ax) {
-      lo[ax] = fmin(lo[ax], __shfl_xor(lo[ax], off, 16));
-      hi[ax] = fmax(hi[ax], __shfl_xor(hi[ax], off, 16));
-    }
-  const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
-  const double ux = p[0] - cx, uy = p[1] - cy, uz = p[2] - cz;
-  double r2 = on ? ux * ux + uy * uy + uz * uz : 0.0;
-  bool finite = !on || (r2 == r2);
-  for (int off = 8; off > 0; off >>= 1) {
-    r2 = fmax(r2, __shfl_xor(r2, off, 16));
-    finite = finite && __shfl_xor((int)finite, off, 16);
-  }
-  if (live && i == 0) {
-    double4 out = {0.0, 0.0, 0.0, -1.0};
-    if (has) {
-      out.x = cx, out.y = cy, out.z = cz;
-      out.w = sqrt(r2) * (1.0 + 1e-9);
-      if (!finite || !(out.w >= 0.0) || !(out.w < 1e299)) out.w = 1e300;  // non-finite plan: never culled, the step-by-step test decides
-    }
-    *reinterpret_cast<double4*>(bounds + 4 * (int64_t)k) = out;
-  }
+  plan_sphere16<false>(live && i == 0, bounds + 4 * (int64_t)k, has, p, on, p, false);
 }
 
-// Longest-processing-time-first launch order. A launch lasts as long as its slowest workgroup chain: with more instances than
-// resident workgroups (2 per CU) an expensive instance that happens to start late sets the kernel time. Workgroups are
-// dispatched in index order, so workgroup w takes instance order[w], the instances sorted by the key they left in the
-// PREVIOUS launch on this handle (largest first; a counting sort on 256 values): the time the instance took, or the maximum if it
-// found no solution (hdsm_core.h, st_key). The previous replan of the same agent is a good predictor (gridlocked neighbourhoods
-// persist); the answer of an instance does not depend on the order. An entry is the pair (instance, its agent id): the workgroup
-// then needs no second, dependent load (agent_id[instance]) before it can ask for the agent's own plan.
-__device__ void launch_order_block(int n_inst, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id, int32_t* __restrict__ order) {
-  __shared__ int bucket[256];
-  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
-  for (int b = tid; b < 256; b += nt) bucket[b] = 0;
-  __syncthreads();
-  for (int k = tid; k < n_inst; k += nt) {
-    const int it = key_prev[k];
-    atomicAdd(&bucket[255 - (it < 0 ? 0 : (it > 255 ? 255 : it))], 1);
-  }
-  __syncthreads();
-  // exclusive prefix over the 256 buckets, a bucket per thread (every launch of this block has 256 threads): scan inside the wavefront,
-  // then the totals of the wavefronts before. (One thread walked the buckets before round 6, 256 dependent LDS round trips; the bench line
-  // does not see the difference — the pre-pass launch is as long as its set-up map tiles.)
-  {
-    __shared__ int wave_total[4];
-    const int c = bucket[tid & 255];
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const int v = __shfl_up(incl, off, 64);
-      if ((tid & 63) >= off) incl += v;
-    }
-    if ((tid & 63) == 63) wave_total[(tid >> 6) & 3] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < ((tid >> 6) & 3); ++w) base += wave_total[w];
-    if (tid < 256) bucket[tid] = base + incl - c;
-  }
-  __syncthreads();
-  for (int k = tid; k < n_inst; k += nt) {
-    const int it = key_prev[k];
-    const int slot = atomicAdd(&bucket[255 - (it < 0 ? 0 : (it > 255 ? 255 : it))], 1);
-    order[2 * slot] = k, order[2 * slot + 1] = agent_id[k];
-  }
-}
 __global__ __launch_bounds__(256) void k_launch_order(int n_inst, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id, int32_t* __restrict__ order) {
   launch_order_block(n_inst, key_prev, agent_id, order);  // level 1 has no pre-pass to ride on
-}
-
-// hdsm_publish_device / hdsm_exchange_device: the has_plan flag travels inside the record (first entry NaN = no plan)
-__global__ __launch_bounds__(256) void k_publish(int rec, int per, int n_local, const double* __restrict__ traj,
-                                                 const uint8_t* __restrict__ has_local, double* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)per * rec) return;
-  const int k = (int)(idx / rec), e = (int)(idx % rec);
-  const bool has = k < n_local && has_local[k];
-  double v = has ? traj[idx] : 0.0;
-  if (!has && e == 0) v = __longlong_as_double(0x7ff8000000000000LL);
-  out[idx] = v;
-}
-__global__ __launch_bounds__(256) void k_has_from_sentinel(int rec, int n, const double* __restrict__ plans,
-                                                           uint8_t* __restrict__ has) {
-  const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (k >= n) return;
-  const double v = plans[(int64_t)k * rec];
-  has[k] = (v == v) ? 1 : 0;
 }
 
 // planes[n_inst][N][n_rob][4] for tests / level-1 callers (AC:1100-1205)
@@ -360,377 +264,6 @@ __global__ __launch_bounds__(256) void k_tasc_planes(const hdsm::Consts* __restr
     }
     double* out = planes + idx * 4;
     out[0] = row[0], out[1] = row[1], out[2] = row[2], out[3] = row[3];
-  }
-}
-
-// ---- next row f1: reference trajectory (AC:1449-1553). One workgroup per agent: the neighbour term of
-// ComputePathVelocity is a min-reduction over (step, neighbour) streamed from the all-gathered plans buffer
-// (thread <-> neighbour, all N+1 positions of that neighbour read back to back), SamplePath is a short sequential
-// walk done by one thread, the velocity references are elementwise.
-struct RefArgs {
-  int32_t n_inst, n_rob, pmax, N;
-  double dt;
-  hdsm_ref_config cfg;
-  const int32_t* agent_id;
-  const double* path;
-  const int32_t* n_path;
-  const double* vel_cap;
-  const double* plans;
-  const uint8_t* has_plan;
-  double* ref_full;
-  double* ref;
-  double* path_vel;
-  const double* rpos;  // [n_rob][N + 1][3] positions of steps 0..N, packed (k_ref_pack)
-  const double* rsph;  // [n_rob][4] enclosing sphere of those positions (radius < 0: no plan)
-  double wocc[hdsm::MAXH + 1];  // GetVelocityLimit's weight of step i (AC:1791-1795, 1805-1817): config only, evaluated by the host's libm
-};
-
-// Positions of steps 0..N of every published plan, packed, and their enclosing sphere: 16 lanes per agent (N + 1 <= 17: lane
-// 15 also takes step 16). The velocity limit reads 24 B per (neighbour, step) from here instead of a 72-B stride of the
-// records, and skips a neighbour whose sphere is further away than the closest one found.
-// In the device-resident loop (one stream, same plans buffer for the reference and the solve of a round) this kernel also leaves
-// what k_plan_prepass would compute a few microseconds later from the same records — positions of steps 1..N (`pos`), their
-// bounding sphere (`bounds`, may be null), the launch order of the solve (one extra workgroup) — and the solve skips its pre-pass.
-__global__ __launch_bounds__(256) void k_ref_pack(int N, int n_rob, const double* __restrict__ plans,
-                                                   const uint8_t* __restrict__ has_plan, double* __restrict__ rpos,
-                                                   double* __restrict__ rsph, double* __restrict__ pos, double* __restrict__ bounds,
-                                                   int n_order, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id,
-                                                   int32_t* __restrict__ order) {
-  if (order != nullptr && blockIdx.x == gridDim.x - 1) {
-    launch_order_block(n_order, key_prev, agent_id, order);
-    return;
-  }
-  const int tid = (int)threadIdx.x, i = tid & 15;
-  const int k = (int)blockIdx.x * 16 + (tid >> 4);
-  const bool live = k < n_rob;
-  const bool has = live && has_plan[k];
-  double p[2][3] = {{0, 0, 0}, {0, 0, 0}};
-  bool on[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int st = i + 16 * u;
-    on[u] = has && st <= N && (u == 0 || i == 0);
-    if (on[u]) {
-      const double* rec = plans + ((int64_t)k * (N + 1) + st) * 9;
-      p[u][0] = rec[0], p[u][1] = rec[1], p[u][2] = rec[2];
-    }
-    if (live && st <= N && (u == 0 || i == 0)) {
-      double* pk = rpos + ((int64_t)k * (N + 1) + st) * 3;
-      pk[0] = p[u][0], pk[1] = p[u][1], pk[2] = p[u][2];
-      if (pos != nullptr && st >= 1) {
-        double* pq = pos + ((int64_t)k * N + st - 1) * 3;
-        pq[0] = p[u][0], pq[1] = p[u][1], pq[2] = p[u][2];
-      }
-    }
-  }
-  if (bounds != nullptr) {  // the sphere of steps 1..N, exactly as k_plan_prepass forms it
-    const bool in0 = on[0] && i >= 1;
-    double lo[3], hi[3];
-    for (int ax = 0; ax < 3; ++ax) {
-      lo[ax] = in0 ? p[0][ax] : 1e300, hi[ax] = in0 ? p[0][ax] : -1e300;
-      if (on[1]) lo[ax] = fmin(lo[ax], p[1][ax]), hi[ax] = fmax(hi[ax], p[1][ax]);
-    }
-    for (int off = 8; off > 0; off >>= 1)
-      for (int ax = 0; ax < 3; ++ax) {
-        lo[ax] = fmin(lo[ax], __shfl_xor(lo[ax], off, 16));
-        hi[ax] = fmax(hi[ax], __shfl_xor(hi[ax], off, 16));
-      }
-    const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
-    double r2 = 0.0;
-    if (in0) {
-      const double ux = p[0][0] - cx, uy = p[0][1] - cy, uz = p[0][2] - cz;
-      r2 = ux * ux + uy * uy + uz * uz;
-    }
-    if (on[1]) {
-      const double ux = p[1][0] - cx, uy = p[1][1] - cy, uz = p[1][2] - cz;
-      r2 = fmax(r2, ux * ux + uy * uy + uz * uz);
-    }
-    bool finite = r2 == r2;
-    for (int off = 8; off > 0; off >>= 1) {
-      r2 = fmax(r2, __shfl_xor(r2, off, 16));
-      finite = finite && __shfl_xor((int)finite, off, 16);
-    }
-    if (live && i == 0) {
-      double4 out = {0.0, 0.0, 0.0, -1.0};
-      if (has) {
-        out.x = cx, out.y = cy, out.z = cz;
-        out.w = sqrt(r2) * (1.0 + 1e-9);
-        if (!finite || !(out.w >= 0.0) || !(out.w < 1e299)) out.w = 1e300;
-      }
-      *reinterpret_cast<double4*>(bounds + 4 * (int64_t)k) = out;
-    }
-  }
-  double lo[3], hi[3];
-  for (int ax = 0; ax < 3; ++ax) {
-    lo[ax] = on[0] ? p[0][ax] : 1e300, hi[ax] = on[0] ? p[0][ax] : -1e300;
-    if (on[1]) lo[ax] = fmin(lo[ax], p[1][ax]), hi[ax] = fmax(hi[ax], p[1][ax]);
-  }
-  for (int off = 8; off > 0; off >>= 1)
-    for (int ax = 0; ax < 3; ++ax) {
-      lo[ax] = fmin(lo[ax], __shfl_xor(lo[ax], off, 16));
-      hi[ax] = fmax(hi[ax], __shfl_xor(hi[ax], off, 16));
-    }
-  const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]), cz = 0.5 * (lo[2] + hi[2]);
-  double r2 = 0.0;
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-    if (on[u]) {
-      const double ux = p[u][0] - cx, uy = p[u][1] - cy, uz = p[u][2] - cz;
-      r2 = fmax(r2, ux * ux + uy * uy + uz * uz);
-    }
-  bool finite = r2 == r2;
-  for (int off = 8; off > 0; off >>= 1) {
-    r2 = fmax(r2, __shfl_xor(r2, off, 16));
-    finite = finite && __shfl_xor((int)finite, off, 16);
-  }
-  if (live && i == 0) {
-    double4 out = {0.0, 0.0, 0.0, -1.0};
-    if (has) {
-      out.x = cx, out.y = cy, out.z = cz;
-      out.w = sqrt(r2) * (1.0 + 1e-9);
-      if (!finite || !(out.w >= 0.0) || !(out.w < 1e299)) out.w = 1e300;  // a non-finite plan is never skipped
-    }
-    *reinterpret_cast<double4*>(rsph + (int64_t)k * 4) = out;
-  }
-}
-
-// wave reductions of k_reference: DPP row rotations + v_readlane (hdsm_wave_gi.h) — a __shfl_xor stage on a double is two
-// ds_bpermute round trips, and the kernel reduces 14 values per instance
-__device__ __forceinline__ double ref_wave_min(double v) { return -hdsm::wave_max64(-v); }
-
-// NT threads per instance: 256 for small batches (more lanes on the one instance's neighbour scans), 64 — one wavefront, every
-// instance of a 1024-agent round resident at once, the workgroup barriers of the reductions cost nothing — for large ones
-// (46 -> ~20 us per 1024-agent round).
-template <int NT>
-__global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
-  __shared__ double own[hdsm::MAXH + 1][3];
-  __shared__ double wocc[hdsm::MAXH + 1];
-  __shared__ double red[NT];
-  __shared__ double d2w[NT / 64][hdsm::MAXH + 1];
-  __shared__ int idx[NT];
-  constexpr int PATH_LDS = 64;
-  __shared__ double spath[PATH_LDS * 3];
-  __shared__ double pts[hdsm::MAXH + 1][3];
-  __shared__ int cnt_s;
-  constexpr int SURV_CAP = 2048;
-  __shared__ int surv[SURV_CAP];
-  __shared__ int surv_n;
-  const int inst = blockIdx.x, tid = threadIdx.x, N = a.N;
-  const int self = a.agent_id[inst];
-  const int np = min(max(a.n_path[inst], 1), a.pmax);  // the host wrapper rejects counts outside [1, pmax]; device callers are clamped
-  const bool own_has = self >= 0 && self < a.n_rob && a.has_plan[self];
-  // the polyline goes through LDS: the sampling walk below is one thread's chain, and every global read in it was a
-  // dependent round trip
-  const double* pth_g = a.path + (int64_t)inst * a.pmax * 3;
-  const bool path_fits = np <= PATH_LDS;
-  if (path_fits)
-    for (int e = tid; e < np * 3; e += NT) spath[e] = pth_g[e];
-  const double* pth = path_fits ? spath : pth_g;
-  if (tid <= N) {
-    for (int c = 0; c < 3; ++c) own[tid][c] = own_has ? a.plans[((int64_t)self * (N + 1) + tid) * 9 + c] : 0.0;
-    wocc[tid] = a.wocc[tid];
-  }
-  __syncthreads();
-  double pv = a.vel_cap ? a.vel_cap[inst] : a.cfg.path_vel_max;
-  if (pv > a.cfg.path_vel_max) pv = a.cfg.path_vel_max;
-  // The limit of one (neighbour, step) pair, v = v_min + (v_max - v_min) (1 - w_i / exp(k d)), does not decrease with the
-  // distance d (k >= 0, w_i >= 0, v_max >= v_min; every operation of the chain is monotone), so the minimum over the
-  // neighbours is taken on the SQUARED distances — three subtractions and three multiply-adds per pair — and the square root,
-  // the exponential and the division are evaluated once per step on the closest neighbour instead of once per pair.
-  const bool monotone = a.cfg.sens_dist >= 0 && a.cfg.path_vel_max >= a.cfg.path_vel_min;
-  if (own_has && np >= 2 && monotone) {
-    // (1) the neighbour whose sphere is closest: its exact squared distances bound the minima from above
-    const double4 ss = *reinterpret_cast<const double4*>(a.rsph + (int64_t)self * 4);
-    double gbest = DBL_MAX;
-    int jbest = -1;
-    constexpr int UB = 8;  // sphere records in flight per thread: the scans are chains of L2 round trips otherwise
-    for (int j0 = tid; j0 < a.n_rob; j0 += UB * NT) {
-      double4 sj[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int j = j0 + u * NT;
-        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < a.n_rob ? j : self) * 4);
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int j = j0 + u * NT;
-        if (j >= a.n_rob || j == self || sj[u].w < 0) continue;  // (w < 0: no plan)
-        const double cx = sj[u].x - ss.x, cy = sj[u].y - ss.y, cz = sj[u].z - ss.z;
-        const double g = sqrt(cx * cx + cy * cy + cz * cz) - sj[u].w - ss.w;  // every step of j is at least this far (g may be < 0)
-        if (g < gbest || jbest < 0) gbest = g, jbest = j;
-      }
-    }
-    {  // (which of several equally close spheres wins only moves the bound below)
-      const double key = jbest >= 0 ? gbest : DBL_MAX;
-      const double m = ref_wave_min(key);
-      const unsigned long long who = __ballot(jbest >= 0 && key == m);
-      const int src = who != 0ull ? __ffsll((long long)who) - 1 : 0;
-      jbest = who != 0ull ? __builtin_amdgcn_readlane(jbest, src) : -1;
-      gbest = m;
-    }
-    if constexpr (NT > 64) {
-      if ((tid & 63) == 0) red[tid >> 6] = gbest, idx[tid >> 6] = jbest;
-      __syncthreads();
-      gbest = red[0], jbest = idx[0];
-#pragma unroll
-      for (int w = 1; w < NT / 64; ++w)
-        if (idx[w] >= 0 && (jbest < 0 || red[w] < gbest)) gbest = red[w], jbest = idx[w];
-      __syncthreads();
-    }
-    const int jstar = jbest;
-    double umax = 0.0;
-    {
-      const int lane = tid & 63;
-      double u = 0.0;
-      if (lane <= N && jstar >= 0) {
-        const double* rp = a.rpos + ((int64_t)jstar * (N + 1) + lane) * 3;
-        const double dx = own[lane][0] - rp[0], dy = own[lane][1] - rp[1], dz = own[lane][2] - rp[2];
-        u = dx * dx + dy * dy + dz * dz;
-        u = (u == u) ? u : DBL_MAX;  // (a non-finite plan bounds nothing)
-      }
-      u = hdsm::wave_max64(u);
-      umax = u;
-    }
-    // (2) minima of the squared distances over the neighbours that can still lower one of them
-    double d2min[hdsm::MAXH + 1];
-#pragma unroll
-    for (int i = 0; i <= hdsm::MAXH; ++i) d2min[i] = DBL_MAX;
-    // The neighbours that pass the sphere test are first LISTED (LDS) and then shared out evenly, one per thread and trip: taken
-    // where they are found, a trip of the scan cost a full round trip to memory for the whole wavefront whenever ANY lane had a
-    // survivor in it — 16 round trips per instance in a dense ring, half of this kernel's time.
-    auto drain = [&]() {
-      __syncthreads();
-      const int cnt = surv_n < SURV_CAP ? surv_n : SURV_CAP;
-      for (int k = tid; k < cnt; k += NT) {
-        const double* rp = a.rpos + (int64_t)surv[k] * (N + 1) * 3;
-#pragma unroll
-        for (int i = 0; i <= hdsm::MAXH; ++i)
-          if (i <= N) {
-            const double dx = own[i][0] - rp[3 * i], dy = own[i][1] - rp[3 * i + 1], dz = own[i][2] - rp[3 * i + 2];
-            d2min[i] = fmin(d2min[i], dx * dx + dy * dy + dz * dz);
-          }
-      }
-      __syncthreads();
-      if (tid == 0) surv_n = 0;
-      __syncthreads();
-    };
-    if (tid == 0) surv_n = 0;
-    __syncthreads();
-    int listed = 0;  // (an upper bound of surv_n, the same in every thread)
-    for (int j0 = tid; j0 - tid < a.n_rob; j0 += UB * NT) {
-      if (listed + UB * NT > SURV_CAP) drain(), listed = 0;
-      double4 sj[UB];
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int j = j0 + u * NT;
-        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < a.n_rob ? j : self) * 4);
-      }
-#pragma unroll
-      for (int u = 0; u < UB; ++u) {
-        const int j = j0 + u * NT;
-        if (j >= a.n_rob || j == self || sj[u].w < 0) continue;
-        const double cx = sj[u].x - ss.x, cy = sj[u].y - ss.y, cz = sj[u].z - ss.z;
-        // (squared: all its steps are further than the closest neighbour's when the gap between the spheres is)
-        const double c2 = cx * cx + cy * cy + cz * cz, reach = sj[u].w + ss.w + sqrt(umax) * (1.0 + 1e-9);
-        if (c2 > reach * reach * (1.0 + 1e-9)) continue;
-        surv[atomicAdd(&surv_n, 1)] = j;
-      }
-      listed += UB * NT;
-    }
-    drain();
-#pragma unroll
-    for (int i = 0; i <= hdsm::MAXH; ++i)
-      if (i <= N) {
-        double m = d2min[i];
-        m = ref_wave_min(m);
-        if ((tid & 63) == 0) d2w[tid >> 6][i] = m;
-      }
-    __syncthreads();
-    if (tid <= N) {
-      double m = d2w[0][tid];
-#pragma unroll
-      for (int w = 1; w < NT / 64; ++w) m = fmin(m, d2w[w][tid]);
-      if (m < DBL_MAX) {
-        const double d = sqrt(m);
-        const double alpha = (1 - wocc[tid] * (1 / exp(a.cfg.sens_dist * d)));
-        const double v = a.cfg.path_vel_min + (a.cfg.path_vel_max - a.cfg.path_vel_min) * alpha;
-        if (v < pv) pv = v;
-      }
-    }
-  } else if (own_has && np >= 2) {  // (a configuration whose limit is not monotone in the distance: every pair is evaluated)
-    for (int j = tid; j < a.n_rob; j += NT) {
-      if (j == self || !a.has_plan[j]) continue;
-      const double* rec = a.plans + (int64_t)j * (N + 1) * 9;
-      for (int i = 0; i <= N; ++i) {
-        const double dx = own[i][0] - rec[9 * i], dy = own[i][1] - rec[9 * i + 1], dz = own[i][2] - rec[9 * i + 2];
-        const double d = sqrt(dx * dx + dy * dy + dz * dz);
-        const double alpha = (1 - wocc[i] * (1 / exp(a.cfg.sens_dist * d)));
-        const double v = a.cfg.path_vel_min + (a.cfg.path_vel_max - a.cfg.path_vel_min) * alpha;
-        if (v < pv) pv = v;
-      }
-    }
-  }
-  pv = ref_wave_min(pv);
-  if constexpr (NT > 64) {
-    if ((tid & 63) == 0) red[tid >> 6] = pv;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) pv = fmin(pv, red[w]);
-  }
-  pv = (np < 2) ? 0.0 : pv;
-  if (tid == 0) {  // SamplePath, AC:1591-1663
-    int cnt = 0;
-    if (np < 2) {
-      for (int i = 0; i < N; ++i, ++cnt)
-        for (int c = 0; c < 3; ++c) pts[cnt][c] = pth[c];
-    } else {
-      const double samp = pv * a.dt;
-      int path_idx = 1, ref_idx = 0;
-      double cur[3] = {pth[0], pth[1], pth[2]};
-      for (int c = 0; c < 3; ++c) pts[0][c] = cur[c];
-      cnt = 1;
-      double limit = samp;
-      while (ref_idx < N) {
-        const double* nx = pth + 3 * path_idx;
-        const double d0 = nx[0] - cur[0], d1 = nx[1] - cur[1], d2 = nx[2] - cur[2];
-        const double dist_next = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-        if (dist_next > limit) {
-          cur[0] = cur[0] + limit * d0 / dist_next, cur[1] = cur[1] + limit * d1 / dist_next;
-          cur[2] = cur[2] + limit * d2 / dist_next;
-          for (int c = 0; c < 3; ++c) pts[cnt][c] = cur[c];
-          ++cnt, ++ref_idx;
-          limit = fmax(0.0, samp - a.cfg.path_vel_dec * a.dt);
-        } else {
-          cur[0] = nx[0], cur[1] = nx[1], cur[2] = nx[2];
-          if (++path_idx == np) {
-            for (int i = ref_idx; i < N; ++i, ++cnt)
-              for (int c = 0; c < 3; ++c) pts[cnt][c] = pth[3 * (np - 1) + c];
-            break;
-          }
-          limit -= dist_next;
-        }
-      }
-    }
-    cnt_s = cnt;
-    a.path_vel[inst] = pv;
-  }
-  __syncthreads();
-  const int cnt = cnt_s;
-  if (tid <= N) {  // velocity reference AC:1527-1547: row i looks back from i+1; the last row copies the previous one
-    const int i = tid < cnt ? tid : cnt - 1;
-    const int ii = (i + 1 < cnt) ? i : (cnt >= 2 ? cnt - 2 : 0);  // pair used by row i
-    double v[3] = {0, 0, 0};
-    if (cnt > 1) {
-      const double d0 = pts[ii][0] - pts[ii + 1][0], d1 = pts[ii][1] - pts[ii + 1][1], d2 = pts[ii][2] - pts[ii + 1][2];
-      const double dist = sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-      if (dist > 1e-2) v[0] = pv * d0 / dist, v[1] = pv * d1 / dist, v[2] = pv * d2 / dist;
-    }
-    double* out = a.ref_full + ((int64_t)inst * (N + 1) + tid) * 6;
-    for (int c = 0; c < 3; ++c) out[c] = pts[i][c], out[3 + c] = v[c];
-    if (a.ref && tid < N) {
-      double* o2 = a.ref + ((int64_t)inst * N + tid) * 6;
-      for (int c = 0; c < 6; ++c) o2[c] = out[c];
-    }
   }
 }
 
@@ -814,65 +347,6 @@ int launch_shape(Handle* h, hdsm::Shape s, const hdsm::Args& a, hipStream_t st, 
 hdsm::ShapeKnobs shape_knobs(const Handle* h) { return {h->n, h->threads, h->P, h->RS, h->duo_min, h->tri_min, h->quad_min}; }
 
 // ---- subtree splitting: set-up of pass 2, merge, lazily allocated state -------------------------------------------------
-// hdsm_replan with page-locked input arrays: ONE kernel reads them from mapped host memory (coalesced reads over PCIe) into the
-// handle's device arrays instead of nine stream-ordered copies, and of the static polyhedra only the rows that exist
-// (n_rows_static of max_rows_static; the rest of the device array is never read by the solver). Blocks 0 .. n_inst - 1 take one
-// instance each, the blocks after them the plans of every agent.
-struct FetchArgs {
-  int32_t n_inst, n_rob, N, P, RS, plan_blocks;
-  const int32_t *agent_id, *n_poly, *n_rows;
-  const double *state, *ref, *A, *b, *plans;
-  const uint8_t* has;
-  int32_t *d_agent, *d_npoly, *d_nrows;
-  double *d_state, *d_ref, *d_A, *d_b, *d_plans;
-  uint8_t* d_has;
-};
-__global__ __launch_bounds__(256) void k_fetch(FetchArgs a) {
-  const int tid = (int)threadIdx.x, blk = (int)blockIdx.x;
-  if (blk >= a.n_inst) {
-    const int64_t total = (int64_t)a.n_rob * (a.N + 1) * 9;
-    for (int64_t e = (int64_t)(blk - a.n_inst) * 256 + tid; e < total; e += (int64_t)a.plan_blocks * 256) a.d_plans[e] = a.plans[e];
-    for (int e = (blk - a.n_inst) * 256 + tid; e < a.n_rob; e += a.plan_blocks * 256) a.d_has[e] = a.has[e];
-    return;
-  }
-  const int k = blk, P = a.P, RS = a.RS;
-  __shared__ int32_t rows_s[HDSM_MAX_POLY];  // (read once over PCIe, not once per entry)
-  if (tid == 0) a.d_agent[k] = a.agent_id[k];
-  const int np = a.n_poly[k];
-  if (tid == 1) a.d_npoly[k] = np;
-  if (tid < 9) a.d_state[(int64_t)k * 9 + tid] = a.state[(int64_t)k * 9 + tid];
-  if (tid < P) {
-    const int32_t nr = a.n_rows[(int64_t)k * P + tid];
-    rows_s[tid] = nr, a.d_nrows[(int64_t)k * P + tid] = nr;
-  }
-  for (int e = tid; e < 6 * a.N; e += 256) a.d_ref[(int64_t)k * 6 * a.N + e] = a.ref[(int64_t)k * 6 * a.N + e];
-  __syncthreads();
-  for (int e = tid; e < P * RS * 4; e += 256) {  // entry (polyhedron j, row r, component c): c < 3 -> A, c = 3 -> b
-    const int c = e & 3, jr = e >> 2, j = jr / RS, r = jr % RS;
-    if (j >= np || r >= rows_s[j]) continue;
-    const int64_t row = ((int64_t)k * P + j) * RS + r;
-    if (c < 3) a.d_A[row * 3 + c] = a.A[row * 3 + c];
-    else a.d_b[row] = a.b[row];
-  }
-}
-
-// hdsm_replan with page-locked output arrays (hdsm_host_register): the results go from HBM straight into the caller's arrays —
-// mapped host memory, written over PCIe by the device — and only for instances that HAVE a solution ("outputs are left
-// untouched" otherwise): no staging download, no host-side filter copy. One 64-lane group per instance.
-__global__ __launch_bounds__(256) void k_deliver(int n_inst, int trj, int ctl, int P, const double* __restrict__ traj, const double* __restrict__ ctrl,
-                                                 const double* __restrict__ obj, const int32_t* __restrict__ status, const uint8_t* __restrict__ used,
-                                                 double* o_traj, double* o_ctrl, double* o_obj, int32_t* o_status, uint8_t* o_used) {
-  const int k = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
-  if (k >= n_inst) return;
-  const int stt = status[k];
-  if (lane == 0) o_status[k] = stt;
-  if (stt == HDSM_NO_SOLUTION) return;
-  for (int e = lane; e < trj; e += 64) o_traj[(int64_t)k * trj + e] = traj[(int64_t)k * trj + e];
-  for (int e = lane; e < ctl; e += 64) o_ctrl[(int64_t)k * ctl + e] = ctrl[(int64_t)k * ctl + e];
-  if (lane < P) o_used[(int64_t)k * P + lane] = used[(int64_t)k * P + lane];
-  if (lane == 0) o_obj[k] = obj[k];
-}
-
 // One wavefront per instance that pass 1 handed over: the best answer of its items becomes the instance's answer. `a` holds
 // the instance-indexed arrays of the launch, `b` the arrays of pass 2 (indexed by the item's place in the queue).
 __global__ __launch_bounds__(64) void k_split_merge(int N, int P, hdsm::Args a, hdsm::Args b) {
@@ -888,20 +362,20 @@ int launch_rescue(Handle* h, const hdsm::Args& a, hipStream_t st) {
   return launch_shape(h, hdsm::pick_shape(shape_knobs(h), r.n_inst, hdsm::PASS_RESCUE), r, st, r.n_inst);
 }
 
-// The handle's device state (snapshots, warm-start sets, prefilter records, staging buffers) is shared by all its calls: one that
-// arrives on another stream than the previous launch waits for it. (Who launches on `st` also names it as last_stream; who only
-// stages into the handle's buffers does not.)
-hipError_t join_stream(Handle* h, hipStream_t st) {
-  return h->launched && st != h->last_stream ? hipStreamWaitEvent(st, h->ev_done.get(), 0) : hipSuccess;
+}  // namespace
+
+int hdsm_entry::rescue_if_flagged(Handle* h, hipStream_t st) {
+  if (h->last_small && h->rescue_ttl == 0) {  // (a launch that already carried the rescue pass needs no second one)
+    HIP_TRY(hipStreamSynchronize(st));
+    if (*h->ovf_flag.host() != 0) {  // an instance ran out of staging rows in a shared-CU kernel: solve it again now, with the large area
+      *h->ovf_flag.host() = 0, h->rescue_ttl = 256;
+      return launch_rescue(h, h->last_args, st);
+    }
+  }
+  return HDSM_OK;
 }
 
-// ... and this is the point it waits for: the end of what a device entry point enqueued
-hipError_t mark_done(Handle* h, hipStream_t st) {
-  if (!h->defer_done)
-    if (const hipError_t e = hipEventRecord(h->ev_done.get(), st)) return e;
-  h->launched = true;
-  return hipSuccess;
-}
+namespace {
 
 // the eight statistics of a launch, `stride` entries each, in one block
 void stat_views(hdsm::Args& a, int32_t* base, size_t stride) {
@@ -909,15 +383,6 @@ void stat_views(hdsm::Args& a, int32_t* base, size_t stride) {
   a.st_sph = base + 4 * stride, a.st_pairs = base + 5 * stride;
   a.st_flags = reinterpret_cast<uint32_t*>(base + 6 * stride), a.st_key = base + 7 * stride;
 }
-
-// stream-ordered copies of a host-pointer entry point: nothing to do for zero bytes, and nothing more after the first error
-struct Copies {
-  hipStream_t st;
-  hdsm_mem::FirstError err;
-  void operator()(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    if (err.ok() && bytes) err(hipMemcpyAsync(dst, src, bytes, kind, st));
-  }
-};
 
 int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   hdsm_handle::SplitState& sub = h->sub;
@@ -1076,14 +541,6 @@ int64_t scratch_stride_for(int n) {
                  : (int64_t)hdsm::Solver<48, hdsm::CMAX48>::SNAP_STRIDE * hdsm::MAXH;
 }
 
-int check_common(Handle* h, int n_inst, int n_rob) {
-  if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
-  if (n_inst < 0 || n_rob < 0) return set_err(HDSM_ERR_BAD_ARG, "negative size");
-  if (n_inst > h->max_inst) return set_err(HDSM_ERR_CAPACITY, "n_inst exceeds max_instances of the handle");
-  if (n_rob > h->n_rob_max) return set_err(HDSM_ERR_CAPACITY, "n_rob exceeds n_rob_max of the handle");
-  return HDSM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1216,177 +673,6 @@ int hdsm_replan_device(void* handle, int32_t n_inst, int32_t n_rob, const int32_
   return launch(h, a, static_cast<hipStream_t>(hip_stream));
 }
 
-// Registered (page-locked, mapped) host memory. hdsm_host_register records every range it maps — base, length, device-side
-// address — and hdsm_replan takes the kernel paths (k_fetch / k_deliver) only for arrays that lie INSIDE a recorded range with all
-// the bytes the call will touch (an array that merely starts in one, or memory page-locked by somebody else, goes through the copy
-// path like pageable memory). While nothing is registered the look-up is one load: no runtime query per array and call.
-namespace {
-struct HostRange {
-  char* base;
-  size_t bytes;
-  char* dev;
-};
-std::mutex g_reg_mutex;
-std::vector<HostRange> g_reg;
-std::atomic<int> g_reg_count{0};
-
-bool mapped_host_range(const void* p, size_t bytes, void** dev) {
-  if (g_reg_count.load(std::memory_order_acquire) == 0) return false;
-  std::lock_guard<std::mutex> lock(g_reg_mutex);
-  const char* c = static_cast<const char*>(p);
-  for (const HostRange& r : g_reg)
-    if (c >= r.base && bytes <= r.bytes && (size_t)(c - r.base) <= r.bytes - bytes) {
-      *dev = r.dev + (c - r.base);
-      return true;
-    }
-  return false;
-}
-}  // namespace
-
-int hdsm_host_register(void* ptr, size_t bytes) {
-  if (!ptr || bytes == 0) return set_err(HDSM_ERR_BAD_ARG, "hdsm_host_register: null or empty range");
-  hipError_t e = hipHostRegister(ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(HDSM_ERR_DEVICE, std::string("hdsm_host_register: ") + hipGetErrorString(e));
-  }
-  void* dev = nullptr;
-  e = hipHostGetDevicePointer(&dev, ptr, 0);
-  if (e != hipSuccess || dev == nullptr) {
-    (void)hipGetLastError();
-    (void)hipHostUnregister(ptr);
-    return set_err(HDSM_ERR_DEVICE, std::string("hdsm_host_register: no device address for the range: ") + hipGetErrorString(e));
-  }
-  std::lock_guard<std::mutex> lock(g_reg_mutex);
-  g_reg.push_back(HostRange{static_cast<char*>(ptr), bytes, static_cast<char*>(dev)});
-  g_reg_count.store((int)g_reg.size(), std::memory_order_release);
-  return HDSM_OK;
-}
-
-int hdsm_host_unregister(void* ptr) {
-  if (!ptr) return set_err(HDSM_ERR_BAD_ARG, "hdsm_host_unregister: null pointer");
-  {
-    std::lock_guard<std::mutex> lock(g_reg_mutex);
-    for (size_t k = 0; k < g_reg.size(); ++k)
-      if (g_reg[k].base == static_cast<char*>(ptr)) {
-        g_reg.erase(g_reg.begin() + (long)k);
-        break;
-      }
-    g_reg_count.store((int)g_reg.size(), std::memory_order_release);
-  }
-  const hipError_t e = hipHostUnregister(ptr);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return set_err(HDSM_ERR_DEVICE, std::string("hdsm_host_unregister: ") + hipGetErrorString(e));
-  }
-  return HDSM_OK;
-}
-
-int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agent_id,
-                const double* state_curr, const double* traj_ref, const int32_t* n_poly,
-                const int32_t* n_rows_static, const double* A_static, const double* b_static,
-                const double* plans_all, const uint8_t* has_plan, double* traj_out, double* ctrl_out,
-                uint8_t* poly_used, int32_t* status, double* obj) {
-  Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
-  if (n_inst == 0) return HDSM_OK;
-  if (!agent_id || !state_curr || !traj_ref || !n_poly || !n_rows_static || !A_static || !b_static ||
-      !plans_all || !has_plan || !traj_out || !ctrl_out || !poly_used || !status || !obj)
-    return set_err(HDSM_ERR_BAD_ARG, "null array argument");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t I = (size_t)n_inst, N = (size_t)h->N, P = (size_t)h->P, RS = (size_t)h->RS;
-  hdsm_handle::HostStaging& s = h->stage;
-  hipStream_t st = h->stream.get();
-  const auto H2D = hipMemcpyHostToDevice;
-  const auto D2H = hipMemcpyDeviceToHost;
-  HIP_TRY(join_stream(h, st));
-  bool in_mapped = true;
-  {
-    const void* hp[9] = {agent_id, state_curr, traj_ref, n_poly, n_rows_static, A_static, b_static, plans_all, has_plan};
-    const size_t hb[9] = {I * 4, I * 9 * 8, I * N * 6 * 8, I * 4, I * P * 4, I * P * RS * 3 * 8, I * P * RS * 8, (size_t)n_rob * (N + 1) * 9 * 8, (size_t)n_rob};
-    void* dp[9];
-    for (int k = 0; k < 9 && in_mapped; ++k) in_mapped = mapped_host_range(hp[k], hb[k], &dp[k]);
-    if (in_mapped) {  // page-locked arrays of the caller (hdsm_host_register): one fetch kernel
-      FetchArgs f{};
-      f.n_inst = n_inst, f.n_rob = n_rob, f.N = (int)N, f.P = (int)P, f.RS = (int)RS;
-      const int64_t plan_items = (int64_t)n_rob * (int64_t)(N + 1) * 9;
-      f.plan_blocks = (int)((plan_items + 1023) / 1024 < 1 ? 1 : ((plan_items + 1023) / 1024 > 1024 ? 1024 : (plan_items + 1023) / 1024));
-      f.agent_id = static_cast<const int32_t*>(dp[0]), f.state = static_cast<const double*>(dp[1]), f.ref = static_cast<const double*>(dp[2]);
-      f.n_poly = static_cast<const int32_t*>(dp[3]), f.n_rows = static_cast<const int32_t*>(dp[4]), f.A = static_cast<const double*>(dp[5]);
-      f.b = static_cast<const double*>(dp[6]), f.plans = static_cast<const double*>(dp[7]), f.has = static_cast<const uint8_t*>(dp[8]);
-      f.d_agent = s.d_agent.get(), f.d_state = s.d_state.get(), f.d_ref = s.d_ref.get(), f.d_npoly = s.d_npoly.get(), f.d_nrows = s.d_nrows.get();
-      f.d_A = s.d_A.get(), f.d_b = s.d_b.get(), f.d_plans = s.d_plans.get(), f.d_has = s.d_has.get();
-      hipLaunchKernelGGL(k_fetch, dim3((unsigned)(n_inst + f.plan_blocks)), dim3(256), 0, st, f);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  if (!in_mapped) {
-    HIP_TRY(hipMemcpyAsync(s.d_agent.get(), agent_id, I * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_state.get(), state_curr, I * 9 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_ref.get(), traj_ref, I * N * 6 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_npoly.get(), n_poly, I * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_nrows.get(), n_rows_static, I * P * 4, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_A.get(), A_static, I * P * RS * 3 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_b.get(), b_static, I * P * RS * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_plans.get(), plans_all, (size_t)n_rob * (N + 1) * 9 * 8, H2D, st));
-    HIP_TRY(hipMemcpyAsync(s.d_has.get(), has_plan, (size_t)n_rob, H2D, st));
-  }
-  int rc = hdsm_replan_device(handle, n_inst, n_rob, s.d_agent.get(), s.d_state.get(), s.d_ref.get(), s.d_npoly.get(), s.d_nrows.get(),
-                              s.d_A.get(), s.d_b.get(), s.d_plans.get(), s.d_has.get(), s.d_traj.get(), s.d_ctrl.get(), s.d_used.get(),
-                              s.d_status.get(), s.d_obj.get(), st);
-  if (rc) return rc;
-  if (h->last_small && h->rescue_ttl == 0) {  // (a launch that already carried the rescue pass needs no second one)
-    HIP_TRY(hipStreamSynchronize(st));
-    if (*h->ovf_flag.host() != 0) {  // an instance ran out of staging rows in a shared-CU kernel: solve it again now, with the large area
-      *h->ovf_flag.host() = 0, h->rescue_ttl = 256;
-      rc = launch_rescue(h, h->last_args, st);
-      if (rc) return rc;
-    }
-  }
-  // Outputs are "left untouched" for instances without a solution. The caller's arrays are not uploaded to seed the device
-  // copies (a megabyte each way per 1024 agents): the results come back into a pinned staging block of the handle and only
-  // the instances that HAVE a solution are copied into the caller's arrays.
-  const size_t trj = (N + 1) * 9, ctl = N * 3;
-  void* dp[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  {  // page-locked output arrays (hdsm_host_register, every array inside a registered range): delivered by the device, filtered there
-    void* hp[5] = {traj_out, ctrl_out, obj, status, poly_used};
-    const size_t hb[5] = {I * trj * 8, I * ctl * 8, I * 8, I * 4, I * P};
-    bool mapped = true;
-    for (int k = 0; k < 5 && mapped; ++k) mapped = mapped_host_range(hp[k], hb[k], &dp[k]);
-    if (!mapped) dp[0] = nullptr;
-  }
-  if (dp[0] != nullptr) {
-    hipLaunchKernelGGL(k_deliver, dim3((unsigned)((I + 3) / 4)), dim3(256), 0, st, n_inst, (int)trj, (int)ctl, (int)P, s.d_traj.get(), s.d_ctrl.get(), s.d_obj.get(),
-                       s.d_status.get(), s.d_used.get(), static_cast<double*>(dp[0]), static_cast<double*>(dp[1]), static_cast<double*>(dp[2]),
-                       static_cast<int32_t*>(dp[3]), static_cast<uint8_t*>(dp[4]));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-  } else {
-    HIP_TRY(s.out.ensure(I * (trj * 8 + ctl * 8 + 8 + 4 + P)));
-    double* o_traj = static_cast<double*>(s.out.get());
-    double* o_ctrl = o_traj + I * trj;
-    double* o_obj = o_ctrl + I * ctl;
-    int32_t* o_status = reinterpret_cast<int32_t*>(o_obj + I);
-    uint8_t* o_used = reinterpret_cast<uint8_t*>(o_status + I);
-    HIP_TRY(hipMemcpyAsync(o_traj, s.d_traj.get(), I * trj * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_ctrl, s.d_ctrl.get(), I * ctl * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_obj, s.d_obj.get(), I * 8, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_status, s.d_status.get(), I * 4, D2H, st));
-    HIP_TRY(hipMemcpyAsync(o_used, s.d_used.get(), I * P, D2H, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    for (size_t k = 0; k < I; ++k) {
-      status[k] = o_status[k];
-      if (o_status[k] == HDSM_NO_SOLUTION) continue;
-      std::memcpy(traj_out + k * trj, o_traj + k * trj, trj * 8);
-      std::memcpy(ctrl_out + k * ctl, o_ctrl + k * ctl, ctl * 8);
-      std::memcpy(poly_used + k * P, o_used + k * P, P);
-      obj[k] = o_obj[k];
-    }
-  }
-  // (one exit for both delivery paths: anything added after the download applies to registered callers too)
-  return HDSM_OK;
-}
-
 int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agent_id,
                      const double* state_curr, const double* plans_all, const uint8_t* has_plan,
                      double* planes) {
@@ -1417,90 +703,6 @@ int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t*
   cp(planes, s.planes.get(), total * 8, hipMemcpyDeviceToHost);
   if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
   if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_tasc_planes: ") + hipGetErrorString(cp.err.e));
-  return HDSM_OK;
-}
-
-int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_inst, int32_t n_rob,
-                          const int32_t* agent_id, const double* path, const int32_t* n_path, int32_t pmax,
-                          const double* vel_cap, const double* plans_all, const uint8_t* has_plan,
-                          double* ref_full, double* ref, double* path_vel, void* hip_stream) {
-  Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
-  if (n_inst == 0) return HDSM_OK;
-  if (!cfg || !agent_id || !path || !n_path || !plans_all || !has_plan || !ref_full || !path_vel || pmax < 1)
-    return set_err(HDSM_ERR_BAD_ARG, "null or empty argument");
-  HIP_TRY(hipSetDevice(h->device));
-  RefArgs a{};
-  a.n_inst = n_inst, a.n_rob = n_rob, a.pmax = pmax, a.N = h->N, a.dt = h->prm.dt, a.cfg = *cfg;
-  a.agent_id = agent_id, a.path = path, a.n_path = n_path, a.vel_cap = vel_cap, a.plans = plans_all;
-  a.has_plan = has_plan, a.ref_full = ref_full, a.ref = ref, a.path_vel = path_vel;
-  hdsm_handle::Prepass& pp = h->pre;
-  a.rpos = pp.d_rpos.get(), a.rsph = pp.d_rsph.get();
-  for (int i = 0; i <= hdsm::MAXH; ++i) {
-    double occ = 100 * std::pow(cfg->sens_other_agents, (double)i);  // AC:1791-1795
-    occ = occ < 0 ? 0 : (occ > 100 ? 100 : occ);
-    a.wocc[i] = std::pow(occ / 100, cfg->sens_pot);  // GetVelocityLimit AC:1805-1817
-  }
-  // d_rpos / d_rsph are scratch of the HANDLE: a call that arrives on another stream than the previous launch waits for it
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  HIP_TRY(join_stream(h, st));
-  h->last_stream = st;
-  {
-    // device-resident loop (defer_done: one stream, the solve of this round follows on the same plans): the pre-pass rides along
-    const bool with_pre = h->defer_done;
-    const bool ordered = with_pre && h->prm.warm_start && h->order_min > 0 && n_inst >= h->order_min;
-    const bool pre = n_rob >= h->bounds_min;
-    hipLaunchKernelGGL(k_ref_pack, dim3((n_rob + 15) / 16 + (ordered ? 1 : 0)), dim3(256), 0, st, h->N, n_rob, plans_all, has_plan, pp.d_rpos.get(), pp.d_rsph.get(),
-                       with_pre ? pp.d_pos.get() : nullptr, with_pre && pre ? pp.d_bounds.get() : nullptr, n_inst, h->d_stats.get() + 7 * h->max_inst, agent_id,
-                       ordered ? pp.d_order.get() : nullptr);
-    pp.plans = with_pre ? plans_all : nullptr, pp.n_rob = n_rob, pp.n_inst = n_inst, pp.ordered = ordered;
-  }
-  HIP_TRY(hipGetLastError());
-  if (n_inst >= 256) hipLaunchKernelGGL(k_reference<64>, dim3(n_inst), dim3(64), 0, st, a);
-  else hipLaunchKernelGGL(k_reference<256>, dim3(n_inst), dim3(256), 0, st, a);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(mark_done(h, st));
-  return HDSM_OK;
-}
-
-int hdsm_reference(void* handle, const hdsm_ref_config* cfg, int32_t n_inst, int32_t n_rob, const int32_t* agent_id,
-                   const double* path, const int32_t* n_path, int32_t pmax, const double* vel_cap,
-                   const double* plans_all, const uint8_t* has_plan, double* ref_full, double* ref, double* path_vel) {
-  Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
-  if (n_inst == 0) return HDSM_OK;
-  if (!cfg || !agent_id || !path || !n_path || !plans_all || !has_plan || !ref_full || !path_vel || pmax < 1)
-    return set_err(HDSM_ERR_BAD_ARG, "null or empty argument");
-  for (int32_t k = 0; k < n_inst; ++k)
-    if (n_path[k] < 1 || n_path[k] > pmax) return set_err(HDSM_ERR_BAD_ARG, "n_path[k] must be in [1, pmax]");
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t I = (size_t)n_inst, N = (size_t)h->N;
-  hdsm_handle::HostStaging& s = h->stage;
-  hipStream_t st = h->stream.get();
-  hipError_t e = s.path.ensure(I * pmax * 3, st);
-  if (e == hipSuccess) e = s.cap.ensure(I, st);
-  if (e == hipSuccess) e = s.full.ensure(I * (N + 1) * 6, st);
-  if (e == hipSuccess) e = s.pv.ensure(I, st);
-  if (e == hipSuccess) e = s.np.ensure(I, st);
-  if (e != hipSuccess) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_reference: ") + hipGetErrorString(e));
-  HIP_TRY(join_stream(h, st));
-  Copies cp{st};
-  cp(s.path.get(), path, I * pmax * 3 * 8, hipMemcpyHostToDevice);
-  cp(s.np.get(), n_path, I * 4, hipMemcpyHostToDevice);
-  if (vel_cap) cp(s.cap.get(), vel_cap, I * 8, hipMemcpyHostToDevice);
-  cp(s.d_agent.get(), agent_id, I * 4, hipMemcpyHostToDevice);
-  cp(s.d_plans.get(), plans_all, (size_t)n_rob * (N + 1) * 9 * 8, hipMemcpyHostToDevice);
-  cp(s.d_has.get(), has_plan, (size_t)n_rob, hipMemcpyHostToDevice);
-  int rc = HDSM_OK;
-  if (cp.err.ok())
-    rc = hdsm_reference_device(handle, cfg, n_inst, n_rob, s.d_agent.get(), s.path.get(), s.np.get(), pmax, vel_cap ? s.cap.get() : nullptr,
-                               s.d_plans.get(), s.d_has.get(), s.full.get(), ref ? s.d_ref.get() : nullptr, s.pv.get(), st);
-  cp(ref_full, s.full.get(), I * (N + 1) * 6 * 8, hipMemcpyDeviceToHost);
-  if (ref) cp(ref, s.d_ref.get(), I * N * 6 * 8, hipMemcpyDeviceToHost);
-  cp(path_vel, s.pv.get(), I * 8, hipMemcpyDeviceToHost);
-  if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
-  if (rc) return rc;
-  if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_reference: ") + hipGetErrorString(cp.err.e));
   return HDSM_OK;
 }
 
@@ -1546,6 +748,70 @@ int hdsm_last_kernel_ms(void* handle, float* ms) {
   return HDSM_OK;
 }
 
+#ifdef HDSM_TIMELINE
+// development aid: the launch seen from the instances (100 MHz clock): span, the slowest instance, late starters
+static int print_timeline(Handle* h, int32_t n_inst) {
+  std::vector<long long> pr((size_t)n_inst * 32);
+  HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  long long t0 = pr[0], t1 = pr[1];
+  int worst = 0, last = 0;
+  double busy = 0;
+  for (int k = 0; k < n_inst; ++k) {
+    const long long b = pr[(size_t)k * 32], e = pr[(size_t)k * 32 + 1];
+    if (b < t0) t0 = b;
+    if (e > t1) t1 = e, last = k;
+    if (e - b > pr[(size_t)worst * 32 + 1] - pr[(size_t)worst * 32]) worst = k;
+    busy += (double)(e - b);
+  }
+  int late = 0;
+  for (int k = 0; k < n_inst; ++k) late += pr[(size_t)k * 32] - t0 > 200;  // started more than 2 us after the first
+  if (const char* path = std::getenv("HDSM_TIMELINE_DUMP")) {  // raw rows for offline analysis, one block per launch
+    if (FILE* f = std::fopen(path, "ab")) {
+      const long long head[2] = {0x54494d454c494e33LL, n_inst};  // ("TIMELIN3": 32 entries per instance)
+      std::fwrite(head, sizeof(long long), 2, f);
+      for (int k = 0; k < n_inst; ++k) std::fwrite(&pr[(size_t)k * 32], sizeof(long long), 32, f);
+      std::fclose(f);
+    }
+  }
+  auto us = [](long long ticks) { return (double)ticks * 0.01; };
+  const long long *w = &pr[(size_t)worst * 32], *l = &pr[(size_t)last * 32];
+  std::fprintf(stderr,
+               "HDSM_TIMELINE span %.2f us | slowest inst %d: %.2f us, start +%.2f, block %lld, iters %lld nodes %lld sweeps %lld staged %lld+%lld flags %lld status %lld | last to finish inst %d: "
+               "start +%.2f dur %.2f block %lld iters %lld | %d of %d started > 2 us late | sum of instance times %.1f us (%.2f per span-slot of 512)\n",
+               us(t1 - t0), worst, us(w[1] - w[0]), us(w[0] - t0), w[2], w[4], w[5], w[6], w[7], w[9], w[8], w[10], last, us(l[0] - t0), us(l[1] - l[0]), l[2], l[4], late,
+               n_inst, us((long long)busy), busy / (double)(t1 - t0) / 512.0);
+  return HDSM_OK;
+}
+#endif
+#ifdef HDSM_PROFILE
+// development aid: phase cycle counters of the slowest instance and the batch mean
+static int print_profile(Handle* h, int32_t n_inst) {
+  std::vector<long long> pr((size_t)n_inst * 32);
+  HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
+  int worst = 0;
+  double mean[32] = {0};
+  for (int k = 0; k < n_inst; ++k) {
+    if (pr[(size_t)k * 32 + 11] > pr[(size_t)worst * 32 + 11]) worst = k;
+    for (int j = 0; j < 32; ++j) mean[j] += (double)pr[(size_t)k * 32 + j] / n_inst;
+  }
+  static const char* nm[32] = {"states", "select", "normal", "d", "sums", "upd", "add", "drop", "setup", "sweep",
+                               "leaf", "TOTAL", "iters", "sweeps", "warm_ops", "warm_cycles", "sw_cull", "sw_filter",
+                               "sw_load", "sw_body", "sw_tail", "su_stage", "su_grad", "su_fact",
+                               "w_prep", "w_fetch", "w_normal", "w_dir", "w_add", "w_pair", "w_drop", "w_7"};
+#ifdef HDSM_PROF_OP  // record 16..31 = slots 8..23: the inside of a regular operation (OP_PROF in hdsm_wave_gi.h / hdsm_wave_gib.h)
+  static const char* op_nm[16] = {"sel_boxes", "sel_rows", "w0_wait_done", "normal_entry", "d_reduce", "d_sums", "d_gather_z", "d_urow", "add_scalars", "add_gather",
+                                  "add_update", "sc_states", "sc_rows", "sc_max", "sc_normal", "sc_wait_go"};
+  for (int j = 0; j < 16; ++j) nm[16 + j] = op_nm[j];
+#endif
+  std::fprintf(stderr, "HDSM_PROFILE worst inst %d:", worst);
+  for (int j = 0; j < 32; ++j) std::fprintf(stderr, " %s=%lld", nm[j], pr[(size_t)worst * 32 + j]);
+  std::fprintf(stderr, "\nHDSM_PROFILE mean:");
+  for (int j = 0; j < 32; ++j) std::fprintf(stderr, " %s=%.0f", nm[j], mean[j]);
+  std::fprintf(stderr, "\n");
+  return HDSM_OK;
+}
+#endif
+
 int hdsm_last_stats(void* handle, int32_t n_inst, int32_t* qp_iters, int32_t* nodes, int32_t* sweeps,
                     int32_t* cand) {
   Handle* h = static_cast<Handle*>(handle);
@@ -1553,63 +819,10 @@ int hdsm_last_stats(void* handle, int32_t n_inst, int32_t* qp_iters, int32_t* no
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipStreamSynchronize(h->last_stream));
 #ifdef HDSM_TIMELINE
-  {  // development aid: the launch seen from the instances (100 MHz clock): span, the slowest instance, late starters
-    std::vector<long long> pr((size_t)n_inst * 32);
-    HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    long long t0 = pr[0], t1 = pr[1];
-    int worst = 0, last = 0;
-    double busy = 0;
-    for (int k = 0; k < n_inst; ++k) {
-      const long long b = pr[(size_t)k * 32], e = pr[(size_t)k * 32 + 1];
-      if (b < t0) t0 = b;
-      if (e > t1) t1 = e, last = k;
-      if (e - b > pr[(size_t)worst * 32 + 1] - pr[(size_t)worst * 32]) worst = k;
-      busy += (double)(e - b);
-    }
-    int late = 0;
-    for (int k = 0; k < n_inst; ++k) late += pr[(size_t)k * 32] - t0 > 200;  // started more than 2 us after the first
-    if (const char* path = std::getenv("HDSM_TIMELINE_DUMP")) {  // raw rows for offline analysis, one block per launch
-      if (FILE* f = std::fopen(path, "ab")) {
-        const long long head[2] = {0x54494d454c494e33LL, n_inst};  // ("TIMELIN3": 32 entries per instance)
-        std::fwrite(head, sizeof(long long), 2, f);
-        for (int k = 0; k < n_inst; ++k) std::fwrite(&pr[(size_t)k * 32], sizeof(long long), 32, f);
-        std::fclose(f);
-      }
-    }
-    auto us = [](long long ticks) { return (double)ticks * 0.01; };
-    const long long *w = &pr[(size_t)worst * 32], *l = &pr[(size_t)last * 32];
-    std::fprintf(stderr,
-                 "HDSM_TIMELINE span %.2f us | slowest inst %d: %.2f us, start +%.2f, block %lld, iters %lld nodes %lld sweeps %lld staged %lld+%lld flags %lld status %lld | last to finish inst %d: "
-                 "start +%.2f dur %.2f block %lld iters %lld | %d of %d started > 2 us late | sum of instance times %.1f us (%.2f per span-slot of 512)\n",
-                 us(t1 - t0), worst, us(w[1] - w[0]), us(w[0] - t0), w[2], w[4], w[5], w[6], w[7], w[9], w[8], w[10], last, us(l[0] - t0), us(l[1] - l[0]), l[2], l[4], late,
-                 n_inst, us((long long)busy), busy / (double)(t1 - t0) / 512.0);
-  }
+  if (int rc = print_timeline(h, n_inst)) return rc;
 #endif
 #ifdef HDSM_PROFILE
-  {  // development aid: phase cycle counters of the slowest instance and the batch mean
-    std::vector<long long> pr((size_t)n_inst * 32);
-    HIP_TRY(hipMemcpy(pr.data(), h->d_prof.get(), pr.size() * sizeof(long long), hipMemcpyDeviceToHost));
-    int worst = 0;
-    double mean[32] = {0};
-    for (int k = 0; k < n_inst; ++k) {
-      if (pr[(size_t)k * 32 + 11] > pr[(size_t)worst * 32 + 11]) worst = k;
-      for (int j = 0; j < 32; ++j) mean[j] += (double)pr[(size_t)k * 32 + j] / n_inst;
-    }
-    static const char* nm[32] = {"states", "select", "normal", "d", "sums", "upd", "add", "drop", "setup", "sweep",
-                                 "leaf", "TOTAL", "iters", "sweeps", "warm_ops", "warm_cycles", "sw_cull", "sw_filter",
-                                 "sw_load", "sw_body", "sw_tail", "su_stage", "su_grad", "su_fact",
-                                 "w_prep", "w_fetch", "w_normal", "w_dir", "w_add", "w_pair", "w_drop", "w_7"};
-#ifdef HDSM_PROF_OP  // record 16..31 = slots 8..23: the inside of a regular operation (OP_PROF in hdsm_wave_gi.h / hdsm_wave_gib.h)
-    static const char* op_nm[16] = {"sel_boxes", "sel_rows", "w0_wait_done", "normal_entry", "d_reduce", "d_sums", "d_gather_z", "d_urow", "add_scalars", "add_gather",
-                                    "add_update", "sc_states", "sc_rows", "sc_max", "sc_normal", "sc_wait_go"};
-    for (int j = 0; j < 16; ++j) nm[16 + j] = op_nm[j];
-#endif
-    std::fprintf(stderr, "HDSM_PROFILE worst inst %d:", worst);
-    for (int j = 0; j < 32; ++j) std::fprintf(stderr, " %s=%lld", nm[j], pr[(size_t)worst * 32 + j]);
-    std::fprintf(stderr, "\nHDSM_PROFILE mean:");
-    for (int j = 0; j < 32; ++j) std::fprintf(stderr, " %s=%.0f", nm[j], mean[j]);
-    std::fprintf(stderr, "\n");
-  }
+  if (int rc = print_profile(h, n_inst)) return rc;
 #endif
   int32_t* dst[4] = {qp_iters, nodes, sweeps, cand};
   for (int k = 0; k < 4; ++k)
@@ -1684,97 +897,6 @@ int hdsm_last_sweep_stats(void* handle, int32_t n_inst, int32_t* sphere_records,
   for (int k = 0; k < 3; ++k)
     if (dst[k])
       HIP_TRY(hipMemcpy(dst[k], h->d_stats.get() + (size_t)(4 + k) * h->max_inst, (size_t)n_inst * 4, hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-// ---- multi-GPU exchange (RCCL) -------------------------------------------------------------------------------------
-struct Comm {
-  ncclComm_t nccl = nullptr;
-  int rank = 0, world = 1, device = 0, rec = 0;  // rec = doubles per published record, (N + 1) * 9
-};
-
-#define NCCL_TRY(expr)                                                                                 \
-  do {                                                                                                  \
-    ncclResult_t r_ = (expr);                                                                           \
-    if (r_ != ncclSuccess) return set_err(HDSM_ERR_COMM, std::string(#expr) + ": " + ncclGetErrorString(r_)); \
-  } while (0)
-
-int hdsm_comm_unique_id(uint8_t id[HDSM_COMM_ID_BYTES]) {
-  static_assert(sizeof(ncclUniqueId) <= HDSM_COMM_ID_BYTES, "ncclUniqueId does not fit HDSM_COMM_ID_BYTES");
-  if (!id) return set_err(HDSM_ERR_BAD_ARG, "null id");
-  ncclUniqueId u;
-  NCCL_TRY(ncclGetUniqueId(&u));
-  std::memset(id, 0, HDSM_COMM_ID_BYTES);
-  std::memcpy(id, &u, sizeof u);
-  return HDSM_OK;
-}
-
-int hdsm_comm_create(void* handle, const uint8_t id[HDSM_COMM_ID_BYTES], int32_t rank, int32_t world, void** comm) {
-  Handle* h = static_cast<Handle*>(handle);
-  if (!h || !id || !comm || world < 1 || rank < 0 || rank >= world) return set_err(HDSM_ERR_BAD_ARG, "bad hdsm_comm_create argument");
-  *comm = nullptr;
-  HIP_TRY(hipSetDevice(h->device));
-  Comm* c = new (std::nothrow) Comm;
-  if (!c) return set_err(HDSM_ERR_DEVICE, "out of host memory");
-  c->rank = rank, c->world = world, c->device = h->device, c->rec = (h->N + 1) * 9;
-  ncclUniqueId u;
-  std::memcpy(&u, id, sizeof u);
-  ncclResult_t r = ncclCommInitRank(&c->nccl, world, u, rank);
-  if (r != ncclSuccess) {
-    delete c;
-    return set_err(HDSM_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
-  }
-  *comm = c;
-  return HDSM_OK;
-}
-
-int hdsm_comm_info(void* comm, int32_t* rank, int32_t* world) {
-  Comm* c = static_cast<Comm*>(comm);
-  if (!c) return set_err(HDSM_ERR_BAD_ARG, "null comm");
-  int r = -1, w = -1;
-  NCCL_TRY(ncclCommUserRank(c->nccl, &r));   // what RCCL itself says, not what the caller passed
-  NCCL_TRY(ncclCommCount(c->nccl, &w));
-  if (rank) *rank = r;
-  if (world) *world = w;
-  return HDSM_OK;
-}
-
-void hdsm_comm_destroy(void* comm) {
-  Comm* c = static_cast<Comm*>(comm);
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->nccl) (void)ncclCommDestroy(c->nccl);
-  delete c;
-}
-
-int hdsm_publish_device(void* handle, int32_t per, int32_t n_local, const double* traj, const uint8_t* has_plan_local,
-                        double* plans_local, void* hip_stream) {
-  Handle* h = static_cast<Handle*>(handle);
-  if (!h || per < 0 || n_local < 0 || n_local > per) return set_err(HDSM_ERR_BAD_ARG, "bad hdsm_publish_device argument");
-  if (per == 0) return HDSM_OK;
-  if (!traj || !has_plan_local || !plans_local) return set_err(HDSM_ERR_BAD_ARG, "null array argument");
-  HIP_TRY(hipSetDevice(h->device));
-  const int rec = (h->N + 1) * 9;
-  const int64_t tot = (int64_t)per * rec;
-  hipLaunchKernelGGL(k_publish, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(hip_stream), rec, per,
-                     n_local, traj, has_plan_local, plans_local);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
-
-int hdsm_exchange_device(void* comm, int32_t per, const double* plans_local, double* plans_all, uint8_t* has_plan_all,
-                         void* hip_stream) {
-  Comm* c = static_cast<Comm*>(comm);
-  if (!c || per < 0) return set_err(HDSM_ERR_BAD_ARG, "bad hdsm_exchange_device argument");
-  if (per == 0) return HDSM_OK;
-  if (!plans_local || !plans_all || !has_plan_all) return set_err(HDSM_ERR_BAD_ARG, "null array argument");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  // ONE collective per replan round: rank r's shard lands at plans_all + r * per * rec (in place if it already is there)
-  NCCL_TRY(ncclAllGather(plans_local, plans_all, (size_t)per * c->rec, ncclDouble, c->nccl, st));
-  const int n = per * c->world;
-  hipLaunchKernelGGL(k_has_from_sentinel, dim3((n + 255) / 256), dim3(256), 0, st, c->rec, n, plans_all, has_plan_all);
-  HIP_TRY(hipGetLastError());
   return HDSM_OK;
 }
 

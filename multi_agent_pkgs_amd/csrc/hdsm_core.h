@@ -1624,7 +1624,7 @@ struct Solver {
       if (a.st_pairs) a.st_pairs[out] = s.st_pairs;
       if (a.st_flags) a.st_flags[out] = flags;
       if (a.st_key) {
-        // what the next launch sorts by (hdsm_api.hip, launch_order_block): how long this instance took; an instance without
+        // what the next launch sorts by (plan_pack.h, launch_order_block): how long this instance took; an instance without
         // a solution goes first whatever it took — its next replan either ends on the certificate at once or is among the
         // longest of the launch, and starting a short one early costs nothing
         // (+ 9 units per row of the final working set: next to the duration, the size of the active set is what predicts the

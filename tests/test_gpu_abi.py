@@ -707,3 +707,89 @@ def test_replan_device_refuses_a_tensor_of_another_dtype_before_the_launch(hdsm)
     with pytest.raises(hdsm.HdsmError) as e:
         sol.replan(*[big[k] for k in ARG_KEYS])
     assert e.value.code == hdsm.HDSM_ERR_CAPACITY and str(e.value) == "hdsm error -4: n_inst exceeds max_instances of the handle"
+
+
+def _ring_round(prm, n_rob, absent):
+    """A replan round on problems.circle_states' ring, 6.5 m in radius: the agents fly along it at 2 m/s, 1.1 m apart, so every
+    agent's neighbours stay within the staging radius over the whole horizon; one roomy box as corridor."""
+    N, P, RS, dt = prm.n_hor, prm.poly_hor, prm.max_rows_static, prm.dt
+    R, w = 6.5, 2.0 / 6.5
+    starts, _ = problems.circle_states(n_rob, R=R, cx=0.0, cy=0.0)
+    ang = np.arctan2(starts[:, 1], starts[:, 0])[:, None] + w * dt * np.arange(N + 1)[None, :]
+    plans = np.zeros((n_rob, N + 1, 9))
+    plans[:, :, 0], plans[:, :, 1], plans[:, :, 2] = R * np.cos(ang), R * np.sin(ang), 1.5
+    plans[:, :, 3], plans[:, :, 4] = -R * w * np.sin(ang), R * w * np.cos(ang)
+    plans[:, :, 6], plans[:, :, 7] = -R * w * w * np.cos(ang), -R * w * w * np.sin(ang)
+    state = plans[:, 1].copy()
+    ref = np.stack([problems.ref_from_path(state[k, :3], state[k, 3:6], R * w, dt, N) for k in range(n_rob)])
+    n_poly, n_rows, A, b = problems.pack_static([[problems.box_rows(state[k, :3] - 3.0, state[k, :3] + 3.0)] for k in range(n_rob)], P, RS)
+    has_plan = np.ones(n_rob, np.uint8)
+    has_plan[absent] = 0
+    plans[absent] = 0.0
+    return dict(agent_id=np.arange(n_rob, dtype=np.int32), state=state, ref=ref, n_poly=n_poly, n_rows=n_rows, A=A, b=b, plans=plans,
+                has_plan=has_plan)
+
+
+@pytest.mark.parametrize("n_hor", [10, 16])
+def test_prepass_carried_by_the_reference_equals_the_solvers_own(hdsm, monkeypatch, n_hor):
+    """The solver's pre-pass — packed positions of steps 1..N, their enclosing sphere, the launch order — is computed by
+    k_plan_prepass, or, in the device-resident loop, left by k_ref_pack of the reference trajectory that precedes the solve on the
+    same plans (both form the sphere with plan_pack.h's plan_sphere16). Handle A replans alone; handle B runs the loop's sequence
+    (records deferred, reference, replan, one record). 37 agents: the last group of 16 is partly dead; five agents without a plan at
+    both ends and inside a group; H = 10 leaves lanes idle, H = 16 puts step 16 into the second slot of k_ref_pack's lane 0. Two
+    rounds: the second launches warm and in the order of the first's keys. Answers bit for bit, statistics and sphere / pair counts
+    per instance — the pair count is what a different sphere changes first. (The test cannot see which pre-pass ran: the `packed`
+    condition of launch() is exercised end to end by the device-loop tests.)"""
+    import ctypes as C
+    import torch
+    monkeypatch.setenv("HDSM_BOUNDS_MIN", "1")
+    monkeypatch.setenv("HDSM_ORDER_MIN", "1")
+    n = 37
+    prm = agile_params(n_hor, max_rows_static=18)
+    N, P = prm.n_hor, prm.poly_hor
+    sn = _ring_round(prm, n, absent=[0, 5, 17, 20, 36])
+    sols = [hdsm.Solver(prm, n, n), hdsm.Solver(prm, n, n)]   # (hdsm_create reads the two knobs)
+    L = hdsm.load()
+    dev = torch.device("cuda", 0)
+    d = {k: torch.from_numpy(np.ascontiguousarray(sn[k])).to(dev) for k in ARG_KEYS}
+    path = np.zeros((n, 2, 3))
+    path[:, 0], path[:, 1] = sn["state"][:, :3], sn["state"][:, :3] + 5.0 * sn["state"][:, 3:6]
+    d_path, d_npath = torch.from_numpy(path).to(dev), torch.full((n,), 2, dtype=torch.int32, device=dev)
+    r_full, r_ref, r_pv = (torch.zeros(s, dtype=torch.float64, device=dev) for s in ((n, N + 1, 6), (n, N, 6), (n,)))
+    st = torch.cuda.Stream(device=dev)
+    hst = C.c_void_p(st.cuda_stream)
+    any_spheres = False
+    for rnd in range(2):
+        got = []
+        for which, sol in enumerate(sols):
+            o = dict(traj=torch.full((n, N + 1, 9), np.nan, dtype=torch.float64, device=dev), ctrl=torch.full((n, N, 3), np.nan, dtype=torch.float64, device=dev),
+                     used=torch.zeros((n, P), dtype=torch.uint8, device=dev), status=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                     obj=torch.full((n,), np.nan, dtype=torch.float64, device=dev))
+            torch.cuda.synchronize()
+            if which == 1:
+                assert L.hdsm_internal_defer_done(sol.h, C.c_int(1)) == 0
+                sol.reference_device(agile_ref_config(), d["agent_id"], d_path, d_npath, d["plans"], d["has_plan"], r_full, r_ref, r_pv, stream=st)
+            sol.replan_device(*[d[k] for k in ARG_KEYS], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"], stream=st)
+            if which == 1:
+                assert L.hdsm_internal_defer_done(sol.h, C.c_int(0)) == 0
+                assert L.hdsm_internal_record_done(sol.h, hst) == 0
+            torch.cuda.synchronize()
+            g = {k: v.cpu().numpy() for k, v in o.items()}
+            g.update(sol.last_stats(n))
+            g.update(sol.last_sweep_stats(n))
+            got.append(g)
+        a, b = got
+        solved = a["status"] != 2
+        assert solved.any() and (a["status"] >= 0).all(), (rnd, a["status"])
+        for k in ("status", "traj", "ctrl", "obj"):
+            assert a[k].tobytes() == b[k].tobytes(), (rnd, k)
+        for k in ("traj", "ctrl", "obj"):
+            assert np.isfinite(a[k][solved]).all(), (rnd, k)
+        for k in ("qp_iters", "nodes", "sweeps", "cand", "sphere_records", "pairs"):
+            assert (a[k] == b[k]).all(), (rnd, k, a[k], b[k])
+        any_spheres = any_spheres or bool((a["sphere_records"] > 0).any())
+        # the next round: every agent that had a plan and got an answer publishes it
+        pub = torch.from_numpy(solved & (sn["has_plan"] != 0)).to(dev)
+        d["plans"][pub] = torch.from_numpy(a["traj"]).to(dev)[pub]
+        d["state"][pub] = d["plans"][pub][:, 1]
+    assert any_spheres
