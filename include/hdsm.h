@@ -182,8 +182,11 @@ int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agen
  * Streams: a handle owns per-instance device state (branch-and-bound snapshots, warm-start sets, the prefilter
  * records). Launches on ONE stream are ordered by the stream; when a call arrives on a different stream than the
  * previous launch of the same handle, the library makes the new stream wait for that launch (event), so successive
- * calls never overlap on the handle's state whatever streams they use. The host-pointer entry points use the handle's
- * own stream. Every entry point selects the handle's device itself.                                          */
+ * calls never overlap on the handle's state whatever streams they use. The event is recorded on the PREVIOUS stream at
+ * that moment, not behind every launch (a caller that stays on one stream, the normal case, has no event on its queue):
+ * a stream passed to a device entry point must therefore outlive the next call on the handle (any entry point, the
+ * statistics getters included). The host-pointer entry points use the handle's own stream. Every entry point selects
+ * the handle's device itself.                                                                                 */
 int hdsm_replan_device(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agent_id,
                        const double* state_curr, const double* traj_ref, const int32_t* n_poly,
                        const int32_t* n_rows_static, const double* A_static, const double* b_static,

@@ -715,9 +715,10 @@ int hdsm_reset_warm_start(void* handle) {
   return HDSM_OK;
 }
 
-// Internal (csrc/swarm_kernels.hip; not in include/): every device entry point records ev_done so that a later call on ANOTHER
-// stream can wait for the handle's scratch. Each record is a barrier packet — 5-6 us of idle queue in front of the next kernel.
-// The device-resident loop issues its whole round on one stream, so it defers the records and leaves one at the end of the round.
+// Internal (csrc/swarm_kernels.hip; not in include/): the device-resident loop issues its whole round on one stream and says so
+// (defer_done: the pre-pass of its solve rides on the reference kernel); at the end of the round it names the point a later call on
+// ANOTHER stream has to wait for. (Until the done event became lazy — hdsm_entry.h, join_stream — every device entry point recorded
+// it, a barrier packet in front of the next kernel, and this pair existed to leave one record per round instead of one per call.)
 extern "C" int hdsm_internal_defer_done(void* handle, int on) {
   Handle* h = static_cast<Handle*>(handle);
   if (!h) return HDSM_ERR_BAD_ARG;
@@ -727,7 +728,12 @@ extern "C" int hdsm_internal_defer_done(void* handle, int on) {
 extern "C" int hdsm_internal_record_done(void* handle, void* hip_stream) {
   Handle* h = static_cast<Handle*>(handle);
   if (!h) return HDSM_ERR_BAD_ARG;
-  HIP_TRY(hipEventRecord(h->ev_done.get(), static_cast<hipStream_t>(hip_stream)));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  if (h->launched && st == h->last_stream) {  // the tail of last_stream at the next join is at or after this point
+    h->done_pending = true;
+    return HDSM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ev_done.get(), st));  // (a stream the handle has not launched on: as before)
   return HDSM_OK;
 }
 

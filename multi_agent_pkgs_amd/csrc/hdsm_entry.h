@@ -31,16 +31,22 @@ int rescue_if_flagged(Handle* h, hipStream_t st);
 
 // The handle's device state (snapshots, warm-start sets, prefilter records, staging buffers) is shared by all its calls: one that
 // arrives on another stream than the previous launch waits for it. (Who launches on `st` also names it as last_stream; who only
-// stages into the handle's buffers does not.)
+// stages into the handle's buffers does not.) The event it waits for is recorded HERE, at the tail of last_stream — at or after the
+// handle's last launch, which is all the wait needs — and not after every launch: a caller that stays on one stream (the documented
+// normal case) never puts a record, a barrier packet in front of its next kernel, on its queue. last_stream must still be alive.
 inline hipError_t join_stream(Handle* h, hipStream_t st) {
-  return h->launched && st != h->last_stream ? hipStreamWaitEvent(st, h->ev_done.get(), 0) : hipSuccess;
+  if (!h->launched || st == h->last_stream) return hipSuccess;
+  if (h->done_pending) {
+    if (const hipError_t e = hipEventRecord(h->ev_done.get(), h->last_stream)) return e;
+    h->done_pending = false;
+  }
+  return hipStreamWaitEvent(st, h->ev_done.get(), 0);
 }
 
-// ... and this is the point it waits for: the end of what a device entry point enqueued
+// ... and this is the point it waits for: the end of what a device entry point enqueued on last_stream (nothing is recorded here)
 inline hipError_t mark_done(Handle* h, hipStream_t st) {
-  if (!h->defer_done)
-    if (const hipError_t e = hipEventRecord(h->ev_done.get(), st)) return e;
-  h->launched = true;
+  (void)st;
+  h->launched = true, h->done_pending = true;
   return hipSuccess;
 }
 

@@ -93,9 +93,10 @@ struct Handle {
 
   hdsm_mem::DevStream stream;
   hipStream_t last_stream = nullptr;
-  hdsm_mem::DevEvent ev_done;  // recorded after every launch: orders launches that arrive on different streams
+  hdsm_mem::DevEvent ev_done;  // orders launches that arrive on different streams: recorded on last_stream when a call on ANOTHER stream joins
   bool launched = false;
-  bool defer_done = false;     // the device-resident loop records ev_done once per round (hdsm_internal_record_done), not once per call
+  bool done_pending = false;   // launches on last_stream since ev_done was last recorded (hdsm_entry.h, mark_done / join_stream)
+  bool defer_done = false;     // the device-resident loop is issuing a round on one stream (hdsm_internal_defer_done): the pre-pass rides on the reference
   hdsm_mem::TimedInterval kernel_time;  // hdsm_set_kernel_timing: around the solver kernel alone (after the pre-pass)
   bool time_kernel = false;
 

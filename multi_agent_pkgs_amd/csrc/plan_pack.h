@@ -58,19 +58,38 @@ __device__ __forceinline__ void plan_sphere16(bool lead, double* rec, bool has, 
 // then needs no second, dependent load (agent_id[instance]) before it can ask for the agent's own plan.
 __device__ inline void launch_order_block(int n_inst, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id, int32_t* __restrict__ order) {
   __shared__ int bucket[256];
+  __shared__ int wave_total[4];
   const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  // The block is ONE chain of dependent steps (histogram, scan, scatter), and it sits in a launch whose other workgroups need two or three
+  // memory round trips: so every thread asks for all its keys and agent ids at once, before the first LDS operation, and keeps them in
+  // registers for both passes — one round trip for batches of up to LB x 256 instances. (Walking the keys once per pass, a load and an LDS
+  // atomic at a time, was eight dependent trips at 1024 instances.) The instances beyond the first batch take a batch-wide trip per pass.
+  constexpr int LB = 4;
+  int bk[LB], ag[LB];
+#pragma unroll
+  for (int u = 0; u < LB; ++u) {
+    const int k = tid + u * nt;
+    const int it = k < n_inst ? key_prev[k] : 0;
+    ag[u] = k < n_inst ? agent_id[k] : 0;
+    bk[u] = 255 - (it < 0 ? 0 : (it > 255 ? 255 : it));
+  }
   for (int b = tid; b < 256; b += nt) bucket[b] = 0;
   __syncthreads();
-  for (int k = tid; k < n_inst; k += nt) {
-    const int it = key_prev[k];
-    atomicAdd(&bucket[255 - (it < 0 ? 0 : (it > 255 ? 255 : it))], 1);
+#pragma unroll
+  for (int u = 0; u < LB; ++u)
+    if (tid + u * nt < n_inst) atomicAdd(&bucket[bk[u]], 1);
+  for (int k0 = LB * nt + tid; k0 - tid < n_inst; k0 += LB * nt) {
+    int it[LB];
+#pragma unroll
+    for (int u = 0; u < LB; ++u) it[u] = k0 + u * nt < n_inst ? key_prev[k0 + u * nt] : 0;
+#pragma unroll
+    for (int u = 0; u < LB; ++u)
+      if (k0 + u * nt < n_inst) atomicAdd(&bucket[255 - (it[u] < 0 ? 0 : (it[u] > 255 ? 255 : it[u]))], 1);
   }
   __syncthreads();
   // exclusive prefix over the 256 buckets, a bucket per thread (every launch of this block has 256 threads): scan inside the wavefront,
-  // then the totals of the wavefronts before. (One thread walked the buckets before round 6, 256 dependent LDS round trips; the bench line
-  // does not see the difference — the pre-pass launch is as long as its set-up map tiles.)
+  // then the totals of the wavefronts before. (One thread walked the buckets before round 6, 256 dependent LDS round trips.)
   {
-    __shared__ int wave_total[4];
     const int c = bucket[tid & 255];
     int incl = c;
 #pragma unroll
@@ -85,9 +104,19 @@ __device__ inline void launch_order_block(int n_inst, const int32_t* __restrict_
     if (tid < 256) bucket[tid] = base + incl - c;
   }
   __syncthreads();
-  for (int k = tid; k < n_inst; k += nt) {
-    const int it = key_prev[k];
-    const int slot = atomicAdd(&bucket[255 - (it < 0 ? 0 : (it > 255 ? 255 : it))], 1);
-    order[2 * slot] = k, order[2 * slot + 1] = agent_id[k];
+  int2* const pairs = reinterpret_cast<int2*>(order);  // (read as int2 by the solver's workgroups too)
+#pragma unroll
+  for (int u = 0; u < LB; ++u)
+    if (tid + u * nt < n_inst) pairs[atomicAdd(&bucket[bk[u]], 1)] = make_int2(tid + u * nt, ag[u]);
+  for (int k0 = LB * nt + tid; k0 - tid < n_inst; k0 += LB * nt) {
+    int it[LB], id[LB];
+#pragma unroll
+    for (int u = 0; u < LB; ++u) {
+      const int k = k0 + u * nt;
+      it[u] = k < n_inst ? key_prev[k] : 0, id[u] = k < n_inst ? agent_id[k] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < LB; ++u)
+      if (k0 + u * nt < n_inst) pairs[atomicAdd(&bucket[255 - (it[u] < 0 ? 0 : (it[u] > 255 ? 255 : it[u]))], 1)] = make_int2(k0 + u * nt, id[u]);
   }
 }

@@ -1106,8 +1106,9 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
   }
   HIP_TRY(hipSetDevice(d->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  // The solver handle's "done" event (what a later call on another stream waits for) is recorded once, when the round has been
-  // issued, instead of after each of its entry points: every record is a barrier packet in front of the next kernel (5-6 us each).
+  // The round is issued on ONE stream and says so to the solver handle: the pre-pass of the solve then rides on the reference kernel
+  // (hdsm_api.hip, `packed`). At its end it names the point a later call on another stream has to wait for; the handle records its
+  // "done" event only when such a call arrives (hdsm_entry.h) — a record is a barrier packet, 5-6 us of idle queue in front of the next kernel.
   struct DoneOnce {
     void* solver;
     hipStream_t st;

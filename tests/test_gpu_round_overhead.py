@@ -1,0 +1,195 @@
+"""What a replan round spends outside the solver kernel: the launch-order workgroup of the pre-pass keeps its keys in registers, and the
+handle's done event is recorded only when a call arrives on another stream. Neither may change an answer: the launch order is a
+permutation whatever the batch size, the pre-pass leaks nothing of a plan record that is absent or not finite, and calls that hop
+between streams still see what the previous call wrote.
+
+Small swarms on a ring (circle scenario, H = 10 unless stated, agile_params): neighbours 1.1 m apart flying along the ring."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import problems
+from multi_agent_pkgs_amd.params import agile_params
+
+pytestmark = pytest.mark.gpu
+
+ARG_KEYS = ("agent_id", "state", "ref", "n_poly", "n_rows", "A", "b", "plans", "has_plan")
+
+
+@pytest.fixture(scope="module")
+def hdsm():
+    from multi_agent_pkgs_amd import lib
+    return lib
+
+
+def ring_round(prm, n_rob, absent=()):
+    """A replan round of n_rob agents on a ring (neighbours 1.1 m apart, at least 2 m in radius) which they fly along at 2 m/s; one
+    roomy box as corridor. `absent`: agents without a plan."""
+    N, P, RS, dt = prm.n_hor, prm.poly_hor, prm.max_rows_static, prm.dt
+    R = max(2.0, 1.1 * n_rob / (2 * np.pi))
+    w = 2.0 / R
+    starts, _ = problems.circle_states(n_rob, R=R, cx=0.0, cy=0.0)
+    ang = np.arctan2(starts[:, 1], starts[:, 0])[:, None] + w * dt * np.arange(N + 1)[None, :]
+    plans = np.zeros((n_rob, N + 1, 9))
+    plans[:, :, 0], plans[:, :, 1], plans[:, :, 2] = R * np.cos(ang), R * np.sin(ang), 1.5
+    plans[:, :, 3], plans[:, :, 4] = -R * w * np.sin(ang), R * w * np.cos(ang)
+    plans[:, :, 6], plans[:, :, 7] = -R * w * w * np.cos(ang), -R * w * w * np.sin(ang)
+    state = plans[:, 1].copy()
+    ref = np.stack([problems.ref_from_path(state[k, :3], state[k, 3:6], R * w, dt, N) for k in range(n_rob)])
+    n_poly, n_rows, A, b = problems.pack_static([[problems.box_rows(state[k, :3] - 3.0, state[k, :3] + 3.0)] for k in range(n_rob)], P, RS)
+    has_plan = np.ones(n_rob, np.uint8)
+    has_plan[list(absent)] = 0
+    return dict(agent_id=np.arange(n_rob, dtype=np.int32), state=state, ref=ref, n_poly=n_poly, n_rows=n_rows, A=A, b=b, plans=plans,
+                has_plan=has_plan)
+
+
+def device_args(sn, dev):
+    import torch
+    return {k: torch.from_numpy(np.ascontiguousarray(sn[k])).to(dev) for k in ARG_KEYS}
+
+
+def stale_outputs(n, N, P, dev):
+    import torch
+    return dict(traj=torch.full((n, N + 1, 9), np.nan, dtype=torch.float64, device=dev), ctrl=torch.full((n, N, 3), np.nan, dtype=torch.float64, device=dev),
+                used=torch.zeros((n, P), dtype=torch.uint8, device=dev), status=torch.full((n,), -1, dtype=torch.int32, device=dev),
+                obj=torch.full((n,), np.nan, dtype=torch.float64, device=dev))
+
+
+@pytest.mark.parametrize("n", [1, 63, 256, 257, 600])
+def test_launch_order_from_registers_is_a_permutation_at_every_batch_size(hdsm, n):
+    """launch_order_block keeps a thread's keys and agent ids in registers: one item per thread up to 256 instances, two from 257 on, 600 gives
+    three and a ragged last batch, 1 and 63 leave most threads without an item. The same two consecutive rounds with the launch order on
+    (launch_order = 1; the second call sorts by the keys the first left) and off (-1), every output array stale before each call: an
+    instance missing from `order` leaves its status at -1 and its rows NaN, a duplicated one displaces another. Same statuses, trajectories
+    and objectives to 1e-9 (the bound the suite holds the same problem to through two launch forms, test_gpu_parity.py)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    got = {}
+    for order in (1, -1):
+        prm = agile_params(10, max_rows_static=18, launch_order=order)
+        N, P = prm.n_hor, prm.poly_hor
+        d = device_args(ring_round(prm, n), dev)
+        sol = hdsm.Solver(prm, n, n)
+        rounds = []
+        for rnd in range(2):
+            o = stale_outputs(n, N, P, dev)
+            torch.cuda.synchronize()
+            sol.replan_device(*[d[k] for k in ARG_KEYS], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"])
+            torch.cuda.synchronize()
+            rounds.append({k: v.cpu().numpy() for k, v in o.items()})
+        sol.close()
+        got[order] = rounds
+    for rnd in range(2):
+        a, b = got[1][rnd], got[-1][rnd]
+        assert (a["status"] >= 0).all() and (b["status"] >= 0).all(), (rnd, a["status"], b["status"])
+        assert (a["status"] == b["status"]).all(), rnd
+        solved = a["status"] != 2
+        assert solved.any()
+        for k in ("traj", "ctrl", "obj"):
+            assert np.isfinite(a[k][solved]).all() and np.isfinite(b[k][solved]).all(), (rnd, k)
+        dt_, dj = np.abs(a["traj"] - b["traj"])[solved].max(), np.abs(a["obj"] - b["obj"])[solved].max()
+        print(f"n = {n}, round {rnd}: ordered against unordered, max |traj| difference {dt_:.3e}, |obj| {dj:.3e}, {int(solved.sum())} solved")
+        assert dt_ < 1e-9 and dj < 1e-9, (rnd, dt_, dj)
+
+
+@pytest.mark.parametrize("n_hor", [10, 15])
+@pytest.mark.parametrize("n_rob", [1, 15, 16, 17, 40])
+def test_prepass_outputs_with_absent_and_non_finite_plans_match_the_oracle(hdsm, oracle, n_rob, n_hor):
+    """What the pre-pass leaves for the solver (packed positions, spheres, the set-up map) from plan buffers that hold garbage where no
+    plan is: agents without a plan carry NaN in their records — a NaN that leaks into `pos` or into a sphere changes a status or a
+    trajectory; one agent publishes a non-finite plan (has_plan = 1): its sphere is the never-culled one. Bounds on at every size
+    (prefilter_min_agents = 1); 15 / 16 / 17 agents end in, at and behind a 16-agent group of the pack workgroups and a 16-instance tile
+    of the set-up map. H = 10: 18 k-steps per tile, two chunks; H = 15: 25 k-steps, three. hdsm_replan_device against the oracle with
+    the tolerances of test_gpu_parity.py. (Written when unconditional plan loads and one-trip tiles were tried: profiles/README.md.)"""
+    import torch
+    from test_gpu_parity import compare
+    prm = agile_params(n_hor, max_rows_static=18, prefilter_min_agents=1)
+    N, P = prm.n_hor, prm.poly_hor
+    absent = [k for k in (0, 5, 14, 16, 20, 39) if k < n_rob and n_rob > 1]
+    sn = ring_round(prm, n_rob, absent)
+    sn["plans"][absent] = np.nan
+    if n_rob > 3:
+        sn["plans"][3, 2:, :3] = np.inf   # has_plan[3] = 1
+        sn["plans"][3, 4, 0] = np.nan
+    dev = torch.device("cuda", 0)
+    d = device_args(sn, dev)
+    o = stale_outputs(n_rob, N, P, dev)
+    sol = hdsm.Solver(prm, n_rob, n_rob)
+    torch.cuda.synchronize()
+    sol.replan_device(*[d[k] for k in ARG_KEYS], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"])
+    torch.cuda.synchronize()
+    g = {k: v.cpu().numpy() for k, v in o.items()}
+    sol.close()
+    want = oracle.replan(prm, *[sn[k] for k in ARG_KEYS], n_threads=8)
+    assert (want["status"] != 2).any()
+    compare(g, want)
+
+
+def _hop_sequence(hdsm, prm, sn, streams, defer_middle):
+    """Six chained calls on one handle: call i reads as plans_all what call i - 1 wrote as traj_out (buffers that start as the first round's
+    plans, so an instance without a solution republishes those). `streams`: a torch stream per device call, None for the host-pointer
+    hdsm_replan (the handle's own stream). Nothing but the handle orders a call after its predecessor on another stream: no event, no
+    device-wide synchronisation between the device calls; the host-pointer call needs its input on the host, so the stream of its
+    predecessor — that stream alone — is synchronised before it."""
+    import torch
+    n, N, P = sn["state"].shape[0], prm.n_hor, prm.poly_hor
+    dev = torch.device("cuda", 0)
+    L = hdsm.load()
+    d = device_args(sn, dev)
+    outs = []
+    for _ in streams:
+        o = stale_outputs(n, N, P, dev)
+        o["traj"].copy_(d["plans"])
+        outs.append(o)
+    sol = hdsm.Solver(prm, n, n)
+    torch.cuda.synchronize()
+    plans, host_plans, prev = d["plans"], None, None
+    res = []
+    for i, st in enumerate(streams):
+        o = outs[i]
+        if defer_middle and i == 2:
+            assert L.hdsm_internal_defer_done(sol.h, C.c_int(1)) == 0
+        if st is None:
+            prev.synchronize()
+            hp = plans.cpu().numpy()
+            g = sol.replan(*[sn[k] for k in ARG_KEYS[:7]], hp, sn["has_plan"], out=dict(traj=hp.copy(), ctrl=np.full((n, N, 3), np.nan), used=np.zeros((n, P), np.uint8),
+                                                                                       status=np.full(n, -1, np.int32), obj=np.full(n, np.nan)), stats=False)
+            res.append({k: g[k].copy() for k in ("traj", "status", "obj")})
+            plans = torch.from_numpy(g["traj"]).to(dev)
+            torch.cuda.current_stream().synchronize()
+        else:
+            sol.replan_device(*[d[k] for k in ARG_KEYS[:7]], plans, d["has_plan"], o["traj"], o["ctrl"], o["used"], o["status"], o["obj"], stream=st)
+            res.append(o)
+            plans, prev = o["traj"], st
+        if defer_middle and i == 3:
+            assert L.hdsm_internal_defer_done(sol.h, C.c_int(0)) == 0
+            assert L.hdsm_internal_record_done(sol.h, C.c_void_p(st.cuda_stream)) == 0
+    torch.cuda.synchronize()
+    sol.close()
+    return [{k: (r[k].cpu().numpy() if hasattr(r[k], "cpu") else r[k]) for k in ("traj", "status", "obj")} for r in res]
+
+
+@pytest.mark.parametrize("defer_middle", [False, True])
+def test_calls_that_hop_between_streams_see_what_the_previous_call_wrote(hdsm, defer_middle):
+    """The done event is recorded lazily: nothing behind a launch, a record on the previous stream when a call arrives on another one.
+    One handle, 40 agents, streams A, A, B, A, the handle's own (hdsm_replan), B; each call's plans are the previous call's trajectories.
+    The answers of the same six calls on ONE stream are the yardstick: same statuses, trajectories and objectives to 1e-9 per call (the
+    suite's bound for one problem through two launch forms; the chain feeds rounding differences of one call into the next, where they
+    move planes by as much — they do not grow). With hdsm_internal_defer_done(1) around calls three and four as well, the device loop's
+    bracket: a call that joins inside it must wait for the launches of the bracket, not for an older record."""
+    import torch
+    prm = agile_params(10, max_rows_static=18)
+    sn = ring_round(prm, 40)
+    dev = torch.device("cuda", 0)
+    A, B, S = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    want = _hop_sequence(hdsm, prm, sn, [S, S, S, S, None, S], False)
+    got = _hop_sequence(hdsm, prm, sn, [A, A, B, A, None, B], defer_middle)
+    assert any((w["status"] == 0).any() for w in want)
+    for i, (g, w) in enumerate(zip(got, want)):
+        assert (w["status"] >= 0).all() and (g["status"] == w["status"]).all(), (i, g["status"], w["status"])
+        ok = w["status"] != 2
+        dt_ = np.abs(g["traj"] - w["traj"]).max()   # (every row: an instance without a solution keeps the first round's plan in both runs)
+        dj = np.abs(g["obj"] - w["obj"])[ok].max() if ok.any() else 0.0
+        print(f"call {i}: hopping against one stream, max |traj| difference {dt_:.3e}, |obj| {dj:.3e}")
+        assert dt_ < 1e-9 and dj < 1e-9, (i, dt_, dj)
