@@ -349,6 +349,18 @@ int hdsm_publish_device(void* handle, int32_t per, int32_t n_local, const double
 int hdsm_exchange_device(void* comm, int32_t per, const double* plans_local, double* plans_all, uint8_t* has_plan_all,
                          void* hip_stream);
 
+/* ---- neighbour groups (ABI 1.8): many independent swarms in one batch ------------------------------------------
+ * A partition of the agent ids [0, n_total) into n_groups contiguous ranges: group_start[n_groups + 1] (host pointer, copied)
+ * with group_start[0] = 0, strictly increasing, group_start[n_groups] = n_total <= n_rob_max. An agent's neighbours are the agents
+ * of its own range and nobody else, wherever the handle enumerates other agents: every result for agent a is what the call
+ * returns without a partition when has_plan is zeroed for every agent outside a's range. Honoured by hdsm_replan,
+ * hdsm_replan_device, hdsm_tasc_planes (rows of agents outside the range are zeros, like absent ones), hdsm_reference and
+ * hdsm_reference_device; hdsm_solve has no neighbours. A call's n_rob may exceed n_total (the padded tail of a sharded exchange:
+ * those ids belong to no group and are nobody's neighbour); n_rob < n_total is HDSM_ERR_BAD_ARG. n_groups = 0 or group_start =
+ * NULL: one group, as before 1.8 (one group covering everything is the same). The groups share hdsm_params and the world; the
+ * warm-start sets and the launch order stay keyed by instance index. Synchronises the handle.                             */
+int hdsm_set_groups(void* handle, int32_t n_groups, const int32_t* group_start);
+
 /* Forget the working sets kept for warm_start (e.g. after re-assigning agents to instance indices).      */
 int hdsm_reset_warm_start(void* handle);
 
@@ -363,7 +375,8 @@ const char* hdsm_last_error(void);
  * _last_audit_round / _last_audit_ms / _set_history / _download_history; all in hdsm_swarm.h); 1.7: + map updates in flight
  * (hdsm_map_region_extent / _region_scratch_bytes / hdsm_map_preprocess_region / _region_device here; hdsm_swarm_update_world,
  * hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats in
- * hdsm_swarm.h); nothing removed or changed.   */
+ * hdsm_swarm.h); 1.8: + neighbour groups (hdsm_set_groups here; hdsm_swarm_set_groups, hdsm_dswarm_group_report and
+ * hdsm_group_report in hdsm_swarm.h); nothing removed or changed.   */
 int32_t hdsm_version(void);
 
 #ifdef __cplusplus

@@ -371,6 +371,33 @@ int hdsm_dswarm_last_audit_ms(void* dswarm, float* ms);
 int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds);
 int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_t max_rounds, int32_t* n_rounds, int32_t* dropped);
 
+/* ---- neighbour groups (ABI 1.8): many independent swarms in one flight ---------------------------------------------------------
+ * The definition is hdsm_set_groups' (hdsm.h): a partition of the ids into contiguous ranges group_start[n_groups + 1], and an agent's
+ * neighbours are the agents of its own range — what the ungrouped code returns when has_plan is zeroed for everybody else.
+ *   hdsm_swarm_set_groups     the host mirror: group_start[n_groups] must equal the mirror's n_rob (HDSM_ERR_BAD_ARG otherwise, and for
+ *                             a non-zero first entry or entries that do not increase strictly); n_groups = 0 or NULL: one group. The
+ *                             host reference generation (ComputePathVelocity's neighbour term) and hdsm_swarm_audit honour it.
+ *   hdsm_dswarm_create        takes the mirror's partition and sets it on the solver handle it is given (no partition: it clears the
+ *                             handle's): the reference, the solver and the audit of every round are grouped, on one rank or several.
+ *   hdsm_dswarm_group_report  out[n_groups] (one record for the whole swarm without a partition): the device form of a per-group flight
+ *                             summary over the group's LOCAL agents (k_group_report: one wavefront per group). Synchronises.
+ *                             Only integer sums, minima and maxima: the result does not depend on the order of reduction. The audit
+ *                             fields are zeros and -1 while the audit was never on; with it on, a group without a pair has
+ *                             sep2_min = DBL_MAX and sep_agent = -1. */
+typedef struct hdsm_group_report {
+  int32_t first, count, n_local;       /* the group's id range [first, first + count) and how many of them are local agents     */
+  int32_t no_solution_last;            /* local agents whose last status is HDSM_NO_SOLUTION                                  */
+  int64_t failed_total;                /* sum of the local agents' n_fail                                                     */
+  double  dist_goal_max;               /* largest distance to the goal among them                                            */
+  int64_t rounds, positions, close_rounds, occupied, unknown, crossed, pot_sum; /* rounds: max; the others: sums             */
+  double  sep2_min;                    /* min of the agents' sep2_min, ties to the lower agent id; DBL_MAX without a pair     */
+  int32_t sep_agent, sep_partner, sep_substep, reserved0;   /* global ids (-1 none)                                          */
+  int64_t sep_round;
+  double  speed_max;
+} hdsm_group_report;
+int hdsm_swarm_set_groups(void* swarm, int32_t n_groups, const int32_t* group_start);
+int hdsm_dswarm_group_report(void* dswarm, hdsm_group_report* out);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

@@ -37,8 +37,9 @@ hipError_t device_alloc(DeviceBufs* b, int G, int n_local, int S);  // (on an er
 
 // One round on `st`. audit: k_audit_pack, k_audit, then k_audit_track (merge, own track, d_round, and the flight record when d_report
 // is given). hist_row (may be NULL): [n_local][9] receives the 9 doubles at state0 + k * state_stride bytes of every subject.
-// With audit == false only the history is written.
-hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const uint8_t* d_has, int n_hor, int first, const Weights& w,
+// With audit == false only the history is written. d_range (neighbour groups; may be NULL = everybody): [G][2] = the id range (lo, hi)
+// a subject takes its partners from.
+hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const uint8_t* d_has, const int32_t* d_range, int n_hor, int first, const Weights& w,
                   const World& wd, hdsm_flight_report* d_report, double warn2, const double* state0, size_t state_stride, double* hist_row,
                   hipStream_t st);
 

@@ -17,6 +17,14 @@ extern "C" int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, 
 extern "C" int hdsm_flight_audit_host(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan,
                                       int32_t first, int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world,
                                       const int32_t wdim[3], const double worigin[3], double voxel_size, hdsm_audit_round* out) {
+  return hdsm_internal_audit_host_grouped(n_rob, plans_all, has_plan, n_hor, step_plan, first, n_local, drone_radius, drone_z_offset, world, wdim,
+                                          worigin, voxel_size, nullptr, out);
+}
+
+extern "C" int hdsm_internal_audit_host_grouped(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan,
+                                                int32_t first, int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world,
+                                                const int32_t wdim[3], const double worigin[3], double voxel_size, const int32_t* range,
+                                                hdsm_audit_round* out) {
   const int rc = hdsm_internal_audit_args(n_rob, plans_all, has_plan, n_hor, step_plan, first, n_local, drone_radius, drone_z_offset, world,
                                           wdim, worigin, voxel_size, out);
   if (rc) return rc;
@@ -33,8 +41,9 @@ extern "C" int hdsm_flight_audit_host(int32_t n_rob, const double* plans_all, co
     if (!has_plan[a]) continue;
     const double* pa = plans_all + (size_t)a * rec;
     hdsm_audit::Best best = hdsm_audit::no_partner();
+    const int b_lo = range ? range[2 * (size_t)a] : 0, b_hi = range ? range[2 * (size_t)a + 1] : n_rob;  // partners: the subject's group
     for (int s = 0; s < step_plan; ++s)
-      for (int b = 0; b < n_rob; ++b) {
+      for (int b = b_lo; b < b_hi; ++b) {
         if (b == a || !has_plan[b]) continue;
         const double* pb = plans_all + (size_t)b * rec;
         hdsm_audit::take(best, hdsm_audit::pair_q(w, pa + 9 * s, pa + 9 * (s + 1), pb + 9 * s, pb + 9 * (s + 1)), s, b);

@@ -28,12 +28,23 @@ __global__ __launch_bounds__(256) void k_audit_pack(int G, int S, int rec, const
 }
 
 __global__ __launch_bounds__(SWEEP_THREADS) void k_audit(int G, int n_local, int S, int first, int tile, Weights w, const double* pos,
-                                                         const uint8_t* has, Partial* part) {
+                                                         const uint8_t* has, const int32_t* __restrict__ range, Partial* part) {
   __shared__ double t_pos[TILE_DOUBLES];
   __shared__ uint8_t t_has[TILE_PARTNERS];
   const int tid = (int)threadIdx.x, k = (int)blockIdx.x * SWEEP_THREADS + tid, chunk = (int)blockIdx.y;
   const int per = (S + 1) * 3, p0 = chunk * tile;
   const int cnt = G - p0 < tile ? G - p0 : tile;  // (>= 1: the grid has ceil(G / tile) chunks)
+  // neighbour groups: a lane takes a partner only inside its subject's id range [lo, hi). A workgroup (ONE wavefront) none of whose
+  // subjects' ranges meets the chunk has nothing to read: "no partner" partials, the tile is not staged.
+  static_assert(SWEEP_THREADS == 64, "the vote below is the whole workgroup's");
+  int lo = 0, hi = G;
+  if (range != nullptr) {
+    lo = k < n_local ? range[2 * (size_t)(first + k)] : 0, hi = k < n_local ? range[2 * (size_t)(first + k) + 1] : 0;
+    if (!__any(lo < p0 + cnt && hi > p0)) {
+      if (k < n_local) part[(size_t)chunk * n_local + k] = Partial{DBL_MAX, -1, 0};
+      return;
+    }
+  }
   for (int e = tid; e < cnt * per; e += SWEEP_THREADS) t_pos[e] = pos[(size_t)p0 * per + e];
   for (int e = tid; e < cnt; e += SWEEP_THREADS) t_has[e] = has[p0 + e];
   __syncthreads();
@@ -47,6 +58,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_audit(int G, int n_local, int
       const double a1[3] = {pa[3 * s + 3], pa[3 * s + 4], pa[3 * s + 5]};
       for (int j = 0; j < cnt; ++j) {
         if (!t_has[j]) continue;  // (the same for every lane)
+        if (p0 + j < lo || p0 + j >= hi) continue;  // (not of this subject's group)
         const double* pb = t_pos + j * per + 3 * s;
         const double q = pair_q(w, a0, a1, pb, pb + 3);
         if (p0 + j != a) take(best, q, s, p0 + j);
@@ -96,7 +108,7 @@ hipError_t device_alloc(DeviceBufs* b, int G, int n_local, int S) {
   return e;
 }
 
-hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const uint8_t* d_has, int n_hor, int first, const Weights& w,
+hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const uint8_t* d_has, const int32_t* d_range, int n_hor, int first, const Weights& w,
                   const World& wd, hdsm_flight_report* d_report, double warn2, const double* state0, size_t state_stride, double* hist_row,
                   hipStream_t st) {
   if (b.n_local <= 0) return hipSuccess;
@@ -105,7 +117,7 @@ hipError_t launch(const DeviceBufs& b, bool audit, const double* d_plans, const 
     const long long elems = (long long)b.G * (b.S + 1) * 3;
     hipLaunchKernelGGL(k_audit_pack, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, st, b.G, b.S, rec, d_plans, b.d_pos.get());
     hipLaunchKernelGGL(k_audit, dim3((unsigned)((b.n_local + SWEEP_THREADS - 1) / SWEEP_THREADS), (unsigned)b.chunks), dim3(SWEEP_THREADS), 0, st,
-                       b.G, b.n_local, b.S, first, b.tile, w, b.d_pos.get(), d_has, b.d_part.get());
+                       b.G, b.n_local, b.S, first, b.tile, w, b.d_pos.get(), d_has, d_range, b.d_part.get());
   }
   hipLaunchKernelGGL(k_audit_track, dim3((unsigned)((b.n_local + 63) / 64)), dim3(64), 0, st, b.n_local, b.S, first, b.chunks, audit ? 1 : 0, wd,
                      b.d_pos.get(), d_plans, rec, d_has, b.d_part.get(), b.d_round.get(), d_report, warn2, state0, state_stride, hist_row);
@@ -142,7 +154,7 @@ extern "C" int hdsm_flight_audit_batch(int32_t device, int32_t n_rob, const doub
     wd.world = d_world.get(), wd.voxel_size = voxel_size;
     if (world)
       for (int k = 0; k < 3; ++k) wd.wdim[k] = wdim[k], wd.worigin[k] = worigin[k];
-    ok(hdsm_audit::launch(b, true, d_plans.get(), d_has.get(), n_hor, first, hdsm_audit::weights(drone_radius, drone_z_offset), wd, nullptr, 0.0, nullptr, 0,
+    ok(hdsm_audit::launch(b, true, d_plans.get(), d_has.get(), nullptr, n_hor, first, hdsm_audit::weights(drone_radius, drone_z_offset), wd, nullptr, 0.0, nullptr, 0,
                           nullptr, nullptr));
     ok(hipDeviceSynchronize());
   }

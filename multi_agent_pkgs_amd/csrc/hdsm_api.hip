@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_launch_order(int n_inst, const int32_t*
 __global__ __launch_bounds__(256) void k_tasc_planes(const hdsm::Consts* __restrict__ cp, int n_inst, int n_rob,
                                                      const int32_t* agent_id, const double* state,
                                                      const double* plans, const uint8_t* has_plan,
-                                                     double* planes) {
+                                                     double* planes, const int32_t* __restrict__ range) {
   const hdsm::Consts& c = *cp;
   const int N = c.N;
   const int64_t total = (int64_t)n_inst * N * n_rob;
@@ -253,7 +253,10 @@ __global__ __launch_bounds__(256) void k_tasc_planes(const hdsm::Consts* __restr
     const int inst = (int)(idx / ((int64_t)n_rob * N));
     const int self = agent_id[inst];
     double row[4] = {0, 0, 0, 0};
-    if (k != self && has_plan[k]) {
+    // (neighbour groups: an agent outside self's id range is absent; an instance whose id is not an agent has no range to take)
+    const bool ranged = range != nullptr && self >= 0 && self < n_rob;
+    const bool near = range == nullptr || (ranged && k >= range[2 * self] && k < range[2 * self + 1]);
+    if (k != self && near && has_plan[k]) {
       double cp3[3];
       const bool own = self >= 0 && self < n_rob && has_plan[self];
       for (int ax = 0; ax < 3; ++ax)
@@ -395,6 +398,9 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   HIP_TRY(join_stream(h, st));
   h->last_stream = st;
   a.bounds = nullptr, a.pos = nullptr, a.order = nullptr;
+  a.range = a.l1_rows == nullptr ? h->range() : nullptr;
+  // (the prefilter pays from a number of NEIGHBOURS on: with a partition the largest group, not the buffer. It shapes work, never answers.)
+  const bool prefilter = h->prefilter_agents(a.n_rob) >= h->bounds_min;
   const bool ordered = a.warm != nullptr && h->order_min > 0 && a.n_inst >= h->order_min;
   if (ordered) a.order = pp.d_order.get();
   const bool packed = h->defer_done && a.l1_rows == nullptr && pp.plans == a.plans && pp.n_rob == a.n_rob && pp.n_inst == a.n_inst && pp.ordered == ordered;
@@ -410,14 +416,14 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   const int sm_blocks = sm.out != nullptr ? (sm.row_tiles * ((a.n_inst + 15) / 16) + 3) / 4 : 0;
   if (packed) {
     a.pos = pp.d_pos.get();
-    a.bounds = a.n_rob >= h->bounds_min ? pp.d_bounds.get() : nullptr;
+    a.bounds = prefilter ? pp.d_bounds.get() : nullptr;
     if (sm_blocks > 0) {  // (the device-resident loop packs the plans elsewhere: the tiles alone)
       sm.first_block = 0;
       hipLaunchKernelGGL(k_plan_prepass, dim3(sm_blocks), dim3(256), 0, st, h->N, 0, a.plans, a.has_plan, pp.d_pos.get(), nullptr, 0, a.st_key, a.agent_id, nullptr, sm);
       HIP_TRY(hipGetLastError());
     }
   } else if (a.l1_rows == nullptr) {
-    double* const bounds = a.n_rob >= h->bounds_min ? pp.d_bounds.get() : nullptr;
+    double* const bounds = prefilter ? pp.d_bounds.get() : nullptr;
     sm.first_block = (a.n_rob + 15) / 16 + (ordered ? 1 : 0);
     hipLaunchKernelGGL(k_plan_prepass, dim3(sm.first_block + sm_blocks), dim3(256), 0, st, h->N, a.n_rob, a.plans, a.has_plan,
                        pp.d_pos.get(), bounds, a.n_inst, a.st_key, a.agent_id, ordered ? pp.d_order.get() : nullptr, sm);
@@ -545,7 +551,7 @@ int64_t scratch_stride_for(int n) {
 
 extern "C" {
 
-int32_t hdsm_version(void) { return (1 << 16) | 7; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister; 1.4: + the path step (hdsm_swarm_set_goals / _set_path_period / _replan_paths / _path_errors, hdsm_local_path_batch / _host, hdsm_dswarm_set_goals / _path_stats / _last_path_ms); 1.5: + the path step's clearance mode (hdsm_swarm_set_path_clearance, hdsm_local_path_dmp_batch / _host); 1.6: + the flight audit and the state history (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report / _last_audit_round / _last_audit_ms / _set_history / _download_history); 1.7: + map updates in flight (hdsm_map_region_extent / _region_scratch_bytes, hdsm_map_preprocess_region / _region_device, hdsm_swarm_update_world, hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats)
+int32_t hdsm_version(void) { return (1 << 16) | 8; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister; 1.4: + the path step (hdsm_swarm_set_goals / _set_path_period / _replan_paths / _path_errors, hdsm_local_path_batch / _host, hdsm_dswarm_set_goals / _path_stats / _last_path_ms); 1.5: + the path step's clearance mode (hdsm_swarm_set_path_clearance, hdsm_local_path_dmp_batch / _host); 1.6: + the flight audit and the state history (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report / _last_audit_round / _last_audit_ms / _set_history / _download_history); 1.7: + map updates in flight (hdsm_map_region_extent / _region_scratch_bytes, hdsm_map_preprocess_region / _region_device, hdsm_swarm_update_world, hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats); 1.8: + neighbour groups (hdsm_set_groups, hdsm_swarm_set_groups, hdsm_dswarm_group_report)
 
 const char* hdsm_last_error(void) { return g_err.c_str(); }
 
@@ -658,7 +664,7 @@ int hdsm_replan_device(void* handle, int32_t n_inst, int32_t n_rob, const int32_
                        double* ctrl_out, uint8_t* poly_used, int32_t* status, double* obj,
                        void* hip_stream) {
   Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (int rc = check_neighbours(h, n_inst, n_rob)) return rc;
   if (n_inst == 0) return HDSM_OK;
   if (!agent_id || !state_curr || !traj_ref || !n_poly || !n_rows_static || !A_static || !b_static ||
       !plans_all || !has_plan || !traj_out || !ctrl_out || !poly_used || !status || !obj)
@@ -677,7 +683,7 @@ int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t*
                      const double* state_curr, const double* plans_all, const uint8_t* has_plan,
                      double* planes) {
   Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (int rc = check_neighbours(h, n_inst, n_rob)) return rc;
   if (n_inst == 0 || n_rob == 0) return HDSM_OK;
   if (!agent_id || !state_curr || !plans_all || !has_plan || !planes)
     return set_err(HDSM_ERR_BAD_ARG, "null array argument");
@@ -697,12 +703,46 @@ int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t*
     const int64_t items = (int64_t)(total / 4);
     const int blocks = (int)((items + 255) / 256 > 4096 ? 4096 : (items + 255) / 256);
     hipLaunchKernelGGL(k_tasc_planes, dim3(blocks), dim3(256), 0, st, h->d_consts.get(), n_inst, n_rob, s.d_agent.get(),
-                       s.d_state.get(), s.d_plans.get(), s.d_has.get(), s.planes.get());
+                       s.d_state.get(), s.d_plans.get(), s.d_has.get(), s.planes.get(), h->range());
     cp.err(hipGetLastError());
   }
   cp(planes, s.planes.get(), total * 8, hipMemcpyDeviceToHost);
   if (cp.err.ok()) cp.err(hipStreamSynchronize(st));
   if (!cp.err.ok()) return set_err(HDSM_ERR_DEVICE, std::string("hdsm_tasc_planes: ") + hipGetErrorString(cp.err.e));
+  return HDSM_OK;
+}
+
+// Neighbour groups. The partition becomes a per-agent table [n_rob_max][2] = (lo, hi) of the agent's id range, (0, 0) behind the
+// partition: a workgroup reads its two bounds with the inputs of its instance (hdsm_core.h, the set-up) and the loops that run over
+// the other agents run over [lo, hi) instead of [0, n_rob) (hdsm_wave_gi.h sweep_planes, k_tasc_planes, k_reference).
+int hdsm_set_groups(void* handle, int32_t n_groups, const int32_t* group_start) {
+  Handle* h = static_cast<Handle*>(handle);
+  if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
+  if (n_groups < 0) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_groups: negative n_groups");
+  const bool none = n_groups == 0 || group_start == nullptr;
+  int gmax = 0;
+  if (!none) {
+    if (group_start[0] != 0) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_groups: group_start[0] must be 0");
+    for (int g = 0; g < n_groups; ++g) {
+      if (group_start[g + 1] <= group_start[g]) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_groups: group_start must be strictly increasing");
+      if (group_start[g + 1] - group_start[g] > gmax) gmax = group_start[g + 1] - group_start[g];
+    }
+    if (group_start[n_groups] > h->n_rob_max) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_groups: more agents than n_rob_max of the handle");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  h->pre.plans = nullptr;  // (a pre-pass of before the change is not this partition's)
+  if (none) {
+    h->n_total = 0, h->group_max = 0;
+    return HDSM_OK;
+  }
+  std::vector<int32_t> table((size_t)h->n_rob_max * 2, 0);
+  for (int g = 0; g < n_groups; ++g)
+    for (int k = group_start[g]; k < group_start[g + 1]; ++k) table[2 * (size_t)k] = group_start[g], table[2 * (size_t)k + 1] = group_start[g + 1];
+  h->n_total = 0;
+  if (!h->d_range) HIP_TRY(h->d_range.alloc(table.size()));
+  HIP_TRY(hipMemcpy(h->d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->n_total = group_start[n_groups], h->group_max = gmax;
   return HDSM_OK;
 }
 

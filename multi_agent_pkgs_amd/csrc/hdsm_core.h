@@ -179,6 +179,8 @@ struct Shm {
   int32_t rc, iters_sh;  // device build: results of wave 0's active-set run, shared with the other waves
   int32_t cmd;           // command word for the helper waves (0 = leave, 1 = scan staged rows)
   int32_t nlist;         // sweeps with a.bounds: neighbours of the current chunk that survive the sphere test
+  int32_t grp[2];        // the id range [lo, hi) this instance takes its neighbours from (Args::range; [0, n_rob) without a partition),
+                         // fetched by the set-up with the instance's inputs: the sweeps read it back as two wave-uniform values
   int32_t list[LC];
   double sw[5];          // sweep scalars: cull radius, own sphere (centre, radius)
   double sw_ref[MAXH + 1][3];  // positions at the last STAGING sweep and its radius (0 = none): every row not staged then
@@ -966,6 +968,14 @@ struct Solver {
       const bool self_ok = self >= 0 && self < g.n_rob;
       const int sidx = self_ok ? self : 0;
       const uint8_t has_own = g.has_plan[sidx];
+      if (tid == 0) {  // the neighbour range (requested with the own plan: no round trip of its own)
+        int lo = 0, hi = g.n_rob;
+        if (g.range != nullptr) {
+          const int r_lo = g.range[2 * sidx], r_hi = g.range[2 * sidx + 1];
+          lo = self_ok ? r_lo : 0, hi = self_ok ? min_i(r_hi, g.n_rob) : 0;
+        }
+        s.grp[0] = lo, s.grp[1] = hi;
+      }
       for (int k = tid; k < 3 * N; k += nt) {
         const int ci = k / 3, cax = k % 3;
         const double from_plan = g.plans[((int64_t)sidx * (N + 1) + (ci + 1)) * 9 + cax];

@@ -67,4 +67,11 @@ inline int check_common(Handle* h, int n_inst, int n_rob) {
   return HDSM_OK;
 }
 
+// ... and for the entry points that enumerate neighbours: a partition (hdsm_set_groups) must lie inside the call's n_rob
+inline int check_neighbours(Handle* h, int n_inst, int n_rob) {
+  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (n_rob < h->n_total) return set_err(HDSM_ERR_BAD_ARG, "n_rob is smaller than the agents of the partition (hdsm_set_groups)");
+  return HDSM_OK;
+}
+
 }  // namespace hdsm_entry

@@ -84,6 +84,12 @@ struct Handle {
   DevBuf<long long> d_prof;  // 32 * max_inst (HDSM_PROFILE / HDSM_TIMELINE builds)
   DevBuf<int32_t> d_warm;    // (MAXNV + 2) * max_inst: previous optimal working sets (params.warm_start)
   DevBuf<uint8_t> d_zero;    // n_rob_max zero bytes (has_plan of level 1)
+  // neighbour groups (hdsm_set_groups): [n_rob_max][2] id range per agent, allocated by the first partition; n_total = 0: none is set.
+  // group_max: the largest group (what the prefilter decision keys on instead of n_rob)
+  DevBuf<int32_t> d_range;
+  int n_total = 0, group_max = 0;
+  const int32_t* range() const { return n_total > 0 ? d_range.get() : nullptr; }
+  int prefilter_agents(int n_rob) const { return n_total > 0 ? group_max : n_rob; }
   // words in mapped pinned memory the kernels raise (Args::ovf_flag, tree_flag, item_total): an instance ended on a staging overflow;
   // an instance met a deep tree; items queued by the last split launch (the merge writes it)
   hdsm_mem::MappedWord ovf_flag, tree_flag, item_total;

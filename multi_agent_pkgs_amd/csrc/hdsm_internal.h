@@ -24,6 +24,9 @@ int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
 // the audit's setting and record (report [n_local], may be NULL on export)
 int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report);
 int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report);
+// the partition of hdsm_swarm_set_groups: n_groups (0: none) and, when group_start is given, its n_groups + 1 entries
+// (at most n_rob + 1); hdsm_dswarm_create sets it on the solver handle it is given
+int hdsm_swarm_export_groups(void* swarm, int32_t* n_groups, int32_t* group_start);
 // rounds flown on the device into the planner records: rows [n_rounds][n_local][9]
 int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows);
 
@@ -31,6 +34,11 @@ int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows)
 int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan, int32_t first,
                              int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world, const int32_t wdim[3],
                              const double worigin[3], double voxel_size, const hdsm_audit_round* out);
+// hdsm_flight_audit_host with neighbour groups: range [n_rob][2] = the id range (lo, hi) a subject takes its partners from
+// (NULL: everybody, which is hdsm_flight_audit_host itself)
+int hdsm_internal_audit_host_grouped(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan, int32_t first,
+                                     int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world, const int32_t wdim[3],
+                                     const double worigin[3], double voxel_size, const int32_t* range, hdsm_audit_round* out);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

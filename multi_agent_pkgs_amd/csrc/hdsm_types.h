@@ -189,6 +189,9 @@ struct Args {
   int32_t* ovf_flag;      // host-visible word an instance raises when it ends on a staging overflow (the handle then adds the rescue pass)
   int32_t* warm_out;      // where the NEXT replan's guess is written: warm itself, or the per-sub-block copy of pass 2
   int32_t* st_key;    // launch-order key for the NEXT launch: duration of this instance in 0.64-us units + 9 per active row (<= 254), 255 = no solution
+  // neighbour groups (hdsm_set_groups): [n_rob_max][2] = the id range [lo, hi) agent k takes its neighbours from ((0, 0) for ids behind
+  // the partition); null = [0, n_rob) for everybody. The last member, and null by default: code that fills Args member by member stays as it is.
+  const int32_t* range = nullptr;
 };
 
 }  // namespace hdsm

@@ -665,7 +665,7 @@ struct WaveGI {
   template <bool SOLO = false>
   static __device__ __forceinline__ void sweep_planes(S& s, const Consts& c, const Args& a, int self, double thresh,
                                                       bool check_fixed, int lane, const double* pts = nullptr, int pstride = 9) {
-    const int N = c.N, n_rob = a.n_rob, nt = SOLO ? 64 : (int)blockDim.x;  // lane = thread of the WORKGROUP (all waves sweep) unless SOLO
+    const int N = c.N, nt = SOLO ? 64 : (int)blockDim.x;  // lane = thread of the WORKGROUP (all waves sweep) unless SOLO
     if (pts == nullptr) pts = &s.st[0][0];
     const GPtr<const double> g_bounds = gptr(a.bounds), g_pos = gptr(a.pos);
     const GPtr<const uint8_t> g_has = gptr(a.has_plan);
@@ -707,9 +707,12 @@ struct WaveGI {
     bar();
     const double cull = s.sw[0], cull2 = cull * cull;
     SW_PROF(8)
-    const int chunk = pre ? S::LC : n_rob;
-    for (int base = 0; base < n_rob; base += chunk) {
-      const int end = (base + chunk < n_rob) ? base + chunk : n_rob;
+    // neighbour groups: the ids the instance sweeps, [lo, hi) instead of [0, n_rob) — two wave-uniform values the set-up left in LDS
+    // (scalar registers from here on: loop bounds, no lane holds them). Lists, chunks and cand_src keep working on global ids.
+    const int g_lo = uni(s.grp[0]), g_hi = uni(s.grp[1]);
+    const int chunk = pre ? S::LC : (g_hi > g_lo ? g_hi - g_lo : 1);
+    for (int base = g_lo; base < g_hi; base += chunk) {
+      const int end = (base + chunk < g_hi) ? base + chunk : g_hi;
       int cnt = end - base;
       if (pre) {
         const double sx = s.sw[1], sy = s.sw[2], sz = s.sw[3], reach0 = cull + s.sw[4];
@@ -783,7 +786,7 @@ struct WaveGI {
         }
         SW_PROF(11)
       }
-      if (pre && end < n_rob) {  // next chunk reuses the list
+      if (pre && end < g_hi) {  // next chunk reuses the list
         bar();
         if (lane == 0) s.nlist = 0;
         bar();

@@ -350,7 +350,8 @@ struct WaveGIB : WaveGI<NVT, CMAX, SMALL> {
         if (i - 1 >= 1) pre = mk_id(K_S, ((i - 1) << 5) | (p & 31));
       } else if (kind == K_C && a.l1_rows == nullptr) {
         const int e = p & 1, i = ((p >> 1) & 31) - 1, k = p >> 6;
-        if (i >= 0 && i + e > c.pinned_steps && k != self && k < a.n_rob && wpre.has) {
+        // (k inside the instance's neighbour range — [0, n_rob) without a partition: a guess kept from before hdsm_set_groups may name others)
+        if (i >= 0 && i + e > c.pinned_steps && k != self && k >= s.grp[0] && k < s.grp[1] && wpre.has) {
           const double op[3] = {wpre.ox, wpre.oy, wpre.oz};
           if (tasc_plane_eval(c, s.cprev[i], op, my_row)) pre = -2, my_m = i + e, my_src = (k << 6) | (i << 1) | e;
         }

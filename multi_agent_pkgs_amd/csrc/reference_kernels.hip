@@ -35,6 +35,7 @@ struct RefArgs {
   double* path_vel;
   const double* rpos;  // [n_rob][N + 1][3] positions of steps 0..N, packed (k_ref_pack)
   const double* rsph;  // [n_rob][4] enclosing sphere of those positions (radius < 0: no plan)
+  const int32_t* range;  // neighbour groups (hdsm_set_groups): [.][2] id range per agent, null = [0, n_rob)
   double wocc[hdsm::MAXH + 1];  // GetVelocityLimit's weight of step i (AC:1791-1795, 1805-1817): config only, evaluated by the host's libm
 };
 
@@ -107,6 +108,12 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   const int self = a.agent_id[inst];
   const int np = min(max(a.n_path[inst], 1), a.pmax);  // the host wrapper rejects counts outside [1, pmax]; device callers are clamped
   const bool own_has = self >= 0 && self < a.n_rob && a.has_plan[self];
+  // the ids the three neighbour scans below run over (the same for the whole workgroup: scalar loads, scalar loop bounds)
+  int g_lo = 0, g_hi = a.n_rob;
+  if (a.range != nullptr) {
+    const bool agent = self >= 0 && self < a.n_rob;
+    g_lo = agent ? a.range[2 * self] : 0, g_hi = agent ? min(a.range[2 * self + 1], a.n_rob) : 0;
+  }
   // the polyline goes through LDS: the sampling walk below is one thread's chain, and every global read in it was a
   // dependent round trip
   const double* pth_g = a.path + (int64_t)inst * a.pmax * 3;
@@ -132,17 +139,17 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
     double gbest = DBL_MAX;
     int jbest = -1;
     constexpr int UB = 8;  // sphere records in flight per thread: the scans are chains of L2 round trips otherwise
-    for (int j0 = tid; j0 < a.n_rob; j0 += UB * NT) {
+    for (int j0 = g_lo + tid; j0 < g_hi; j0 += UB * NT) {
       double4 sj[UB];
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int j = j0 + u * NT;
-        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < a.n_rob ? j : self) * 4);
+        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < g_hi ? j : self) * 4);
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int j = j0 + u * NT;
-        if (j >= a.n_rob || j == self || sj[u].w < 0) continue;  // (w < 0: no plan)
+        if (j >= g_hi || j == self || sj[u].w < 0) continue;  // (w < 0: no plan)
         const double cx = sj[u].x - ss.x, cy = sj[u].y - ss.y, cz = sj[u].z - ss.z;
         const double g = sqrt(cx * cx + cy * cy + cz * cz) - sj[u].w - ss.w;  // every step of j is at least this far (g may be < 0)
         if (g < gbest || jbest < 0) gbest = g, jbest = j;
@@ -205,18 +212,18 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
     if (tid == 0) surv_n = 0;
     __syncthreads();
     int listed = 0;  // (an upper bound of surv_n, the same in every thread)
-    for (int j0 = tid; j0 - tid < a.n_rob; j0 += UB * NT) {
+    for (int j0 = g_lo + tid; j0 - tid < g_hi; j0 += UB * NT) {
       if (listed + UB * NT > SURV_CAP) drain(), listed = 0;
       double4 sj[UB];
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int j = j0 + u * NT;
-        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < a.n_rob ? j : self) * 4);
+        sj[u] = *reinterpret_cast<const double4*>(a.rsph + (int64_t)(j < g_hi ? j : self) * 4);
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
         const int j = j0 + u * NT;
-        if (j >= a.n_rob || j == self || sj[u].w < 0) continue;
+        if (j >= g_hi || j == self || sj[u].w < 0) continue;
         const double cx = sj[u].x - ss.x, cy = sj[u].y - ss.y, cz = sj[u].z - ss.z;
         // (squared: all its steps are further than the closest neighbour's when the gap between the spheres is)
         const double c2 = cx * cx + cy * cy + cz * cz, reach = sj[u].w + ss.w + sqrt(umax) * (1.0 + 1e-9);
@@ -246,7 +253,7 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
       }
     }
   } else if (own_has && np >= 2) {  // (a configuration whose limit is not monotone in the distance: every pair is evaluated)
-    for (int j = tid; j < a.n_rob; j += NT) {
+    for (int j = g_lo + tid; j < g_hi; j += NT) {
       if (j == self || !a.has_plan[j]) continue;
       const double* rec = a.plans + (int64_t)j * (N + 1) * 9;
       for (int i = 0; i <= N; ++i) {
@@ -331,7 +338,7 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
                           const double* vel_cap, const double* plans_all, const uint8_t* has_plan,
                           double* ref_full, double* ref, double* path_vel, void* hip_stream) {
   Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (int rc = check_neighbours(h, n_inst, n_rob)) return rc;
   if (n_inst == 0) return HDSM_OK;
   if (!cfg || !agent_id || !path || !n_path || !plans_all || !has_plan || !ref_full || !path_vel || pmax < 1)
     return set_err(HDSM_ERR_BAD_ARG, "null or empty argument");
@@ -341,7 +348,7 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
   a.agent_id = agent_id, a.path = path, a.n_path = n_path, a.vel_cap = vel_cap, a.plans = plans_all;
   a.has_plan = has_plan, a.ref_full = ref_full, a.ref = ref, a.path_vel = path_vel;
   hdsm_handle::Prepass& pp = h->pre;
-  a.rpos = pp.d_rpos.get(), a.rsph = pp.d_rsph.get();
+  a.rpos = pp.d_rpos.get(), a.rsph = pp.d_rsph.get(), a.range = h->range();
   for (int i = 0; i <= hdsm::MAXH; ++i) {
     double occ = 100 * std::pow(cfg->sens_other_agents, (double)i);  // AC:1791-1795
     occ = occ < 0 ? 0 : (occ > 100 ? 100 : occ);
@@ -355,7 +362,7 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
     // device-resident loop (defer_done: one stream, the solve of this round follows on the same plans): the pre-pass rides along
     const bool with_pre = h->defer_done;
     const bool ordered = with_pre && h->prm.warm_start && h->order_min > 0 && n_inst >= h->order_min;
-    const bool pre = n_rob >= h->bounds_min;
+    const bool pre = h->prefilter_agents(n_rob) >= h->bounds_min;
     hipLaunchKernelGGL(k_ref_pack, dim3((n_rob + 15) / 16 + (ordered ? 1 : 0)), dim3(256), 0, st, h->N, n_rob, plans_all, has_plan, pp.d_rpos.get(), pp.d_rsph.get(),
                        with_pre ? pp.d_pos.get() : nullptr, with_pre && pre ? pp.d_bounds.get() : nullptr, n_inst, h->d_stats.get() + 7 * h->max_inst, agent_id,
                        ordered ? pp.d_order.get() : nullptr);
@@ -373,7 +380,7 @@ int hdsm_reference(void* handle, const hdsm_ref_config* cfg, int32_t n_inst, int
                    const double* path, const int32_t* n_path, int32_t pmax, const double* vel_cap,
                    const double* plans_all, const uint8_t* has_plan, double* ref_full, double* ref, double* path_vel) {
   Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (int rc = check_neighbours(h, n_inst, n_rob)) return rc;
   if (n_inst == 0) return HDSM_OK;
   if (!cfg || !agent_id || !path || !n_path || !plans_all || !has_plan || !ref_full || !path_vel || pmax < 1)
     return set_err(HDSM_ERR_BAD_ARG, "null or empty argument");

@@ -149,7 +149,7 @@ int hdsm_replan(void* handle, int32_t n_inst, int32_t n_rob, const int32_t* agen
                 const double* plans_all, const uint8_t* has_plan, double* traj_out, double* ctrl_out,
                 uint8_t* poly_used, int32_t* status, double* obj) {
   Handle* h = static_cast<Handle*>(handle);
-  if (int rc = check_common(h, n_inst, n_rob)) return rc;
+  if (int rc = check_neighbours(h, n_inst, n_rob)) return rc;
   if (n_inst == 0) return HDSM_OK;
   if (!agent_id || !state_curr || !traj_ref || !n_poly || !n_rows_static || !A_static || !b_static ||
       !plans_all || !has_plan || !traj_out || !ctrl_out || !poly_used || !status || !obj)

@@ -85,6 +85,11 @@ struct Swarm {
   double sep_warn = 1.0;
   std::vector<hdsm_flight_report> flight;
   std::vector<hdsm_audit_round> audit_last;
+  // neighbour groups (hdsm_swarm_set_groups): the partition as given (empty: none) and the id range per agent, [n_rob][2]
+  std::vector<int32_t> group_start, range;
+  void neighbour_range(int id, int* lo, int* hi) const {
+    *lo = range.empty() ? 0 : range[2 * (size_t)id], *hi = range.empty() ? n_rob : range[2 * (size_t)id + 1];
+  }
   ~Swarm() {
     for (AgentX& a : extra) hdsm_stats_destroy(a.stats);
   }
@@ -111,10 +116,12 @@ double compute_path_velocity(const Swarm& sw, const AgentS& ag, const std::vecto
   // voxel / potential-field term (AC:1709-1766) on the agent's local grid, then the neighbour term (AC:1769-1801)
   const hdsm_sw::Cfg cc = sw.core_cfg();
   double path_vel = hdsm_sw::voxel_velocity_cap(cc, ref_config(sw), hdsm_sw::local_grid_origin(cc, ag), path.data(), (int)path.size());
+  int g_lo, g_hi;  // the agent's neighbours: its group (everybody without a partition)
+  sw.neighbour_range(ag.id, &g_lo, &g_hi);
   for (int i = 0; i < (ag.has_traj ? N + 1 : 0); ++i) {
     const V3 start = {{ag.traj_curr[i][0], ag.traj_curr[i][1], ag.traj_curr[i][2]}};
     const double occ = 100 * std::pow(sw.cfg.sens_other_agents, (double)i);
-    for (int j = 0; j < sw.n_rob; ++j) {
+    for (int j = g_lo; j < g_hi; ++j) {
       if (j == ag.id || !has_plan[j]) continue;
       const double* st = plans_all + ((size_t)j * (N + 1) + i) * 9;
       const double d = norm(sub(start, V3{{st[0], st[1], st[2]}}));
@@ -770,13 +777,41 @@ int hdsm_swarm_audit(void* swarm, const double* plans_all, const uint8_t* has_pl
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw || !plans_all || !has_plan || !sw->audit_on) return HDSM_ERR_BAD_ARG;
   sw->audit_last.resize((size_t)sw->n_local);
-  const int rc = hdsm_flight_audit_host(sw->n_rob, plans_all, has_plan, sw->prm.n_hor, sw->cfg.step_plan, sw->first_id, sw->n_local,
-                                        sw->prm.drone_radius, sw->prm.drone_z_offset, sw->has_world ? sw->world.data() : nullptr, sw->wdim,
-                                        sw->worigin, sw->cfg.voxel_size, sw->audit_last.data());
+  const int rc = hdsm_internal_audit_host_grouped(sw->n_rob, plans_all, has_plan, sw->prm.n_hor, sw->cfg.step_plan, sw->first_id, sw->n_local,
+                                                  sw->prm.drone_radius, sw->prm.drone_z_offset, sw->has_world ? sw->world.data() : nullptr, sw->wdim,
+                                                  sw->worigin, sw->cfg.voxel_size, sw->range.empty() ? nullptr : sw->range.data(),
+                                                  sw->audit_last.data());
   if (rc) return rc;
   const double warn2 = sw->sep_warn * sw->sep_warn;
   for (int k = 0; k < sw->n_local; ++k)
     if (has_plan[sw->first_id + k]) hdsm_audit::accumulate(&sw->flight[k], sw->audit_last[k], sw->cfg.step_plan, warn2);
+  return HDSM_OK;
+}
+
+// ---- neighbour groups of the host mirror (ABI 1.8; the definition: include/hdsm.h, hdsm_set_groups) ----
+int hdsm_swarm_set_groups(void* swarm, int32_t n_groups, const int32_t* group_start) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || n_groups < 0) return HDSM_ERR_BAD_ARG;
+  if (n_groups == 0 || !group_start) {
+    sw->group_start.clear(), sw->range.clear();
+    return HDSM_OK;
+  }
+  if (group_start[0] != 0 || group_start[n_groups] != sw->n_rob) return HDSM_ERR_BAD_ARG;
+  for (int g = 0; g < n_groups; ++g)
+    if (group_start[g + 1] <= group_start[g]) return HDSM_ERR_BAD_ARG;
+  sw->group_start.assign(group_start, group_start + n_groups + 1);
+  sw->range.assign((size_t)sw->n_rob * 2, 0);
+  for (int g = 0; g < n_groups; ++g)
+    for (int k = group_start[g]; k < group_start[g + 1]; ++k) sw->range[2 * (size_t)k] = group_start[g], sw->range[2 * (size_t)k + 1] = group_start[g + 1];
+  return HDSM_OK;
+}
+
+int hdsm_swarm_export_groups(void* swarm, int32_t* n_groups, int32_t* group_start) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !n_groups) return HDSM_ERR_BAD_ARG;
+  *n_groups = sw->group_start.empty() ? 0 : (int32_t)sw->group_start.size() - 1;
+  if (group_start)
+    for (size_t g = 0; g < sw->group_start.size(); ++g) group_start[g] = sw->group_start[g];
   return HDSM_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cstddef>
 #include <cstdlib>
 #include <memory>
@@ -648,6 +649,66 @@ struct WorldEdits {
   DevBuf<unsigned long long> d_dropped;
 };
 
+// ---- neighbour groups: the per-group flight summary (hdsm_dswarm_group_report) ----
+// One wavefront per group over the group's LOCAL agents [max(lo, first), min(hi, first + n_local)), 64 at a time; groups larger than
+// a wavefront loop. Every figure is an integer sum, a minimum or a maximum, reduced over the wave by butterflies: the result does not
+// depend on the order. The separation minimum orders (sep2_min, agent id) — a total order: ties go to the lower agent id. No atomics,
+// no LDS. report == nullptr (the audit was never on): the audit fields are zeros and -1. With the audit on, a group without a pair
+// (one agent) has sep2_min = DBL_MAX and sep_agent = -1, as in an empty hdsm_flight_report.
+template <class T>
+__device__ __forceinline__ T wave_xor(T v, int m) {
+  return __shfl_xor(v, m, 64);
+}
+__global__ __launch_bounds__(64) void k_group_report(int first, int n_local, const int32_t* __restrict__ gstart, const AgentS* __restrict__ agents,
+                                                     const int32_t* __restrict__ status, const hdsm_flight_report* __restrict__ report,
+                                                     hdsm_group_report* __restrict__ out) {
+  const int g = (int)blockIdx.x, lane = (int)threadIdx.x;
+  const int lo = gstart[g], hi = gstart[g + 1];
+  const int l0 = lo > first ? lo : first, l1 = hi < first + n_local ? hi : first + n_local;
+  long long no_sol = 0, failed = 0, rounds = 0, positions = 0, close_r = 0, occupied = 0, unknown = 0, crossed = 0, pot = 0;
+  double dist_goal = 0.0, speed_max = 0.0, q = DBL_MAX;
+  int q_agent = -1, q_partner = -1, q_sub = 0;
+  long long q_round = -1;
+  for (int a = l0 + lane; a < l1; a += 64) {
+    const int k = a - first;
+    const AgentS& ag = agents[k];
+    no_sol += status[k] == HDSM_NO_SOLUTION, failed += ag.n_fail;
+    const double dg = hdsm_sw::norm(hdsm_sw::sub(V3{{ag.state_curr[0], ag.state_curr[1], ag.state_curr[2]}}, ag.goal));
+    dist_goal = dg > dist_goal ? dg : dist_goal;
+    if (report != nullptr) {
+      const hdsm_flight_report r = report[k];
+      rounds = r.rounds > rounds ? r.rounds : rounds;
+      positions += r.positions, close_r += r.close_rounds, occupied += r.occupied, unknown += r.unknown, crossed += r.crossed, pot += r.pot_sum;
+      speed_max = r.speed_max > speed_max ? r.speed_max : speed_max;
+      if (r.sep_partner >= 0 && (q_agent < 0 || r.sep2_min < q))  // (ids ascend within a lane: '<' keeps the lower one)
+        q = r.sep2_min, q_agent = a, q_partner = r.sep_partner, q_sub = r.sep_substep, q_round = r.sep_round;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    no_sol += wave_xor(no_sol, m), failed += wave_xor(failed, m), positions += wave_xor(positions, m), close_r += wave_xor(close_r, m);
+    occupied += wave_xor(occupied, m), unknown += wave_xor(unknown, m), crossed += wave_xor(crossed, m), pot += wave_xor(pot, m);
+    const long long o_rounds = wave_xor(rounds, m);
+    rounds = o_rounds > rounds ? o_rounds : rounds;
+    const double o_dg = wave_xor(dist_goal, m), o_sp = wave_xor(speed_max, m);
+    dist_goal = o_dg > dist_goal ? o_dg : dist_goal, speed_max = o_sp > speed_max ? o_sp : speed_max;
+    const double o_q = wave_xor(q, m);
+    const int o_agent = wave_xor(q_agent, m), o_partner = wave_xor(q_partner, m), o_sub = wave_xor(q_sub, m);
+    const long long o_round = wave_xor(q_round, m);
+    if (o_agent >= 0 && (q_agent < 0 || o_q < q || (o_q == q && o_agent < q_agent)))
+      q = o_q, q_agent = o_agent, q_partner = o_partner, q_sub = o_sub, q_round = o_round;
+  }
+  if (lane == 0) {
+    hdsm_group_report r;
+    r.first = lo, r.count = hi - lo, r.n_local = l1 > l0 ? l1 - l0 : 0, r.no_solution_last = (int32_t)no_sol;
+    r.failed_total = failed, r.dist_goal_max = dist_goal;
+    r.rounds = rounds, r.positions = positions, r.close_rounds = close_r, r.occupied = occupied, r.unknown = unknown, r.crossed = crossed;
+    r.pot_sum = pot, r.sep2_min = report != nullptr ? q : 0.0, r.sep_agent = q_agent, r.sep_partner = q_partner, r.sep_substep = q_sub, r.reserved0 = 0;
+    r.sep_round = q_round, r.speed_max = speed_max;
+    out[g] = r;
+  }
+}
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -670,6 +731,12 @@ struct DSwarm {
   Audit audit;
   History hist;
   WorldEdits edits;
+  // neighbour groups (taken from the mirror by hdsm_dswarm_create; one group = the whole swarm without a partition): the
+  // partition, the id range per record of the plans buffer ([per * world][2], for the audit; null without a partition), the report
+  std::vector<int32_t> group_start;
+  bool grouped = false;
+  DevBuf<int32_t> d_gstart, d_range;
+  DevBuf<hdsm_group_report> d_greport;
 };
 
 // every event a timed round records (hdsm_dswarm_set_phase_timing; _set_audit and _set_history when the timing is already on)
@@ -808,6 +875,28 @@ int take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
   }
   if (hworld) HIP_TRY(hipMemcpy(d.d_world.get(), hworld, (size_t)d.c.wdim[0] * d.c.wdim[1] * d.c.wdim[2], hipMemcpyHostToDevice));
   d.c.world = d.d_world.get();
+  {  // the mirror's partition goes onto the solver handle (none: the handle's is cleared) and, for the audit, into a range table
+    int32_t ng = 0;
+    if (int rc = hdsm_swarm_export_groups(swarm, &ng, nullptr)) return refused(rc);
+    d.grouped = ng > 0;
+    d.group_start.assign((size_t)(d.grouped ? ng + 1 : 2), 0);
+    if (d.grouped) {
+      if (int rc = hdsm_swarm_export_groups(swarm, &ng, d.group_start.data())) return refused(rc);
+    } else {
+      d.group_start[1] = d.n_rob;
+    }
+    if (int rc = hdsm_set_groups(d.solver, d.grouped ? ng : 0, d.grouped ? d.group_start.data() : nullptr))
+      return fail(rc, std::string("hdsm_set_groups: ") + hdsm_last_error());
+    HIP_TRY(hipSetDevice(d.device));  // (the handle may live on another device)
+    if (d.grouped) {
+      const size_t G = (size_t)d.per * d.world;
+      std::vector<int32_t> table(2 * G + 2, 0);
+      for (int g = 0; g < ng; ++g)
+        for (int k = d.group_start[g]; k < d.group_start[g + 1]; ++k) table[2 * (size_t)k] = d.group_start[g], table[2 * (size_t)k + 1] = d.group_start[g + 1];
+      HIP_TRY(d.d_range.alloc(table.size()));
+      HIP_TRY(hipMemcpy(d.d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+  }
   int32_t on = 0, ever = 0;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
   if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, nullptr)) return refused(rc);
   if (ever) {
@@ -934,8 +1023,8 @@ int audit_and_history(DSwarm& d, hipStream_t st) {
     hdsm_audit::World wd{};
     wd.world = d.c.has_world ? d.d_world.get() : nullptr, wd.voxel_size = d.c.voxel_size;
     for (int k = 0; k < 3; ++k) wd.wdim[k] = d.c.wdim[k], wd.worigin[k] = d.c.worigin[k];
-    HIP_TRY(hdsm_audit::launch(a.buf, a.on, d.d_plans.get(), d.d_has.get(), d.c.N, d.first, hdsm_audit::weights(d.prm.drone_radius, d.prm.drone_z_offset),
-                               wd, a.d_report.get(), a.sep_warn * a.sep_warn, &d.d_agents.get()[0].state_curr[0], sizeof(AgentS),
+    HIP_TRY(hdsm_audit::launch(a.buf, a.on, d.d_plans.get(), d.d_has.get(), d.d_range.get(), d.c.N, d.first,
+                               hdsm_audit::weights(d.prm.drone_radius, d.prm.drone_z_offset), wd, a.d_report.get(), a.sep_warn * a.sep_warn, &d.d_agents.get()[0].state_curr[0], sizeof(AgentS),
                                hist ? h.d_rows.get() + (size_t)h.n * n * 9 : nullptr, st));
     if (d.phase_timing) HIP_TRY(a.timed.record_stop(st));
     if (a.on) ++a.rounds;
@@ -949,6 +1038,26 @@ int audit_and_history(DSwarm& d, hipStream_t st) {
 extern "C" {
 
 const char* hdsm_dswarm_last_error(void) { return g_err.c_str(); }
+
+// The flight per group (one record for the whole swarm without a partition): k_group_report over the agents' states, the last
+// statuses and — once the audit has been on — the flight records. Launched here and nowhere else: a round never pays for it.
+int hdsm_dswarm_group_report(void* dswarm, hdsm_group_report* out) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  const int ng = (int)d->group_start.size() - 1;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!d->d_gstart) {
+    HIP_TRY(d->d_gstart.alloc(d->group_start.size()));
+    HIP_TRY(hipMemcpy(d->d_gstart.get(), d->group_start.data(), d->group_start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(d->d_greport.alloc((size_t)ng));
+  }
+  hipLaunchKernelGGL(k_group_report, dim3((unsigned)ng), dim3(64), 0, nullptr, d->first, d->n_local, d->d_gstart.get(), d->d_agents.get(), d->d_status.get(),
+                     d->audit.ever ? d->audit.d_report.get() : nullptr, d->d_greport.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, d->d_greport.get(), (size_t)ng * sizeof(hdsm_group_report), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
 
 // Where a round of the device-resident loop goes, measured with HIP events on the round's own stream: the records sit between the
 // launches of hdsm_dswarm_round — [0] k_corridor, [1] k_vel_cap, [2] hdsm_reference_device (pack + reference), [3] k_keep_free,

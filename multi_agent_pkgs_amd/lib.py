@@ -33,7 +33,12 @@ AUDIT_ROUND = np.dtype([("sep2", "<f8"), ("partner", "<i4"), ("substep", "<i4"),
 FLIGHT_REPORT = np.dtype([("rounds", "<i8"), ("positions", "<i8"), ("sep2_min", "<f8"), ("sep_partner", "<i4"), ("sep_substep", "<i4"),
                           ("sep_round", "<i8"), ("close_rounds", "<i8"), ("occupied", "<i8"), ("unknown", "<i8"), ("crossed", "<i8"),
                           ("pot_sum", "<i8"), ("dist", "<f8"), ("speed_sum", "<f8"), ("speed_max", "<f8")])  # hdsm_flight_report
-assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104
+GROUP_REPORT = np.dtype([("first", "<i4"), ("count", "<i4"), ("n_local", "<i4"), ("no_solution_last", "<i4"), ("failed_total", "<i8"),
+                         ("dist_goal_max", "<f8"), ("rounds", "<i8"), ("positions", "<i8"), ("close_rounds", "<i8"), ("occupied", "<i8"),
+                         ("unknown", "<i8"), ("crossed", "<i8"), ("pot_sum", "<i8"), ("sep2_min", "<f8"), ("sep_agent", "<i4"),
+                         ("sep_partner", "<i4"), ("sep_substep", "<i4"), ("reserved0", "<i4"), ("sep_round", "<i8"),
+                         ("speed_max", "<f8")])                                                            # hdsm_group_report
+assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104 and GROUP_REPORT.itemsize == 128
 
 
 class HdsmError(RuntimeError):
@@ -67,7 +72,8 @@ CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "double": C.c_double, "size_t": 
           "void**": C.POINTER(C.c_void_p), "char*": C.c_char_p}
 CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32_t", np.int32), ("int8_t", np.int8), ("uint8_t", np.uint8),
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
-                                                  ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT))})
+                                                  ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
+                                                  ("hdsm_group_report", GROUP_REPORT))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
                                                   ("hdsm_swarm_config", SwarmConfig))})
 
@@ -276,6 +282,16 @@ class Solver:
         planes = np.zeros((n_inst, N, n_rob, 4))
         call("hdsm_tasc_planes", self.h, n_inst, n_rob, agent_id, state, plans, has_plan, planes)
         return planes
+
+    def set_groups(self, group_start=None):
+        """hdsm_set_groups: group_start [n_groups + 1] partitions the agent ids into contiguous ranges (0 first, strictly increasing,
+        the last entry = the number of agents); from then on an agent's neighbours are the agents of its own range, in replan*,
+        reference* and tasc_planes. None (or an empty list): one group, as without the call. Synchronises the handle."""
+        gs = _i32([] if group_start is None else group_start)
+        if gs.size < 2:
+            call("hdsm_set_groups", self.h, 0, None)
+        else:
+            call("hdsm_set_groups", self.h, gs.size - 1, gs)
 
     def reset_warm_start(self):
         call("hdsm_reset_warm_start", self.h)

@@ -39,6 +39,17 @@ def circle_scenario(n, radius=None, cx=18.0, cy=15.0, z=1.5):
     return starts, goals
 
 
+def repeat_scenario(starts, goals, copies, offset=(0.0, 0.0, 0.0)):
+    """`copies` copies of one scenario as neighbour groups of one flight (hdsm_set_groups / hdsm_swarm_set_groups): copy g holds
+    the ids [g n, (g + 1) n) and is shifted by g * offset — (0, 0, 0), the default, flies every copy at the same coordinates,
+    which only groups can do; a large offset is the tiling a flight without groups has to use.
+    Returns starts [copies n][3], goals [copies n][3], group_start int32 [copies + 1]."""
+    starts, goals = np.asarray(starts, dtype=np.float64), np.asarray(goals, dtype=np.float64)
+    n = starts.shape[0]
+    shift = np.repeat(np.arange(copies)[:, None] * np.asarray(offset, dtype=np.float64)[None, :], n, axis=0)
+    return np.tile(starts, (copies, 1)) + shift, np.tile(goals, (copies, 1)) + shift, (n * np.arange(copies + 1)).astype(np.int32)
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

@@ -16,7 +16,7 @@ import numpy as np
 from . import lib as _lib
 from .lib import _f64, _i8, _i32, _stream, _u8, call
 from .params import HdsmParams, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
-from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario  # noqa: F401  (scenario geometry lives in scenarios.py)
+from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario, repeat_scenario  # noqa: F401  (scenario geometry lives in scenarios.py)
 
 
 def default_swarm_config():
@@ -154,6 +154,17 @@ class SwarmShard:
         has_local = np.zeros(self.n_local, np.uint8)
         call("hdsm_swarm_commit", self.h, _f64(out["traj"]), _f64(out["ctrl"]), _u8(out["used"]), _i32(out["status"]), plans_local, has_local)
         return plans_local, has_local
+
+    def set_groups(self, group_start=None):
+        """hdsm_swarm_set_groups: group_start [n_groups + 1] partitions the ids [0, n_rob) into contiguous ranges; an agent's
+        neighbours are the agents of its own range (the host reference generation and the audit; a DeviceSwarm made from this shard
+        takes the partition over and sets it on its solver). None: one group."""
+        gs = _i32([] if group_start is None else group_start)
+        if gs.size < 2:
+            call("hdsm_swarm_set_groups", self.h, 0, None)
+        else:
+            call("hdsm_swarm_set_groups", self.h, gs.size - 1, gs)
+        self.group_start = None if gs.size < 2 else gs.copy()
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_swarm_set_audit: the flight audit of the host mirror (csrc/audit_core.h). The flight record starts when it is first
@@ -304,6 +315,8 @@ class DeviceSwarm:
         self.world_size = int(world_size)
         call("hdsm_dswarm_create", shard.h, solver.h, device, world_size, C.byref(self.h))
         self.per = (shard.n_rob + self.world_size - 1) // self.world_size
+        gs = getattr(shard, "group_start", None)
+        self.n_groups = 1 if gs is None else len(gs) - 1   # (the partition is taken from the shard when the dswarm is made)
 
     def upload_plans(self, plans_all, has_plan):
         call("hdsm_dswarm_upload_plans", self.h, _f64(plans_all), _u8(has_plan))
@@ -409,6 +422,13 @@ class DeviceSwarm:
         rep = np.zeros(self.shard.n_local, _lib.FLIGHT_REPORT)
         call("hdsm_dswarm_flight_report", self.h, rep)
         return rep
+
+    def group_report(self):
+        """hdsm_dswarm_group_report: the flight per group over the group's local agents (lib.GROUP_REPORT; one record for the whole
+        swarm without a partition) — last statuses, failures, distance to the goal and the fold of the flight records. Synchronises."""
+        out = np.zeros(self.n_groups, _lib.GROUP_REPORT)
+        call("hdsm_dswarm_group_report", self.h, out)
+        return out
 
     def last_audit_round(self):
         """hdsm_dswarm_last_audit_round: what the last round's audit found per local agent (lib.AUDIT_ROUND)."""

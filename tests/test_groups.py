@@ -1,0 +1,130 @@
+"""Neighbour groups on the host (ABI 1.8, include/hdsm.h hdsm_set_groups): the host mirror with a partition against separate
+mirrors of the groups, and the argument checks. The definition under test: every result for agent a is what the ungrouped code
+returns when has_plan is zeroed for every agent outside a's group — so the yardsticks are the ungrouped mirrors and the oracle
+with masked flags."""
+import numpy as np
+import pytest
+
+from multi_agent_pkgs_amd import lib, scenarios, swarm
+from multi_agent_pkgs_amd.params import agile_params
+
+GROUPS = np.array([0, 1, 3, 8, 16], dtype=np.int32)
+KEYS = ("state", "ref", "n_poly", "n_rows", "A", "b")
+
+
+def _masked(has, lo, hi):
+    m = np.zeros_like(has)
+    m[lo:hi] = has[lo:hi]
+    return m
+
+
+def solve_per_group(oracle, prm, inp, plans, has, groups):
+    """The specification as code: every group solved by the oracle with has_plan masked to the group."""
+    outs = []
+    for lo, hi in zip(groups[:-1], groups[1:]):
+        outs.append(oracle.replan(prm, *[inp[k][lo:hi] for k in ("agent_id",) + KEYS], plans, _masked(has, lo, hi), n_threads=8))
+    return {k: np.concatenate([o[k] for o in outs]) for k in ("traj", "ctrl", "used", "status", "obj")}
+
+
+def test_grouped_mirror_equals_separate_mirrors(oracle):
+    """16 agents of one circle exchange in the groups [0,1,3,8,16] against four mirrors of 1, 2, 5 and 8 agents with renumbered
+    ids: for 4 rounds the solver inputs are equal bit for bit, and so are the flight reports of the audit (partner ids shifted by
+    the group's start). The ungrouped mirror, fed the same plans, must give another reference for at least one agent: the
+    neighbour term binds."""
+    prm = agile_params(10, max_rows_static=18)
+    cfg = swarm.default_swarm_config()
+    n = int(GROUPS[-1])
+    starts, goals = scenarios.circle_scenario(n, radius=6.0)
+    big = swarm.SwarmShard(prm, cfg, n, 0, starts, goals)
+    big.set_groups(GROUPS)
+    plain = swarm.SwarmShard(prm, cfg, n, 0, starts, goals)
+    small = [swarm.SwarmShard(prm, cfg, int(hi - lo), 0, starts[lo:hi], goals[lo:hi]) for lo, hi in zip(GROUPS[:-1], GROUPS[1:])]
+    for s in [big] + small:
+        s.set_audit(True, 1.0)
+    N = prm.n_hor
+    plans, has = np.zeros((n, N + 1, 9)), np.zeros(n, np.uint8)
+    differs = False
+    for r in range(4):
+        inp = {k: v.copy() for k, v in big.prepare(plans, has).items()}
+        assert np.array_equal(inp["agent_id"], np.arange(n))
+        for s, lo, hi in zip(small, GROUPS[:-1], GROUPS[1:]):
+            got = s.prepare(plans[lo:hi], has[lo:hi])
+            assert np.array_equal(got["agent_id"], np.arange(hi - lo))
+            for k in KEYS:
+                assert got[k].tobytes() == inp[k][lo:hi].tobytes(), (r, int(lo), k)
+        differs |= bool((plain.prepare(plans, has)["ref"] != inp["ref"]).any())
+        out = solve_per_group(oracle, prm, inp, plans, has, GROUPS)
+        plans, has = big.commit(out)
+        plain.commit(out)
+        for s, lo, hi in zip(small, GROUPS[:-1], GROUPS[1:]):
+            pl, hl = s.commit({k: v[lo:hi] for k, v in out.items()})
+            assert pl.tobytes() == plans[lo:hi].tobytes() and np.array_equal(hl, has[lo:hi])
+        big.audit(plans, has)
+        for s, lo, hi in zip(small, GROUPS[:-1], GROUPS[1:]):
+            s.audit(plans[lo:hi], has[lo:hi])
+    assert differs and has.all()
+    rep = big.flight_report()
+    assert (rep["rounds"] == 4).all()
+    for s, lo, hi in zip(small, GROUPS[:-1], GROUPS[1:]):
+        want = s.flight_report()
+        want["sep_partner"][want["sep_partner"] >= 0] += lo
+        assert rep[lo:hi].tobytes() == want.tobytes(), int(lo)
+    assert rep["sep_partner"][0] == -1 and (rep["sep_partner"][1:] >= 0).all()     # a group of one has no partner
+    for lo, hi in zip(GROUPS[:-1], GROUPS[1:]):
+        p = rep["sep_partner"][lo:hi]
+        assert ((p >= lo) & (p < hi) | (p < 0)).all()
+    # one group covering everything, and no partition, are the ungrouped mirror
+    whole = swarm.SwarmShard(prm, cfg, n, 0, starts, goals)
+    whole.set_groups([0, n])
+    ref = swarm.SwarmShard(prm, cfg, n, 0, starts, goals)
+    cleared = swarm.SwarmShard(prm, cfg, n, 0, starts, goals)
+    cleared.set_groups(GROUPS)
+    cleared.set_groups(None)
+    want = ref.prepare(plans, has)
+    for s in (whole, cleared):
+        got = s.prepare(plans, has)
+        for k in KEYS:
+            assert got[k].tobytes() == want[k].tobytes(), k
+
+
+@pytest.mark.parametrize("bad", [[1, 3, 8, 16], [0, 3, 3, 16], [0, 8, 3, 16], [0, 3, 8, 15], [0, 3, 8, 17]],
+                         ids=["first-not-zero", "repeated", "decreasing", "total-short", "total-long"])
+def test_swarm_set_groups_refuses_what_is_not_a_partition(bad):
+    prm = agile_params(10, max_rows_static=18)
+    starts, goals = scenarios.circle_scenario(16)
+    shard = swarm.SwarmShard(prm, swarm.default_swarm_config(), 16, 0, starts, goals)
+    with pytest.raises(lib.HdsmError) as e:
+        shard.set_groups(bad)
+    assert e.value.code == lib.HDSM_ERR_BAD_ARG
+    shard.set_groups([0, 3, 8, 16])       # ... and a partition is taken
+
+
+def test_repeat_scenario_returns_the_partition():
+    starts, goals = scenarios.circle_scenario(6, radius=4.0)
+    s, g, gs = scenarios.repeat_scenario(starts, goals, 4)
+    assert s.shape == (24, 3) and gs.tolist() == [0, 6, 12, 18, 24]
+    assert all(np.array_equal(s[6 * k:6 * k + 6], starts) and np.array_equal(g[6 * k:6 * k + 6], goals) for k in range(4))
+    s, g, gs = scenarios.repeat_scenario(starts, goals, 3, offset=(1000.0, 0.0, 0.0))
+    assert np.allclose(s[12:] - starts, [2000.0, 0, 0]) and np.allclose(g[6:12] - goals, [1000.0, 0, 0])
+
+
+def test_touched_and_new_kernels_use_no_scratch(tmp_path):
+    """The kernels the groups touch or add, read from the code objects of the built library: no private segment and no spill in
+    k_group_report (new), k_audit, k_reference and k_tasc_planes (the k_replan* shapes: tests/test_kernel_resources.py), and no
+    LDS in k_group_report."""
+    import os
+
+    from test_flight_audit import _group_segments
+    from test_kernel_resources import LIB, _kernel_descriptors
+    assert os.path.exists(LIB), "libhdsm.so is not built"
+    desc = _kernel_descriptors(tmp_path)
+    lds = _group_segments(tmp_path)
+    seen = set()
+    for k, v in desc.items():
+        for name in ("k_group_report", "k_auditE", "k_reference", "k_tasc_planes"):
+            if name in k:
+                seen.add(name)
+                assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
+                assert name != "k_group_report" or lds[k] == 0, (k, v, lds[k])
+                print(k, dict(v, group_segment_fixed_size=lds[k]))
+    assert seen == {"k_group_report", "k_auditE", "k_reference", "k_tasc_planes"}, seen
