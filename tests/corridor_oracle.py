@@ -97,12 +97,19 @@ DECOMP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c
                         C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32))
 
 
+REFUSALS = []   # why the decomposition callback refused, in call order (the callers clear it)
+
+
 def _decomp(ctx, seed, grid, dim, n_it, vs, mark, origin, use_new, rows, max_rows, n_rows):
     L = hdsm.load()
     fn = L.hdsm_poly_octa3d_new if use_new else L.hdsm_poly_octa3d
     if any(seed[k] < 0 or seed[k] >= dim[k] for k in range(3)):
+        REFUSALS.append("seed_outside")
         return -1   # (a seed outside the grid: the reference would index out of bounds; the product stops the agent's corridor)
-    return fn(seed, grid, dim, C.c_int32(n_it), C.c_double(vs), C.c_int32(mark), origin, rows, C.c_int32(max_rows), n_rows)
+    rc = fn(seed, grid, dim, C.c_int32(n_it), C.c_double(vs), C.c_int32(mark), origin, rows, C.c_int32(max_rows), n_rows)
+    if rc != 0:   # more rows than the caller takes (n_rows = the count needed), or a growth beyond the fixed workspace (n_rows = 0)
+        REFUSALS.append("rows" if n_rows[0] > max_rows else "workspace")
+    return rc
 
 
 _decomp_cb = DECOMP_FN(_decomp)

@@ -154,7 +154,7 @@ def dijkstra(T, c, gv):
 
 def shorten_dmp_path(pts, origin, vs, val, ldim):
     """ShortenDMPPath (path_tools.cpp:250-312) statement by statement on [(global point)]; val(i, j, k) the grid it sees."""
-    from test_host import _py_raycast
+    from refmath import py_raycast as _py_raycast
     inside = lambda i, j, k: 0 <= i < ldim[0] and 0 <= j < ldim[1] and 0 <= k < ldim[2]
 
     def get_voxel_int(p):  # GetVoxelInt(Vector3d): truncation, -1 outside

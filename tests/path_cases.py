@@ -99,7 +99,7 @@ def _dilate6(a):
 
 def plan(world, off, gk, origin, start, goal, vs=VS, ldim=LDIM):
     """Steps 1-7 of csrc/path_core.h. Returns (status, [points])."""
-    from test_host import _py_raycast
+    from refmath import py_raycast as _py_raycast
     start, goal = [float(x) for x in start], [float(x) for x in goal]
     if world is None:
         return 0, [start, goal]

@@ -6,6 +6,8 @@ variables/bounds/dynamics of Agent::CreateGurobiModel (agent_class.cpp:2071-2167
 rows of Agent::SolveOptimizationProblem (agent_class.cpp:858-1023) — and checks a candidate solution with
 solver-independent KKT certificates (stationarity via non-negative least squares on the active rows).
 """
+import math
+
 import numpy as np
 from scipy.optimize import nnls
 
@@ -194,3 +196,218 @@ def tasc_plane_algebraic(prm, c, o):
     c2 = np.array([-nh[2], 0.0, nh[0]])
     nf = prm.plane_perturb * (c1 + c2) + prm.plane_perturb * c2 + nh
     return np.array([nf[0], nf[1], nf[2], nf @ q])
+
+
+# ---- the map-dependent half of the reference trajectory and the commit bookkeeping, statement by statement from the reference ----
+# (AC = multi_agent_planner/src/agent_class.cpp.) Plain Python floats (IEEE double, one rounding per operation, no contraction):
+# the same number format as the reference, written from its text and not from csrc/swarm_core.h.
+
+
+def py_raycast(val, dim, start, end, max_dist):
+    """voxel_grid_util::Raycast (raycast.cpp:22-183) statement by statement; val(i,j,k) raw voxel, -1 outside."""
+    mod = lambda v, m: math.fmod(math.fmod(v, m) + m, m)
+
+    def intbound(s, ds):
+        if ds < 0:
+            return intbound(-s, -ds)
+        s = mod(s, 1)
+        return (1 - s) / ds if ds != 0 else math.inf
+
+    sg = lambda x: 0 if x == 0 else (-1 if x < 0 else 1)
+    x, y, z = (int(math.floor(c)) for c in start)
+    ex, ey, ez = (int(math.floor(c)) for c in end)
+    d = [end[k] - start[k] for k in range(3)]
+    st = [sg(ex - x), sg(ey - y), sg(ez - z)]
+    tm = [intbound(start[k], d[k]) for k in range(3)]
+    td = [(st[k] / d[k]) if d[k] != 0 else math.nan for k in range(3)]
+    out, hit = [], None
+    if st == [0, 0, 0]:
+        return [list(end), list(start)], None
+    tmax = 0.0
+    inside = lambda i, j, k: 0 <= i < dim[0] and 0 <= j < dim[1] and 0 <= k < dim[2]
+    while True:
+        real = [start[k] + min(1.0, tmax) * d[k] for k in range(3)]
+        if inside(x, y, z):
+            if val(x, y, z) == 100 and tmax <= 1:
+                hit = real
+                out.append(real)
+                break
+            out.append(real)
+            if (x - start[0]) ** 2 + (y - start[1]) ** 2 + (z - start[2]) ** 2 > max_dist ** 2:
+                break
+        if tmax >= 1:
+            break
+        if (tm[0] < tm[1] and st[0] != 0) or st[1] == 0:
+            ax = 0 if ((tm[0] < tm[2] and st[0] != 0) or st[2] == 0) else 2
+        else:
+            ax = 1 if ((tm[1] < tm[2] and st[1] != 0) or st[2] == 0) else 2
+        tmax = tm[ax]
+        if ax == 0:
+            x += st[0]
+        elif ax == 1:
+            y += st[1]
+        else:
+            z += st[2]
+        tm[ax] += td[ax]
+    return out, hit
+
+
+def velocity_limit(vmin, vmax, sens_pot, sens_dist, occ, dist):
+    """Agent::GetVelocityLimit, AC:1805-1817."""
+    return vmin + (vmax - vmin) * (1 - (min(max(occ, 0), 100) / 100) ** sens_pot * (1 / math.exp(sens_dist * dist)))
+
+
+def local_grid_origin(pos, grid_range, vs):
+    """environment_builder.cpp:58-67: origin = floor((position - range / 2) / voxel) * voxel."""
+    return np.array([math.floor((pos[k] - grid_range[k] / 2) / vs) * vs for k in range(3)])
+
+
+def window_value(world, worigin, grid_origin, dim, z_min, vs):
+    """val(i, j, k) of an agent's local grid cut out of the world [wz][wy][wx]: -1 outside the grid and below the ground,
+    0 outside the world, else the world's raw value."""
+    off = [int(round((grid_origin[k] - worigin[k]) / vs)) for k in range(3)]
+    gk = int(math.ceil((z_min - grid_origin[2]) / vs - 1e-9))
+    wz, wy, wx = world.shape
+
+    def val(i, j, k):
+        if not (0 <= i < dim[0] and 0 <= j < dim[1] and 0 <= k < dim[2]):
+            return -1
+        if k < gk:
+            return -1
+        g = (i + off[0], j + off[1], k + off[2])
+        if not (0 <= g[0] < wx and 0 <= g[1] < wy and 0 <= g[2] < wz):
+            return 0
+        return int(world[g[2], g[1], g[0]])
+
+    return val
+
+
+def path_velocity_cap(val, dim, grid_origin, vs, pts, vmin, vmax, sens_pot, sens_dist):
+    """The voxel term of Agent::ComputePathVelocity (AC:1695-1767) over the polyline pts (world metres, pts[0] = path start):
+    segment by segment, the visited voxels of a clear segment (the distance between path_start in WORLD metres and the visited
+    point in LOCAL voxel units, times the voxel size, AC:1735), the collision point of the first segment that is not clear
+    (distance in voxel units, AC:1755), then stop. Returns (cap, segs): segs[i] = (limit of segment i, collided) for EVERY segment
+    of the polyline — the ones behind the first collision too, which the reference never looks at and which do not enter the cap."""
+    pts = [np.asarray(p, dtype=np.float64) for p in pts]
+    cap, segs, stopped = vmax, [], False
+    for i in range(len(pts) - 1):
+        a = [float((pts[i][k] - grid_origin[k]) / vs) for k in range(3)]
+        b = [float((pts[i + 1][k] - grid_origin[k]) / vs) for k in range(3)]
+        md = math.sqrt(sum((a[k] - b[k]) ** 2 for k in range(3)))
+        visited, hit = py_raycast(val, dim, a, b, md)
+        v = vmax
+        if hit is None:
+            for pt in visited + [a]:
+                o = val(int(pt[0]), int(pt[1]), int(pt[2]))
+                o = 100 if o == -1 else o
+                v = min(v, velocity_limit(vmin, vmax, sens_pot, sens_dist, o, float(np.linalg.norm(pts[0] - np.array(pt))) * vs))
+        else:
+            v = min(v, velocity_limit(vmin, vmax, sens_pot, sens_dist, val(int(hit[0]), int(hit[1]), int(hit[2])),
+                                      float(np.linalg.norm(np.array(a) - np.array(hit)))))
+        segs.append((v, hit is not None))
+        if not stopped:
+            cap = min(cap, v)
+        stopped = stopped or hit is not None   # AC:1765: the loop ends here; what follows is looked at for the caller's statistics only
+    return cap, segs
+
+
+def keep_only_free(pts, val, grid_origin, vs):
+    """Agent::KeepOnlyFreeReference (AC:1665-1693) on the positions pts [n][3]: from the first point (after point 0) in an unknown
+    (-1) or occupied (100) voxel on, the last free point is repeated. GetVoxelGlobal truncates (p - origin) / voxel.
+    Returns (points, stop): stop = index of that first point, n if there is none."""
+    pts = np.array(pts, dtype=np.float64)
+    for i in range(1, len(pts)):
+        c = ((pts[i] - grid_origin) / vs).astype(int)
+        if val(int(c[0]), int(c[1]), int(c[2])) in (-1, 100):
+            pts[i:] = pts[i - 1]
+            return pts, i
+    return pts, len(pts)
+
+
+def reference_velocities(pts, path_vel):
+    """The velocity references of AC:1527-1547 on the final reference positions: path_vel * (p_i - p_{i+1}) / dist where the
+    two points are more than 1e-2 apart, else 0; the last point repeats the one before it."""
+    n = len(pts)
+    out = np.zeros((n, 3))
+    v = [0.0, 0.0, 0.0]
+    for i in range(n - 1):
+        dist = math.sqrt(sum((float(pts[i][k]) - float(pts[i + 1][k])) ** 2 for k in range(3)))
+        v = [path_vel * (float(pts[i][k]) - float(pts[i + 1][k])) / dist if dist > 1e-2 else 0.0 for k in range(3)]
+        out[i] = v
+    out[n - 1] = v
+    return out
+
+
+def path_progress(point, path):
+    """path_finding_util::GetPathProgress (path_tools.cpp:419-479), the literal walk in steps of 0.01: returns (progress_final,
+    proj_dist, d0) — d0 the distance of `point` to path[0], proj_dist the smallest distance over the samples (d0 if no sample is
+    strictly closer)."""
+    if len(path) <= 1:
+        return 1.0, 0.0, 0.0
+    p = [float(point[k]) for k in range(3)]
+    path = [[float(q[k]) for k in range(3)] for q in path]
+    norm = lambda v: math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    curr = list(path[0])
+    dist_min = norm([p[k] - curr[k] for k in range(3)])
+    d0 = proj_dist = dist_min
+    idx, progress, progress_final = 1, 0.0, 0.0
+    samp = 0.01
+    while idx < len(path):
+        nxt = path[idx]
+        diff = [nxt[k] - curr[k] for k in range(3)]
+        dist_next = norm(diff)
+        if dist_next > samp:
+            curr = [curr[k] + samp * diff[k] / dist_next for k in range(3)]
+            progress = progress + samp
+        else:
+            curr = list(nxt)
+            idx += 1
+            progress = progress + dist_next
+        d = norm([p[k] - curr[k] for k in range(3)])
+        if d < dist_min:
+            proj_dist = dist_min = d
+            progress_final = progress
+    return progress_final, proj_dist, d0
+
+
+def reference_increment(traj_1, traj_ref, thresh_dist):
+    """Agent::CheckReferenceTrajIncrement (AC:569-585): (increment, proj_dist, d0) for traj_curr_[1] and traj_ref_curr_."""
+    progress, proj_dist, d0 = path_progress(traj_1, traj_ref)
+    return (1 if (progress > 0 and proj_dist < thresh_dist) else 0), proj_dist, d0
+
+
+def walk_minimum(point, path):
+    """The smallest distance between `point` and the samples of the walk of path_progress AFTER the starting point (the quantity
+    the increment decision compares with d0 and thresh_dist)."""
+    p = [float(point[k]) for k in range(3)]
+    path = [[float(q[k]) for k in range(3)] for q in path]
+    norm = lambda v: math.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    curr, idx, best = list(path[0]), 1, math.inf
+    while idx < len(path):
+        nxt = path[idx]
+        diff = [nxt[k] - curr[k] for k in range(3)]
+        dist_next = norm(diff)
+        if dist_next > 0.01:
+            curr = [curr[k] + 0.01 * diff[k] / dist_next for k in range(3)]
+        else:
+            curr = list(nxt)
+            idx += 1
+        best = min(best, norm([p[k] - curr[k] for k in range(3)]))
+    return best
+
+
+def read_back(traj_prev, ctrl_prev, used_prev, traj_new, ctrl_new, used_new, failed):
+    """What SolveOptimizationProblem leaves in traj_curr_ / control_curr_ / poly_used_idx_ (AC:955-1019). traj_prev / ctrl_prev:
+    the previous plan ([N+1][9], [N][3]) or None when traj_curr_ is empty. A solve that succeeded stores its result; one that
+    failed drops the first state and control of the previous plan and duplicates the last ones — nothing changes without a
+    previous plan, and poly_used_idx_ stays what it was either way. Returns (traj, ctrl, used), traj None = still empty."""
+    if not failed:
+        return np.array(traj_new, dtype=np.float64), np.array(ctrl_new, dtype=np.float64), np.array(used_new, dtype=np.uint8)
+    if traj_prev is None:
+        return None, None, np.array(used_prev, dtype=np.uint8)
+    traj, ctrl = [list(r) for r in np.asarray(traj_prev)], [list(r) for r in np.asarray(ctrl_prev)]
+    traj.pop(0)                    # AC:1006-1007
+    ctrl.pop(0)
+    traj.append(list(traj[-1]))    # AC:1010-1013
+    ctrl.append(list(ctrl[-1]))
+    return np.array(traj, dtype=np.float64), np.array(ctrl, dtype=np.float64), np.array(used_prev, dtype=np.uint8)

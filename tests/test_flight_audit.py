@@ -12,7 +12,7 @@ import dmp_cases as dc
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import agile_params
-from test_host import _py_raycast
+from refmath import py_raycast as _py_raycast
 
 DBL_MAX = np.finfo(np.float64).max
 SEP_RTOL = 1e-12      # sep2 against numpy: the two evaluate the same closed form in a different order of operations

@@ -9,6 +9,7 @@ import pytest
 
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd.params import HdsmParams, agile_params
+from refmath import keep_only_free, py_raycast, velocity_limit, window_value   # the statement-by-statement renderings of the reference
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -366,56 +367,6 @@ def test_swarm_keeps_the_planner_records(oracle, tmp_path):
 
 
 # ---- row f1, map-dependent half: ComputePathVelocity's voxel term and KeepOnlyFreeReference on the host mirror --------
-def _py_raycast(val, dim, start, end, max_dist):
-    """voxel_grid_util::Raycast (raycast.cpp:22-183) statement by statement; val(i,j,k) raw voxel, -1 outside."""
-    import math
-    mod = lambda v, m: math.fmod(math.fmod(v, m) + m, m)
-
-    def intbound(s, ds):
-        if ds < 0:
-            return intbound(-s, -ds)
-        s = mod(s, 1)
-        return (1 - s) / ds if ds != 0 else math.inf
-
-    sg = lambda x: 0 if x == 0 else (-1 if x < 0 else 1)
-    x, y, z = (int(math.floor(c)) for c in start)
-    ex, ey, ez = (int(math.floor(c)) for c in end)
-    d = [end[k] - start[k] for k in range(3)]
-    st = [sg(ex - x), sg(ey - y), sg(ez - z)]
-    tm = [intbound(start[k], d[k]) for k in range(3)]
-    td = [(st[k] / d[k]) if d[k] != 0 else math.nan for k in range(3)]
-    out, hit = [], None
-    if st == [0, 0, 0]:
-        return [list(end), list(start)], None
-    tmax = 0.0
-    inside = lambda i, j, k: 0 <= i < dim[0] and 0 <= j < dim[1] and 0 <= k < dim[2]
-    while True:
-        real = [start[k] + min(1.0, tmax) * d[k] for k in range(3)]
-        if inside(x, y, z):
-            if val(x, y, z) == 100 and tmax <= 1:
-                hit = real
-                out.append(real)
-                break
-            out.append(real)
-            if (x - start[0]) ** 2 + (y - start[1]) ** 2 + (z - start[2]) ** 2 > max_dist ** 2:
-                break
-        if tmax >= 1:
-            break
-        if (tm[0] < tm[1] and st[0] != 0) or st[1] == 0:
-            ax = 0 if ((tm[0] < tm[2] and st[0] != 0) or st[2] == 0) else 2
-        else:
-            ax = 1 if ((tm[1] < tm[2] and st[1] != 0) or st[2] == 0) else 2
-        tmax = tm[ax]
-        if ax == 0:
-            x += st[0]
-        elif ax == 1:
-            y += st[1]
-        else:
-            z += st[2]
-        tm[ax] += td[ax]
-    return out, hit
-
-
 def test_voxel_velocity_cap_and_keep_only_free_follow_the_reference_statements():
     """hdsm_swarm_vel_cap = the voxel term of Agent::ComputePathVelocity (AC:1709-1766) and hdsm_swarm_set_reference's
     KeepOnlyFreeReference (AC:1665-1693), against a statement-by-statement Python rendering of the reference (Raycast,
@@ -459,8 +410,8 @@ def test_voxel_velocity_cap_and_keep_only_free_follow_the_reference_statements()
             pts = [starts[k], goals[k]]
             loc = [(p - go) / vs for p in pts]
             want = vmax
-            visited, hit = _py_raycast(val, (66, 66, 20), list(loc[0]), list(loc[1]), float(np.linalg.norm(loc[0] - loc[1])))
-            lim = lambda o, d: vmin + (vmax - vmin) * (1 - (min(max(o, 0), 100) / 100) ** sp * (1 / math.exp(sd * d)))
+            visited, hit = py_raycast(val, (66, 66, 20), list(loc[0]), list(loc[1]), float(np.linalg.norm(loc[0] - loc[1])))
+            lim = lambda o, d: velocity_limit(vmin, vmax, sp, sd, o, d)
             if hit is None:
                 for pt in visited + [list(loc[0])]:
                     v = val(int(pt[0]), int(pt[1]), int(pt[2]))
@@ -480,16 +431,7 @@ def test_voxel_velocity_cap_and_keep_only_free_follow_the_reference_statements()
         got = sh.inp["ref"]
         for k in range(6):
             go = np.floor((starts[k] - np.array([10.0, 10.0, 3.0])) / vs) * vs
-            pts = ref[k, :, :3].copy()
-            for i in range(1, 11):
-                c = ((pts[i] - go) / vs).astype(int)
-                g = c + np.round((go - origin) / vs).astype(int)
-                inside = (c >= 0).all() and c[0] < 66 and c[1] < 66 and c[2] < 20
-                v = -1 if (not inside or c[2] < int(math.ceil((0.0 - go[2]) / vs - 1e-9))) else (
-                    int(world[g[2], g[1], g[0]]) if (0 <= g[0] < 120 and 0 <= g[1] < 120 and 0 <= g[2] < 30) else 0)
-                if v in (-1, 100):
-                    pts[i:] = pts[i - 1]
-                    break
+            pts, _ = keep_only_free(ref[k, :, :3], window_value(world, origin, go, (66, 66, 20), 0.0, vs), go, vs)
             assert np.abs(got[k, :, :3] - pts[:10]).max() < 1e-12, (case, k)
     assert lowered > 10
 

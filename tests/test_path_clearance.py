@@ -84,7 +84,7 @@ def test_cost_is_the_optimum_over_the_tunnel_and_the_chain_has_less_potential():
 def test_segments_are_free_and_shortcuts_cross_no_potential():
     """Every returned segment is free of occupied voxels; every segment that is not a consecutive pair of the raw path visits only
     voxels with c = 0 (the points Raycast visits, as ShortenDMPPath reads them)."""
-    from test_host import _py_raycast
+    from refmath import py_raycast as _py_raycast
     shortcuts = 0
     for name, world, cs, args, (paths, n_path, status, cost, n_raw), plain, want in _results():
         for t in np.nonzero(status == 0)[0]:
