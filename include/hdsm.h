@@ -348,6 +348,15 @@ int hdsm_publish_device(void* handle, int32_t per, int32_t n_local, const double
                         double* plans_local, void* hip_stream);
 int hdsm_exchange_device(void* comm, int32_t per, const double* plans_local, double* plans_all, uint8_t* has_plan_all,
                          void* hip_stream);
+/* Local ranks (ABI 1.9): the `world` ranks of a sharded swarm held by ONE process, one per GPU or several on one GPU, without RCCL.
+ * handles[world] are solver handles, one per rank, each with its own device and all with the same n_hor; comms[world] receives one
+ * hdsm_comm per rank (hdsm_comm_info works on them; hdsm_comm_destroy of the last member frees what they share). Ranks on
+ * different devices need peer access in both directions (hipDeviceCanAccessPeer; HDSM_ERR_COMM names the pair that lacks it),
+ * which is then enabled; ranks on one device need nothing. The gather reads the other ranks' send buffers through plain pointers
+ * (k_gather_local), one code path for both cases. A rank cannot gather what the others have not yet been asked to publish, so
+ * hdsm_exchange_device and hdsm_dswarm_round refuse a local communicator (HDSM_ERR_BAD_ARG): all ranks of a round are flown by one
+ * call, hdsm_dswarm_round_ranks (hdsm_swarm.h). */
+int hdsm_comm_create_local(int32_t world, void* const* handles, void** comms);
 
 /* ---- neighbour groups (ABI 1.8): many independent swarms in one batch ------------------------------------------
  * A partition of the agent ids [0, n_total) into n_groups contiguous ranges: group_start[n_groups + 1] (host pointer, copied)
@@ -376,7 +385,8 @@ const char* hdsm_last_error(void);
  * (hdsm_map_region_extent / _region_scratch_bytes / hdsm_map_preprocess_region / _region_device here; hdsm_swarm_update_world,
  * hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats in
  * hdsm_swarm.h); 1.8: + neighbour groups (hdsm_set_groups here; hdsm_swarm_set_groups, hdsm_dswarm_group_report and
- * hdsm_group_report in hdsm_swarm.h); nothing removed or changed.   */
+ * hdsm_group_report in hdsm_swarm.h); 1.9: + local ranks (hdsm_comm_create_local here; hdsm_dswarm_round_ranks and
+ * hdsm_dswarm_download_raw in hdsm_swarm.h); nothing removed or changed.   */
 int32_t hdsm_version(void);
 
 #ifdef __cplusplus

@@ -398,6 +398,27 @@ typedef struct hdsm_group_report {
 int hdsm_swarm_set_groups(void* swarm, int32_t n_groups, const int32_t* group_start);
 int hdsm_dswarm_group_report(void* dswarm, hdsm_group_report* out);
 
+/* ---- local ranks (ABI 1.9): a sharded swarm flown by one process ------------------------------------------------------------------
+ *   hdsm_dswarm_round_ranks   one replan round of ALL `world` ranks of a local communicator group (hdsm_comm_create_local, hdsm.h):
+ *                             dswarms[r] is the shard of rank r of comms[r] (created with world_size = world), hip_streams[r] its
+ *                             stream (NULL entries, or a NULL array: the default stream). Asynchronous. First every rank's path step,
+ *                             corridor, reference, solve and k_commit (into its send buffer), then every rank's gather
+ *                             (k_gather_local: one launch that copies the `world` send buffers into the rank's plans buffer and sets
+ *                             the flags from the sentinel), audit and history. Ordered by events alone: a rank records "published"
+ *                             behind its k_commit and "gathered" behind its gather; a gather waits for every "published" of this
+ *                             round, a k_commit for every "gathered" of the round before (until then another rank may still be reading
+ *                             the send buffer). All ranks on one stream is legal. HDSM_ERR_BAD_ARG, before anything is launched, when
+ *                             the comms are not the ranks 0 .. world - 1 of ONE local group of exactly `world` ranks in that order, a
+ *                             dswarm appears twice, is not the block of its rank, is not on its communicator's device, or the shards
+ *                             disagree about n_rob or n_hor. A group of one rank is legal (it publishes through the send buffer too).
+ *                             hdsm_dswarm_last_phase_ms: [6] is the rank's gather; its wait for the other ranks is counted in [5].
+ *   hdsm_dswarm_download_raw  synchronises and copies out the plans buffer [world_size * per][N+1][9] AS IT IS — the sentinel of a slot
+ *                             without a plan (element 0 the quiet NaN 0x7ff8000000000000, zeros behind it) included, which
+ *                             hdsm_dswarm_download replaces by 0 — and the rank's send buffer [per][N+1][9] (all zeros on a single rank
+ *                             without a communicator, which publishes straight into the plans buffer). Either pointer may be NULL. */
+int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* comms, void* const* hip_streams);
+int hdsm_dswarm_download_raw(void* dswarm, double* plans_all_raw, double* send_raw);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

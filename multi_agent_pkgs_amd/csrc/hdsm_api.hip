@@ -551,7 +551,7 @@ int64_t scratch_stride_for(int n) {
 
 extern "C" {
 
-int32_t hdsm_version(void) { return (1 << 16) | 8; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister; 1.4: + the path step (hdsm_swarm_set_goals / _set_path_period / _replan_paths / _path_errors, hdsm_local_path_batch / _host, hdsm_dswarm_set_goals / _path_stats / _last_path_ms); 1.5: + the path step's clearance mode (hdsm_swarm_set_path_clearance, hdsm_local_path_dmp_batch / _host); 1.6: + the flight audit and the state history (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report / _last_audit_round / _last_audit_ms / _set_history / _download_history); 1.7: + map updates in flight (hdsm_map_region_extent / _region_scratch_bytes, hdsm_map_preprocess_region / _region_device, hdsm_swarm_update_world, hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats); 1.8: + neighbour groups (hdsm_set_groups, hdsm_swarm_set_groups, hdsm_dswarm_group_report)
+int32_t hdsm_version(void) { return (1 << 16) | 9; }  // 1.2: + hdsm_poly_octa3d_batch_wave / _device_wave, hdsm_set_kernel_timing / hdsm_last_kernel_ms; 1.3: + hdsm_host_register / _unregister; 1.4: + the path step (hdsm_swarm_set_goals / _set_path_period / _replan_paths / _path_errors, hdsm_local_path_batch / _host, hdsm_dswarm_set_goals / _path_stats / _last_path_ms); 1.5: + the path step's clearance mode (hdsm_swarm_set_path_clearance, hdsm_local_path_dmp_batch / _host); 1.6: + the flight audit and the state history (hdsm_flight_audit_host / _batch, hdsm_swarm_set_audit / _get_audit / _audit / _flight_report, hdsm_dswarm_set_audit / _flight_report / _last_audit_round / _last_audit_ms / _set_history / _download_history); 1.7: + map updates in flight (hdsm_map_region_extent / _region_scratch_bytes, hdsm_map_preprocess_region / _region_device, hdsm_swarm_update_world, hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats); 1.8: + neighbour groups (hdsm_set_groups, hdsm_swarm_set_groups, hdsm_dswarm_group_report); 1.9: + local ranks (hdsm_comm_create_local, hdsm_dswarm_round_ranks, hdsm_dswarm_download_raw)
 
 const char* hdsm_last_error(void) { return g_err.c_str(); }
 

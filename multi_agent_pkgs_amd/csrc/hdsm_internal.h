@@ -11,6 +11,24 @@ extern "C" {
 int hdsm_internal_defer_done(void* handle, int on);
 int hdsm_internal_record_done(void* handle, void* hip_stream);
 
+// (exchange_kernels.hip) local ranks, for hdsm_dswarm_round_ranks. They report through hdsm_last_error.
+// what hdsm_exchange_device and hdsm_dswarm_round answer to a local communicator
+#define HDSM_LOCAL_COMM_REFUSED "a local communicator gathers all its ranks in one call: use hdsm_dswarm_round_ranks"
+// -1 null, 0 RCCL, 1 local; device (may be NULL): the communicator's
+int hdsm_internal_comm_kind(void* comm, int32_t* device);
+// comms[world] are the ranks 0 .. world - 1, in that order, of ONE local group of exactly `world` ranks whose records hold rec doubles
+int hdsm_internal_local_check(int32_t world, void* const* comms, int32_t rec);
+// the send buffers [per][rec] of the ranks; the device tables are written (synchronously) only when one of them changed
+int hdsm_internal_local_bind(int32_t world, void* const* comms, const double* const* send, int32_t per);
+// before the rank's k_commit: its stream waits for every rank's "gathered" of the round before; after it: "published" is recorded
+int hdsm_internal_local_commit_gate(void* comm, void* hip_stream);
+int hdsm_internal_local_published(void* comm, void* hip_stream);
+// the rank's stream waits for every "published", `mark` (a hipEvent_t, may be NULL) is recorded, k_gather_local, "gathered" is recorded
+int hdsm_internal_local_gather(void* comm, double* plans_all, uint8_t* has_plan_all, void* hip_stream, void* mark);
+// k_gather_local alone (also called from the tests): d_send [world] device pointers to shards of per * rec doubles, 8-byte aligned
+int hdsm_internal_gather_local_launch(int32_t world, int32_t per, int32_t rec, const double* const* d_send, double* plans_all,
+                                      uint8_t* has_plan_all, void* hip_stream);
+
 // (swarm_host.cpp) the host mirror's flight in and out of the device-resident loop:
 // the plain agent states (hdsm_sw::AgentS [n_local]) and the configuration of a shard; every out argument may be NULL
 int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id, hdsm_params* prm,

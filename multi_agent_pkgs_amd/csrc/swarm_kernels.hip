@@ -7,7 +7,8 @@
 //   k_replan     planes + MIQP (the hot path)                                                   hdsm_replan_device
 //   k_commit     the new reference into the agent state, read-back, shift fallback, increment check, state advance, published
 //                record                                                                          one wavefront per agent
-//   exchange     ONE RCCL all-gather (hdsm_exchange_device), or a local copy on a single rank
+//   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
+//                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
 // tests/test_gpu_configs.py. AC = multi_agent_planner/src/agent_class.cpp of the reference.
 #include <hip/hip_runtime.h>
@@ -991,17 +992,35 @@ int corridor_to_solve(DSwarm& d, hipStream_t st) {
   return HDSM_OK;
 }
 
-// k_commit and the exchange (marks 5 to 7). One rank: the solve of this round is behind us on the stream, so the records go
-// straight into the plans buffer — slot k = agent k — and the flags with them; several ranks: into the send buffer of the ONE all-gather
-int commit_and_exchange(DSwarm& d, void* comm, hipStream_t st) {
+// k_commit (mark 5, and mark 6 unless the rank is a local one). One rank without a local communicator: the solve of this round is
+// behind us on the stream, so the records go straight into the plans buffer — slot k = agent k — and the flags with them; several
+// ranks, and every local rank (`local`: its communicator, else NULL): into the send buffer of the ONE all-gather. A local rank's
+// k_commit waits until every rank has gathered the round before — until then its send buffer may still be read — and is followed by
+// the rank's "published" event; its mark 6 stands in front of the gather (exchange).
+int commit(DSwarm& d, void* local, hipStream_t st) {
   PHASE_MARK(5);
-  const bool direct = d.world == 1;
+  const bool direct = d.world == 1 && local == nullptr;
+  if (local)
+    if (int rc = hdsm_internal_local_commit_gate(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
   hipLaunchKernelGGL(k_commit, dim3((unsigned)(d.per > 0 ? d.per : 1)), dim3(64), 0, st, d.c, d.n_local, d.per, d.d_agents.get(), d.d_traj.get(),
                      d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), direct ? d.d_plans.get() : d.d_local.get(), d.d_fails.get(),
                      direct ? d.d_has.get() : nullptr, d.d_ref_full.get(), d.d_pv.get());
   HIP_TRY(hipGetLastError());
-  PHASE_MARK(6);
-  if (!direct) {
+  if (local) {
+    if (int rc = hdsm_internal_local_published(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
+  } else {
+    PHASE_MARK(6);
+  }
+  return HDSM_OK;
+}
+
+// the exchange (up to mark 7): ONE RCCL all-gather, nothing on a single rank, or the gather of a local rank (k_gather_local: it waits
+// for every rank's "published", and mark 6 is recorded behind those waits, so that [6] of the phase timing is the gather itself)
+int exchange(DSwarm& d, void* comm, void* local, hipStream_t st) {
+  if (local) {
+    const int rc = hdsm_internal_local_gather(local, d.d_plans.get(), d.d_has.get(), st, d.phase_timing ? d.ev[6].get() : nullptr);
+    if (rc) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
+  } else if (d.world > 1) {
     const int rc = hdsm_exchange_device(comm, d.per, d.d_local.get(), d.d_plans.get(), d.d_has.get(), st);
     if (rc) return fail(rc, std::string("hdsm_exchange_device: ") + hdsm_last_error());
   }
@@ -1030,6 +1049,44 @@ int audit_and_history(DSwarm& d, hipStream_t st) {
     if (a.on) ++a.rounds;
   }
   if (hist) ++h.n;
+  return HDSM_OK;
+}
+
+// The round is issued on ONE stream and says so to the solver handle: the pre-pass of the solve then rides on the reference kernel
+// (hdsm_api.hip, `packed`). At its end it names the point a later call on another stream has to wait for; the handle records its
+// "done" event only when such a call arrives (hdsm_entry.h) — a record is a barrier packet, 5-6 us of idle queue in front of the next kernel.
+struct DoneOnce {
+  void* solver;
+  hipStream_t st;
+  DoneOnce(void* s, hipStream_t q) : solver(s), st(q) { (void)hdsm_internal_defer_done(solver, 1); }
+  ~DoneOnce() {
+    (void)hdsm_internal_defer_done(solver, 0);
+    (void)hdsm_internal_record_done(solver, st);
+  }
+};
+
+// The two halves of a round. hdsm_dswarm_round issues one behind the other; hdsm_dswarm_round_ranks the front of every rank, then the
+// back of every rank (no rank can gather what another has not been asked to publish). `local`: the rank's local communicator or NULL.
+int round_front(DSwarm& d, void* local, hipStream_t st) {
+  if (int rc = path_step(d, st)) return rc;
+  if (int rc = corridor_to_solve(d, st)) return rc;
+  return commit(d, local, st);
+}
+int round_back(DSwarm& d, void* comm, void* local, hipStream_t st) {
+  if (int rc = exchange(d, comm, local, st)) return rc;
+  if (int rc = audit_and_history(d, st)) return rc;
+  if (d.phase_timing) d.phase_valid = true;
+  ++d.rounds;
+  return HDSM_OK;
+}
+
+// the communicator must be the one this shard was cut for: its rank's block starts at first
+int check_comm(const DSwarm& d, void* comm) {
+  int32_t crank = -1, cworld = -1;
+  if (hdsm_comm_info(comm, &crank, &cworld) != HDSM_OK) return fail(HDSM_ERR_COMM, std::string("hdsm_comm_info: ") + hdsm_last_error());
+  const bool empty_tail = d.n_local == 0 && d.first == d.n_rob;  // (any rank behind the last agent)
+  if (cworld != d.world || (d.per > 0 && (empty_tail ? (int64_t)crank * d.per < d.n_rob : crank != d.first / d.per)))
+    return fail(HDSM_ERR_BAD_ARG, "communicator rank / size do not match the shard (first_id / per, world_size)");
   return HDSM_OK;
 }
 
@@ -1206,33 +1263,61 @@ int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   if (d->world > 1 && !comm) return fail(HDSM_ERR_BAD_ARG, "a sharded swarm needs a communicator");
-  if (comm) {  // the communicator must be the one this shard was cut for: its rank's block starts at first
-    int32_t crank = -1, cworld = -1;
-    if (hdsm_comm_info(comm, &crank, &cworld) != HDSM_OK) return fail(HDSM_ERR_COMM, std::string("hdsm_comm_info: ") + hdsm_last_error());
-    const bool empty_tail = d->n_local == 0 && d->first == d->n_rob;  // (any rank behind the last agent)
-    if (cworld != d->world || (d->per > 0 && (empty_tail ? (int64_t)crank * d->per < d->n_rob : crank != d->first / d->per)))
-      return fail(HDSM_ERR_BAD_ARG, "communicator rank / size do not match the shard (first_id / per, world_size)");
+  if (comm) {
+    if (hdsm_internal_comm_kind(comm, nullptr) == 1) return fail(HDSM_ERR_BAD_ARG, HDSM_LOCAL_COMM_REFUSED);
+    if (int rc = check_comm(*d, comm)) return rc;
   }
   HIP_TRY(hipSetDevice(d->device));
   hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  // The round is issued on ONE stream and says so to the solver handle: the pre-pass of the solve then rides on the reference kernel
-  // (hdsm_api.hip, `packed`). At its end it names the point a later call on another stream has to wait for; the handle records its
-  // "done" event only when such a call arrives (hdsm_entry.h) — a record is a barrier packet, 5-6 us of idle queue in front of the next kernel.
-  struct DoneOnce {
-    void* solver;
-    hipStream_t st;
-    DoneOnce(void* s, hipStream_t q) : solver(s), st(q) { (void)hdsm_internal_defer_done(solver, 1); }
-    ~DoneOnce() {
-      (void)hdsm_internal_defer_done(solver, 0);
-      (void)hdsm_internal_record_done(solver, st);
-    }
-  } done_once(d->solver, st);
-  if (int rc = path_step(*d, st)) return rc;
-  if (int rc = corridor_to_solve(*d, st)) return rc;
-  if (int rc = commit_and_exchange(*d, comm, st)) return rc;
-  if (int rc = audit_and_history(*d, st)) return rc;
-  if (d->phase_timing) d->phase_valid = true;
-  ++d->rounds;
+  DoneOnce done_once(d->solver, st);
+  if (int rc = round_front(*d, nullptr, st)) return rc;
+  return round_back(*d, comm, nullptr, st);
+}
+
+int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* comms, void* const* hip_streams) {
+  if (world < 1 || !dswarms || !comms) return fail(HDSM_ERR_BAD_ARG, "bad hdsm_dswarm_round_ranks argument");
+  for (int r = 0; r < world; ++r)
+    if (!dswarms[r] || !comms[r]) return fail(HDSM_ERR_BAD_ARG, "null dswarm or communicator of rank " + std::to_string(r));
+  const DSwarm* d0 = static_cast<const DSwarm*>(dswarms[0]);
+  if (int rc = hdsm_internal_local_check(world, comms, (d0->c.N + 1) * 9)) return fail(rc, std::string("hdsm_dswarm_round_ranks: ") + hdsm_last_error());
+  std::vector<const double*> send((size_t)world);
+  for (int r = 0; r < world; ++r) {
+    const DSwarm* d = static_cast<const DSwarm*>(dswarms[r]);
+    for (int q = 0; q < r; ++q)
+      if (dswarms[q] == dswarms[r]) return fail(HDSM_ERR_BAD_ARG, "the dswarm of rank " + std::to_string(q) + " is given again for rank " + std::to_string(r));
+    // (the gather of every rank copies per * rec doubles out of every send buffer: one n_rob, one n_hor)
+    if (d->n_rob != d0->n_rob || d->c.N != d0->c.N) return fail(HDSM_ERR_BAD_ARG, "the shards of ranks 0 and " + std::to_string(r) + " differ in n_rob or n_hor");
+    if (int rc = check_comm(*d, comms[r])) return rc;
+    int32_t cdev = -1;
+    (void)hdsm_internal_comm_kind(comms[r], &cdev);
+    if (cdev != d->device) return fail(HDSM_ERR_BAD_ARG, "the dswarm of rank " + std::to_string(r) + " is not on the device of its communicator's handle");
+    send[(size_t)r] = d->d_local.get();
+  }
+  if (int rc = hdsm_internal_local_bind(world, comms, send.data(), d0->per)) return fail(rc, std::string("hdsm_dswarm_round_ranks: ") + hdsm_last_error());
+  // every "published" is recorded (front) before a gather waits for it (back); every "gathered" before the next round's k_commit does
+  for (int r = 0; r < world; ++r) {
+    DSwarm* d = static_cast<DSwarm*>(dswarms[r]);
+    HIP_TRY(hipSetDevice(d->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_streams ? hip_streams[r] : nullptr);
+    DoneOnce done_once(d->solver, st);
+    if (int rc = round_front(*d, comms[r], st)) return rc;
+  }
+  for (int r = 0; r < world; ++r) {
+    DSwarm* d = static_cast<DSwarm*>(dswarms[r]);
+    HIP_TRY(hipSetDevice(d->device));
+    if (int rc = round_back(*d, comms[r], comms[r], static_cast<hipStream_t>(hip_streams ? hip_streams[r] : nullptr))) return rc;
+  }
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_raw(void* dswarm, double* plans_all_raw, double* send_raw) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t L = (size_t)d->per, G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
+  if (plans_all_raw && G) HIP_TRY(hipMemcpy(plans_all_raw, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
+  if (send_raw && L) HIP_TRY(hipMemcpy(send_raw, d->d_local.get(), L * rec * 8, hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 

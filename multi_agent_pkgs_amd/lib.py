@@ -79,14 +79,14 @@ CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), (
 
 
 def parse_declarations(text):
-    """{name: (restype, argtypes)} of every `<ret> hdsm_name(<args>);` in the text of a header. `T x[3]` is `T*`; a C type that
-    CTYPES does not know raises."""
+    """{name: (restype, argtypes)} of every `<ret> hdsm_name(<args>);` in the text of a header. `T x[3]` is `T*`, `T* const* x` (an
+    array of pointers the callee only reads) is `T**`; a C type that CTYPES does not know raises."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
 
     def ctype(decl, fn, ret=False):
-        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(?:\w+\s*(\[\w*\])?)?", decl.strip())
-        key = m and m.group(1) + m.group(2) + ("*" if m.group(3) else "")
+        m = re.fullmatch(r"(?:const\s+)?(\w+)\s*(\**)\s*(?:const\s*(\*)\s*)?(?:\w+\s*(\[\w*\])?)?", decl.strip())
+        key = m and m.group(1) + m.group(2) + (m.group(3) or "") + ("*" if m.group(4) else "")
         if ret and key == "void":
             return None
         if key not in CTYPES:

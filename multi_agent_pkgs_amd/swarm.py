@@ -467,6 +467,73 @@ class DeviceSwarm:
             pass
 
 
+class LocalRanks:
+    """A sharded swarm flown by ONE process (hdsm_comm_create_local / hdsm_dswarm_round_ranks, ABI 1.9): the `world` blocks of
+    shard_range as host mirrors, one solver handle and one DeviceSwarm per rank — on devices[r], default all on device 0 — and a
+    local communicator group; round() flies one replan round of all ranks with one call. setup(shard, rank), if given, is called on
+    every host mirror before its dswarm is made (world, paths, groups, audit: what a DeviceSwarm takes over from its shard)."""
+
+    def __init__(self, prm, cfg, n_rob, world, starts=None, goals=None, radius=None, devices=None, setup=None):
+        self.lib = _lib.load()
+        self.n_rob, self.world = int(n_rob), int(world)
+        self.per = (self.n_rob + self.world - 1) // self.world
+        self.devices = [0] * self.world if devices is None else [int(d) for d in devices]
+        assert len(self.devices) == self.world
+        if starts is None:
+            starts, goals = circle_scenario(n_rob, radius)
+        starts, goals = np.asarray(starts, dtype=np.float64), np.asarray(goals, dtype=np.float64)
+        self.shards, self.solvers, self.dswarms = [], [], []
+        self._comms = (C.c_void_p * self.world)()
+        for r in range(self.world):
+            first, n_local = shard_range(self.n_rob, r, self.world)
+            shard = SwarmShard(prm, cfg, self.n_rob, first, starts[first:first + n_local], goals[first:first + n_local])
+            if setup is not None:
+                setup(shard, r)
+            self.shards.append(shard)
+            self.solvers.append(_lib.Solver(prm, self.per, self.world * self.per, device=self.devices[r]))
+        handles = (C.c_void_p * self.world)(*[s.h.value for s in self.solvers])
+        call("hdsm_comm_create_local", self.world, handles, self._comms)
+        for r in range(self.world):
+            self.dswarms.append(DeviceSwarm(self.shards[r], self.solvers[r], world_size=self.world, device=self.devices[r]))
+        self._dsw = (C.c_void_p * self.world)(*[d.h.value for d in self.dswarms])
+
+    @property
+    def comms(self):
+        """The hdsm_comm of every rank (addresses)."""
+        return [self._comms[r] for r in range(self.world)]
+
+    def round(self, streams=None):
+        """hdsm_dswarm_round_ranks: one round of every rank; streams: one torch stream per rank (None entries, or None: the default)."""
+        st = (C.c_void_p * self.world)(*[_stream(s) for s in (streams or [None] * self.world)])
+        call("hdsm_dswarm_round_ranks", self.world, self._dsw, self._comms, st)
+
+    def download_raw(self, rank):
+        """hdsm_dswarm_download_raw of one rank: (plans buffer [world * per][N+1][9] as it is, sentinels included; send buffer
+        [per][N+1][9]). Synchronises that rank's device."""
+        N = self.shards[rank].prm.n_hor
+        plans, send = np.zeros((self.world * self.per, N + 1, 9)), np.zeros((self.per, N + 1, 9))
+        call("hdsm_dswarm_download_raw", self.dswarms[rank].h, plans, send)
+        return plans, send
+
+    def close(self):
+        for d in self.dswarms:
+            d.close()
+        self.dswarms = []
+        for r in range(self.world):
+            if self._comms[r]:
+                self.lib.hdsm_comm_destroy(self._comms[r])
+                self._comms[r] = None
+        for s in self.solvers:
+            s.close()
+        self.solvers = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def flight_summary(reports, first_id=0):
     """Folds per-agent flight records (lib.FLIGHT_REPORT, of one shard or concatenated in id order starting at first_id) into a swarm
     summary: sigma_min (the smallest separation ratio flown, None without a pair) with both ids, the sub-step and the agent's audited
