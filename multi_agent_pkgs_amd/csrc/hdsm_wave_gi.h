@@ -728,7 +728,9 @@ struct WaveGI {
           for (int f = 0; f < FB; ++f) {
             const int k = k0 + f * nt;
             const double ux = bk[f].x - sx, uy = bk[f].y - sy, uz = bk[f].z - sz, reach = reach0 + bk[f].w;
-            if (k < end && k != self && bk[f].w >= 0 && ux * ux + uy * uy + uz * uz < reach * reach)
+            // (not `<`: the never-culled record of a non-finite plan has radius 1e300, reach * reach is +inf, and its centre may be
+            // infinite or NaN — `inf < inf` and `NaN < inf` would skip the neighbour together with its finite steps)
+            if (k < end && k != self && bk[f].w >= 0 && !(ux * ux + uy * uy + uz * uz > reach * reach))
               s.list[atomicAdd(&s.nlist, 1)] = k;
           }
         }

@@ -136,7 +136,11 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   if (own_has && np >= 2 && monotone) {
     // (1) the neighbour whose sphere is closest: its exact squared distances bound the minima from above
     const double4 ss = *reinterpret_cast<const double4*>(a.rsph + (int64_t)self * 4);
-    double gbest = DBL_MAX;
+    // Only a FINITE gap is a candidate (g < +inf, false for a NaN): the centre of a non-finite plan's sphere may be infinite (g = +inf)
+    // or NaN (a plan with +inf and -inf on one axis). Taken as a lane's first candidate, a NaN lost to nobody, and every neighbour
+    // the lane met after it was missing from the bound: with no other candidate the bound became 0 and neighbours whose sphere did
+    // not touch ours were culled. Such a sphere needs no bound: its radius is 1e300 and pass (2) keeps it whatever umax is.
+    double gbest = HUGE_VAL;
     int jbest = -1;
     constexpr int UB = 8;  // sphere records in flight per thread: the scans are chains of L2 round trips otherwise
     for (int j0 = g_lo + tid; j0 < g_hi; j0 += UB * NT) {
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
         if (j >= g_hi || j == self || sj[u].w < 0) continue;  // (w < 0: no plan)
         const double cx = sj[u].x - ss.x, cy = sj[u].y - ss.y, cz = sj[u].z - ss.z;
         const double g = sqrt(cx * cx + cy * cy + cz * cz) - sj[u].w - ss.w;  // every step of j is at least this far (g may be < 0)
-        if (g < gbest || jbest < 0) gbest = g, jbest = j;
+        if (g < gbest) gbest = g, jbest = j;
       }
     }
     {  // (which of several equally close spheres wins only moves the bound below)

@@ -352,7 +352,7 @@ static void cp_instance(cp_batch* B, int k) {
       const double* sj = B->sph + 4 * (size_t)j;                                                                                       \
       if (j == self || sj[3] < 0) continue;                                                                                            \
       const double ux = sj[0] - mid[0], uy = sj[1] - mid[1], uz = sj[2] - mid[2], reach = cull + rho_self + sj[3];                     \
-      if (!(ux * ux + uy * uy + uz * uz < reach * reach)) continue;                                                                    \
+      if (ux * ux + uy * uy + uz * uz > reach * reach) continue; /* (a NaN or infinite centre with radius 1e300: kept) */               \
       for (int i = 0; i < N; i++) {                                                                                                    \
         const double* o = B->plans + ((size_t)j * (N + 1) + i + 1) * 9;                                                                \
         const double dx = o[0] - cprev[i][0], dy = o[1] - cprev[i][1], dz = o[2] - cprev[i][2];                                        \

@@ -411,3 +411,94 @@ def read_back(traj_prev, ctrl_prev, used_prev, traj_new, ctrl_new, used_new, fai
     traj.append(list(traj[-1]))    # AC:1010-1013
     ctrl.append(list(ctrl[-1]))
     return np.array(traj, dtype=np.float64), np.array(ctrl, dtype=np.float64), np.array(used_prev, dtype=np.uint8)
+
+
+# ---- row f1: the reference trajectory of one agent (GenerateReferenceTrajectory AC:1449-1553 on a path that already starts at the
+# starting point, SamplePath AC:1591-1663, the neighbour term of ComputePathVelocity AC:1769-1801, GetVelocityLimit AC:1805-1817)
+LD = np.longdouble
+
+
+def reference_row(n_hor, dt, cfg, agent_id, path, n_path, plans, has_plan, vel_cap=None, ranges=None):
+    """Row f1 in numpy.longdouble, one instance at a time, every (step, neighbour) pair evaluated, nothing culled.
+
+    Layouts of hdsm_reference: path [n_inst][pmax][3], plans [n_rob][N + 1][9], has_plan [n_rob]; cfg has the six fields of
+    hdsm_ref_config. vel_cap (the voxel term, computed elsewhere) starts the minimum, clipped to path_vel_max. ranges (optional,
+    [n_inst][2]): the neighbours of instance k are the ids lo <= j < hi only (neighbour groups).
+    Returns (ref_full [n_inst][N + 1][6], ref [n_inst][N][6], path_vel [n_inst], info): the three outputs rounded to double, and
+    per instance info[k] = dict(walk=[|dist_next - limit| of every comparison of the walk], vel=[|dist - 1e-2| of every
+    velocity row], setter=(neighbour, step) of the pair that set path_vel, or None if the cap did).
+    A path of one point gives N copies of it (AC:1597-1608), reported as N + 1 rows and path_vel 0, the project's convention."""
+    N = int(n_hor)
+    n_inst, n_rob = len(agent_id), len(has_plan)
+    pos = np.asarray(plans, dtype=np.float64)[:, :, :3].astype(LD)
+    has = np.asarray(has_plan).astype(bool)
+    vmin, vmax, kd = LD(cfg.path_vel_min), LD(cfg.path_vel_max), LD(cfg.sens_dist)
+    dec_step = LD(cfg.path_vel_dec) * LD(dt)
+    weight = []
+    for i in range(N + 1):                       # AC:1791-1795 and the clamp of AC:1807-1810
+        occ = LD(100) * np.power(LD(cfg.sens_other_agents), LD(i))
+        occ = min(max(occ, LD(0)), LD(100))
+        weight.append(np.power(occ / LD(100), LD(cfg.sens_pot)))
+    full = np.zeros((n_inst, N + 1, 6))
+    pvs = np.zeros(n_inst)
+    info = []
+    for k in range(n_inst):
+        me, npts = int(agent_id[k]), int(n_path[k])
+        pth = np.asarray(path[k], dtype=np.float64).astype(LD)
+        pv = vmax if vel_cap is None else min(LD(vel_cap[k]), vmax)
+        setter = None
+        lo, hi = (0, n_rob) if ranges is None else (max(int(ranges[k][0]), 0), min(int(ranges[k][1]), n_rob))
+        if npts >= 2 and 0 <= me < n_rob and has[me]:
+            other = np.zeros(n_rob, dtype=bool)
+            other[lo:hi] = has[lo:hi]
+            other[me] = False
+            ids = np.nonzero(other)[0]
+            for i in range(N + 1):               # AC:1770: every state of the agent's own plan
+                if ids.size == 0:
+                    break
+                diff = pos[ids, i] - pos[me, i]
+                with np.errstate(all="ignore"):
+                    dist = np.sqrt(diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1] + diff[:, 2] * diff[:, 2])
+                    lim = vmin + (vmax - vmin) * (LD(1) - weight[i] * (LD(1) / np.exp(kd * dist)))
+                    below = lim < pv             # (false for a NaN: such a pair limits nothing)
+                if below.any():
+                    w = int(np.argmin(np.where(below, lim, np.inf)))
+                    pv, setter = lim[w], (int(ids[w]), i)
+        walk, pts = [], []
+        if npts < 2:
+            pts = [pth[0]] * N
+            pv = LD(0)
+        else:
+            samp = pv * LD(dt)
+            cur, limit, at, done = pth[0], samp, 1, 0
+            pts.append(cur)
+            while done < N:
+                step = pth[at] - cur
+                dist_next = np.sqrt(step[0] * step[0] + step[1] * step[1] + step[2] * step[2])
+                walk.append(float(abs(dist_next - limit)))
+                if dist_next > limit:
+                    cur = cur + limit * step / dist_next
+                    pts.append(cur)
+                    done += 1
+                    limit = max(LD(0), samp - dec_step)
+                else:
+                    cur = pth[at]
+                    at += 1
+                    if at == npts:
+                        pts.extend([pth[npts - 1]] * (N - done))
+                        break
+                    limit = limit - dist_next
+        vel_margin, vel = [], np.zeros(3, dtype=LD)
+        rows = np.zeros((len(pts), 6), dtype=LD)
+        for i, p in enumerate(pts):
+            if i + 1 < len(pts):
+                back = p - pts[i + 1]
+                dist = np.sqrt(back[0] * back[0] + back[1] * back[1] + back[2] * back[2])
+                vel_margin.append(float(abs(dist - LD(1e-2))))
+                vel = pv * back / dist if dist > LD(1e-2) else np.zeros(3, dtype=LD)
+            rows[i, :3], rows[i, 3:] = p, vel if len(pts) > 1 else 0
+        full[k, :len(pts)] = rows.astype(np.float64)
+        full[k, len(pts):] = full[k, len(pts) - 1]
+        pvs[k] = float(pv)
+        info.append(dict(walk=walk, vel=vel_margin, setter=setter))
+    return full, full[:, :N].copy(), pvs, info

@@ -348,6 +348,39 @@ def test_sphere_prefilter_never_changes_the_answer(hdsm, oracle, case, monkeypat
     compare(g_pre, oracle.replan(prm, *args, n_threads=8))
 
 
+@pytest.mark.parametrize("bad", [np.inf, "both"], ids=["plus-inf", "plus-and-minus-inf"])
+def test_sphere_prefilter_keeps_the_finite_steps_of_a_non_finite_plan(hdsm, oracle, monkeypatch, bad):
+    """A neighbour S with has_plan = 1 whose x coordinate is +inf at the last two steps (the centre of its sphere is infinite), or
+    +inf at the last step and -inf at the one before (the centre is NaN): its record is the never-culled one (radius 1e300), and
+    the sphere prefilter (forced by HDSM_BOUNDS_MIN=1) must list it, because the planes of its finite steps shape the answer.
+    S is the first agent for which they do: the oracle's answer for some other agent moves by more than 1e-3 m when S's
+    has_plan is cleared. The kernel against the oracle on the plans as published, tolerances of compare()."""
+    prm = agile_params(10, max_rows_static=18)
+    n_rob, N = 16, prm.n_hor
+    sn = problems.swarm_snapshot(prm, n_rob, seed=2, turn=True)
+    head = [sn[k] for k in ARG_KEYS[:-2]]
+    for S in range(n_rob):
+        plans, gone = sn["plans"].copy(), sn["has_plan"].copy()
+        plans[S, N - 1:, 0] = np.inf
+        if bad == "both":
+            plans[S, N - 1, 0] = -np.inf
+        gone[S] = 0
+        want = oracle.replan(prm, *head, plans, sn["has_plan"], n_threads=8)
+        without = oracle.replan(prm, *head, plans, gone, n_threads=8)
+        others = (np.arange(n_rob) != S) & (want["status"] == 0) & (without["status"] == 0)
+        if sn["has_plan"][S] and others.any() and np.abs(want["traj"] - without["traj"])[others].max() > 1e-3:
+            break
+    else:
+        raise AssertionError("no agent whose finite steps decide another agent's answer")
+    monkeypatch.setenv("HDSM_BOUNDS_MIN", "1")
+    sol = hdsm.Solver(prm, n_rob, n_rob)
+    g = sol.replan(*head, plans, sn["has_plan"])
+    assert (sol.last_sweep_stats(n_rob)["sphere_records"] > 0).any()      # the sphere list ran
+    assert (want["status"] == 0).sum() > n_rob // 2
+    compare(g, want)
+    sol.close()
+
+
 def test_sphere_prefilter_chunks_beyond_list_capacity(hdsm, oracle):
     """1300 agents (> one chunk of 1024 neighbours): instances from both ends of the id range against the oracle."""
     prm = agile_params(10, max_rows_static=18)
