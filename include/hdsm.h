@@ -370,6 +370,29 @@ int hdsm_comm_create_local(int32_t world, void* const* handles, void** comms);
  * warm-start sets and the launch order stay keyed by instance index. Synchronises the handle.                             */
 int hdsm_set_groups(void* handle, int32_t n_groups, const int32_t* group_start);
 
+/* ---- stale plans: time-aligned neighbours and an own-plan override --------------------------------------------
+ * The reference computes how many planning iterations old a neighbour's trajectory is (it_diff, AC:1126-1128) and then reads
+ * traj.states[i + 1] whatever the stamp (AC:1147). A caller that receives plans of different ages says so here.
+ * One definition: with shift[k] = s >= 0, every instance OTHER than k's own reads record k as the record R'[i] = R[min(i + s, N)],
+ * i = 0..N — the plan advanced by s steps with its last state (v = a = 0) held. Every result for agent a is what the call returns
+ * without a shift for a alone when the other agents' records are materialised that way, a's own record is unshifted and comes from
+ * the own-plan override where one is set. Honoured wherever the handle reads other agents' records: hdsm_replan, hdsm_replan_device
+ * (positions AND prefilter spheres), hdsm_reference, hdsm_reference_device, hdsm_tasc_planes; hdsm_solve has no neighbours.
+ *   hdsm_set_plan_shift         shift[n_rob] is a HOST array, copied (n_rob <= n_rob_max; agents behind it are unshifted). NULL or
+ *                               n_rob = 0 clears it. A negative value: HDSM_ERR_BAD_ARG; values above N behave as N. Synchronises.
+ *   hdsm_set_plan_shift_device  d_shift is a BORROWED device array of at least the n_rob of every later call, read by each launch
+ *                               (the caller may rewrite it between launches, ordered by the stream); NULL clears it. Negative
+ *                               entries behave as 0. The two forms replace each other.
+ *   hdsm_set_own_plans_device   borrowed device arrays in the layouts of plans_all / has_plan: the instance of agent a takes its own
+ *                               previous plan and its own flag from d_own_plans[a] / d_own_has[a] instead of plans_all[a] /
+ *                               has_plan[a] (d_own_has NULL: the flag stays has_plan[a]); d_own_plans NULL clears both. For a batch
+ *                               caller that holds many agents with a stale view of EACH OTHER (the device loop with link faults);
+ *                               a single-agent caller simply puts its fresh plan into its own slot of plans_all.
+ * With nothing set every launch is what it was before these calls existed.                                                    */
+int hdsm_set_plan_shift(void* handle, int32_t n_rob, const int32_t* shift);
+int hdsm_set_plan_shift_device(void* handle, const int32_t* d_shift);
+int hdsm_set_own_plans_device(void* handle, const double* d_own_plans, const uint8_t* d_own_has);
+
 /* Forget the working sets kept for warm_start (e.g. after re-assigning agents to instance indices).      */
 int hdsm_reset_warm_start(void* handle);
 
@@ -386,7 +409,9 @@ const char* hdsm_last_error(void);
  * hdsm_dswarm_update_world / _set_raw_world / _update_world_raw / _update_world_raw_device / _download_world / _world_stats in
  * hdsm_swarm.h); 1.8: + neighbour groups (hdsm_set_groups here; hdsm_swarm_set_groups, hdsm_dswarm_group_report and
  * hdsm_group_report in hdsm_swarm.h); 1.9: + local ranks (hdsm_comm_create_local here; hdsm_dswarm_round_ranks and
- * hdsm_dswarm_download_raw in hdsm_swarm.h); nothing removed or changed.   */
+ * hdsm_dswarm_download_raw in hdsm_swarm.h); nothing removed or changed. Stale plans (hdsm_set_plan_shift / _shift_device /
+ * hdsm_set_own_plans_device here; hdsm_link_deliver_host, hdsm_dswarm_set_links / _link_stats / _download_seen in hdsm_swarm.h) were
+ * added WITHOUT a new minor: the word stays 1.9, callers discover them by symbol.   */
 int32_t hdsm_version(void);
 
 #ifdef __cplusplus

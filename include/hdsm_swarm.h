@@ -419,6 +419,44 @@ int hdsm_dswarm_group_report(void* dswarm, hdsm_group_report* out);
 int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* comms, void* const* hip_streams);
 int hdsm_dswarm_download_raw(void* dswarm, double* plans_all_raw, double* send_raw);
 
+/* ---- link faults in the device loop: lossy and late broadcasts (no new ABI minor; discover by symbol) ------------------------------
+ * The reference has no fault injection (com_latency is declared and never used) and uses a stale neighbour plan as it is
+ * (AC:1126-1147). Here every record an agent publishes has a FATE, and a round solves against what has ARRIVED:
+ *   hdsm_dswarm_set_links   fate[n_rounds][n_rob] int8 (host, copied), read cyclically: entry (q mod n_rounds, k) is the fate of the
+ *                           record agent k publishes in link round q — < 0: lost for everyone; d in 0..HDSM_LINK_MAX_DELAY: it arrives
+ *                           d rounds late (0 = on time). Link round 0 is the first round after the call; at the call the view is the
+ *                           current plans buffer and every slot counts as delivered on time. n_rounds = 0 (or fate NULL) turns links
+ *                           off. The model is PER SENDER: every receiver, on every rank, sees the same thing — a link that fails for
+ *                           one receiver only cannot be expressed. Ranks of a sharded swarm each get the same call. time_aware != 0:
+ *                           a record that is `age` rounds old is read advanced by min(age * step_plan, N) steps, last state held
+ *                           (hdsm_set_plan_shift_device, hdsm.h); 0: as it is, the reference's actual behaviour. An entry above
+ *                           HDSM_LINK_MAX_DELAY: HDSM_ERR_BAD_ARG. Synchronises. Device memory is allocated by the first call only; a
+ *                           flight that never calls it allocates and launches nothing new.
+ * While links are on, k_deliver runs behind the exchange of every round: it keeps the last D + 1 rounds of published records (D =
+ * the largest delay of the table), and per slot takes the NEWEST record that has arrived and is newer than the one held (an older
+ * record that arrives after a newer one is ignored) into the `seen` view with its flag, round and shift. The next round's reference
+ * and solve read `seen` / `seen_has` as the plans of the OTHER agents; every agent's own plan stays its fresh one
+ * (hdsm_set_own_plans_device). The plans buffer stays the truth: the audit, the history, hdsm_dswarm_download and the takeover read it
+ * unchanged — the audit judges what was flown, not what was believed.
+ *   hdsm_dswarm_link_stats     out[0] link rounds since the last hdsm_dswarm_set_links, out[1] records delivered into views, out[2]
+ *                              broadcasts lost, out[3] the largest age in rounds any agent's slot reached; folded on the host from the
+ *                              per-slot counters. Synchronises.
+ *   hdsm_dswarm_download_seen  the view as the next round reads it: seen_raw [world_size * per][N+1][9] (raw: a slot without a plan
+ *                              carries the sentinel), seen_has, seen_round (link round of the record held, -1 = the view of the call)
+ *                              and shift, [world_size * per] each; any pointer may be NULL. HDSM_ERR_BAD_ARG before the first
+ *                              hdsm_dswarm_set_links. Synchronises.
+ *   hdsm_link_deliver_host     k_deliver's round on host arrays, the same source (csrc/link_core.h), bit for bit: n_slots records
+ *                              truth[n_slots][N+1][9] published in link round `link_round`; ring [max_delay + 1][n_slots][N+1][9], seen,
+ *                              seen_has, seen_round, shift and counters [n_slots][4] (delivered, lost, largest age, rounds) are updated
+ *                              in place. Slots k >= n_rob (padding) are delivered on time. Pure: no device, no state of its own.   */
+#define HDSM_LINK_MAX_DELAY 7
+int hdsm_dswarm_set_links(void* dswarm, int32_t n_rounds, const int8_t* fate, int32_t time_aware);
+int hdsm_dswarm_link_stats(void* dswarm, int64_t out[4]);
+int hdsm_dswarm_download_seen(void* dswarm, double* seen_raw, uint8_t* seen_has, int32_t* seen_round, int32_t* shift);
+int hdsm_link_deliver_host(int32_t n_slots, int32_t n_rob, int32_t n_hor, int32_t step_plan, int32_t n_rounds, const int8_t* fate,
+                           int32_t max_delay, int32_t time_aware, int32_t link_round, const double* truth, double* ring, double* seen,
+                           uint8_t* seen_has, int32_t* seen_round, int32_t* shift, int32_t* counters);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

@@ -23,6 +23,7 @@
 #include "hdsm_internal.h"
 #include "hdsm_level1.h"
 #include "hdsm_shapes.h"
+#include "link_core.h"
 #include "plan_pack.h"
 
 using namespace hdsm_entry;
@@ -201,10 +202,13 @@ __device__ void setup_map_tile(const SetupMapArgs& m, int tile) {
 //   bounds[n_rob][4]   (only for swarms of at least bounds_min agents) centre of the bounding box of those positions and the
 //                      radius of the sphere around it that holds them (radius -1 = no plan): the sweeps use it to skip
 //                      whole neighbours (hdsm_wave_gi.h, sweep_planes).
+// shift (hdsm_set_plan_shift*; null = none): record k is packed advanced by shift[k] steps with its last state held
+// (hdsm_link::shifted_step) — positions AND sphere, so the sweeps, the prefilter and the warm start's rebuilt rows all see the shifted plan.
 __global__ __launch_bounds__(256) void k_plan_prepass(int N, int n_rob, const double* __restrict__ plans,
                                                       const uint8_t* __restrict__ has_plan, double* __restrict__ pos,
                                                       double* __restrict__ bounds, int n_order, const int32_t* __restrict__ key_prev,
-                                                      const int32_t* __restrict__ agent_id, int32_t* __restrict__ order, SetupMapArgs sm) {
+                                                      const int32_t* __restrict__ agent_id, int32_t* __restrict__ order, SetupMapArgs sm,
+                                                      const int32_t* __restrict__ shift) {
   if (sm.out != nullptr && (int)blockIdx.x >= sm.first_block) {  // the workgroups behind the pre-pass proper: four tiles of the set-up map each
     setup_map_tile(sm, ((int)blockIdx.x - sm.first_block) * 4 + ((int)threadIdx.x >> 6));
     return;
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void k_plan_prepass(int N, int n_rob, const do
   const bool on = has && i < N;
   double p[3] = {0.0, 0.0, 0.0};
   if (on) {
-    const double* rec = plans + ((int64_t)k * (N + 1) + 1 + i) * 9;
+    const double* rec = plans + ((int64_t)k * (N + 1) + hdsm_link::shifted_step(1 + i, shift != nullptr ? shift[k] : 0, N)) * 9;
     p[0] = rec[0], p[1] = rec[1], p[2] = rec[2];
   }
   if (live && i < N) {
@@ -242,7 +246,8 @@ __global__ __launch_bounds__(256) void k_launch_order(int n_inst, const int32_t*
 __global__ __launch_bounds__(256) void k_tasc_planes(const hdsm::Consts* __restrict__ cp, int n_inst, int n_rob,
                                                      const int32_t* agent_id, const double* state,
                                                      const double* plans, const uint8_t* has_plan,
-                                                     double* planes, const int32_t* __restrict__ range) {
+                                                     double* planes, const int32_t* __restrict__ range, const int32_t* __restrict__ shift,
+                                                     const double* own_plans, const uint8_t* own_has) {
   const hdsm::Consts& c = *cp;
   const int N = c.N;
   const int64_t total = (int64_t)n_inst * N * n_rob;
@@ -258,11 +263,13 @@ __global__ __launch_bounds__(256) void k_tasc_planes(const hdsm::Consts* __restr
     const bool near = range == nullptr || (ranged && k >= range[2 * self] && k < range[2 * self + 1]);
     if (k != self && near && has_plan[k]) {
       double cp3[3];
-      const bool own = self >= 0 && self < n_rob && has_plan[self];
+      // (own_plans / own_has: the call's arrays unless hdsm_set_own_plans_device named others; the neighbour's record at its shifted step)
+      const bool own = self >= 0 && self < n_rob && own_has[self];
       for (int ax = 0; ax < 3; ++ax)
-        cp3[ax] = own ? plans[((int64_t)self * (N + 1) + (i + 1)) * 9 + ax] : state[(int64_t)inst * 9 + ax];
+        cp3[ax] = own ? own_plans[((int64_t)self * (N + 1) + (i + 1)) * 9 + ax] : state[(int64_t)inst * 9 + ax];
       double tmp[4];
-      if (hdsm::Solver<32, 16>::tasc_plane(c, cp3, plans + ((int64_t)k * (N + 1) + (i + 1)) * 9, tmp))
+      const int ik = hdsm_link::shifted_step(i + 1, shift != nullptr ? shift[k] : 0, N);
+      if (hdsm::Solver<32, 16>::tasc_plane(c, cp3, plans + ((int64_t)k * (N + 1) + ik) * 9, tmp))
         row[0] = tmp[0], row[1] = tmp[1], row[2] = tmp[2], row[3] = tmp[3];
     }
     double* out = planes + idx * 4;
@@ -405,6 +412,11 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
   if (ordered) a.order = pp.d_order.get();
   const bool packed = h->defer_done && a.l1_rows == nullptr && pp.plans == a.plans && pp.n_rob == a.n_rob && pp.n_inst == a.n_inst && pp.ordered == ordered;
   pp.plans = nullptr;  // (good for one solve: the plans change with the commit that follows it)
+  // Stale plans. The neighbours reach the solver kernels packed (pos / bounds, shifted by the pre-pass) and `plans` is read there for the
+  // instance's own record alone: the own-plan override is resolved here, the kernels only choose where the own flag comes from.
+  const double* const neigh_plans = a.plans;
+  const int32_t* const shift = a.l1_rows == nullptr ? h->shift : nullptr;
+  if (a.l1_rows == nullptr && h->own_plans != nullptr) a.plans = h->own_plans, a.own_has = h->own_has;
   // the set-up map of every instance as one product on the matrix cores (k_plan_prepass, setup_map_tile): rides on the pre-pass launch
   SetupMapArgs sm{};
   a.setup = nullptr;
@@ -419,14 +431,14 @@ int launch(Handle* h, hdsm::Args a, hipStream_t st) {
     a.bounds = prefilter ? pp.d_bounds.get() : nullptr;
     if (sm_blocks > 0) {  // (the device-resident loop packs the plans elsewhere: the tiles alone)
       sm.first_block = 0;
-      hipLaunchKernelGGL(k_plan_prepass, dim3(sm_blocks), dim3(256), 0, st, h->N, 0, a.plans, a.has_plan, pp.d_pos.get(), nullptr, 0, a.st_key, a.agent_id, nullptr, sm);
+      hipLaunchKernelGGL(k_plan_prepass, dim3(sm_blocks), dim3(256), 0, st, h->N, 0, neigh_plans, a.has_plan, pp.d_pos.get(), nullptr, 0, a.st_key, a.agent_id, nullptr, sm, shift);
       HIP_TRY(hipGetLastError());
     }
   } else if (a.l1_rows == nullptr) {
     double* const bounds = prefilter ? pp.d_bounds.get() : nullptr;
     sm.first_block = (a.n_rob + 15) / 16 + (ordered ? 1 : 0);
-    hipLaunchKernelGGL(k_plan_prepass, dim3(sm.first_block + sm_blocks), dim3(256), 0, st, h->N, a.n_rob, a.plans, a.has_plan,
-                       pp.d_pos.get(), bounds, a.n_inst, a.st_key, a.agent_id, ordered ? pp.d_order.get() : nullptr, sm);
+    hipLaunchKernelGGL(k_plan_prepass, dim3(sm.first_block + sm_blocks), dim3(256), 0, st, h->N, a.n_rob, neigh_plans, a.has_plan,
+                       pp.d_pos.get(), bounds, a.n_inst, a.st_key, a.agent_id, ordered ? pp.d_order.get() : nullptr, sm, shift);
     HIP_TRY(hipGetLastError());
     a.pos = pp.d_pos.get();
     a.bounds = bounds;
@@ -703,7 +715,9 @@ int hdsm_tasc_planes(void* handle, int32_t n_inst, int32_t n_rob, const int32_t*
     const int64_t items = (int64_t)(total / 4);
     const int blocks = (int)((items + 255) / 256 > 4096 ? 4096 : (items + 255) / 256);
     hipLaunchKernelGGL(k_tasc_planes, dim3(blocks), dim3(256), 0, st, h->d_consts.get(), n_inst, n_rob, s.d_agent.get(),
-                       s.d_state.get(), s.d_plans.get(), s.d_has.get(), s.planes.get(), h->range());
+                       s.d_state.get(), s.d_plans.get(), s.d_has.get(), s.planes.get(), h->range(), h->shift,
+                       h->own_plans != nullptr ? h->own_plans : s.d_plans.get(),
+                       h->own_plans != nullptr && h->own_has != nullptr ? h->own_has : s.d_has.get());
     cp.err(hipGetLastError());
   }
   cp(planes, s.planes.get(), total * 8, hipMemcpyDeviceToHost);
@@ -743,6 +757,43 @@ int hdsm_set_groups(void* handle, int32_t n_groups, const int32_t* group_start) 
   if (!h->d_range) HIP_TRY(h->d_range.alloc(table.size()));
   HIP_TRY(hipMemcpy(h->d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   h->n_total = group_start[n_groups], h->group_max = gmax;
+  return HDSM_OK;
+}
+
+// Stale plans (include/hdsm.h). The three setters only say where the launches that follow read from; each of them makes the handle's
+// cached pre-pass (Prepass::plans) invalid, because what was packed before the change is not this view's.
+int hdsm_set_plan_shift(void* handle, int32_t n_rob, const int32_t* shift) {
+  Handle* h = static_cast<Handle*>(handle);
+  if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
+  if (n_rob < 0 || n_rob > h->n_rob_max) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_plan_shift: n_rob out of range");
+  const bool none = n_rob == 0 || shift == nullptr;
+  std::vector<int32_t> table((size_t)h->n_rob_max, 0);
+  for (int k = 0; !none && k < n_rob; ++k) {
+    if (shift[k] < 0) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_plan_shift: negative shift");
+    table[(size_t)k] = shift[k] > h->N ? h->N : shift[k];
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  h->pre.plans = nullptr, h->shift = nullptr;
+  if (none) return HDSM_OK;
+  if (!h->d_shift) HIP_TRY(h->d_shift.alloc(table.size()));
+  HIP_TRY(hipMemcpy(h->d_shift.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  h->shift = h->d_shift.get();
+  return HDSM_OK;
+}
+
+int hdsm_set_plan_shift_device(void* handle, const int32_t* d_shift) {
+  Handle* h = static_cast<Handle*>(handle);
+  if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
+  h->pre.plans = nullptr, h->shift = d_shift;
+  return HDSM_OK;
+}
+
+int hdsm_set_own_plans_device(void* handle, const double* d_own_plans, const uint8_t* d_own_has) {
+  Handle* h = static_cast<Handle*>(handle);
+  if (!h) return set_err(HDSM_ERR_BAD_ARG, "null handle");
+  if (d_own_plans == nullptr && d_own_has != nullptr) return set_err(HDSM_ERR_BAD_ARG, "hdsm_set_own_plans_device: flags without plans");
+  h->pre.plans = nullptr, h->own_plans = d_own_plans, h->own_has = d_own_has;
   return HDSM_OK;
 }
 

@@ -967,7 +967,7 @@ struct Solver {
       // the own plan (or, before the first plan exists, the current position at every step)
       const bool self_ok = self >= 0 && self < g.n_rob;
       const int sidx = self_ok ? self : 0;
-      const uint8_t has_own = g.has_plan[sidx];
+      const uint8_t has_own = (g.own_has != nullptr ? g.own_has : g.has_plan)[sidx];  // (a wave-uniform choice of base address)
       if (tid == 0) {  // the neighbour range (requested with the own plan: no round trip of its own)
         int lo = 0, hi = g.n_rob;
         if (g.range != nullptr) {

@@ -90,6 +90,14 @@ struct Handle {
   int n_total = 0, group_max = 0;
   const int32_t* range() const { return n_total > 0 ? d_range.get() : nullptr; }
   int prefilter_agents(int n_rob) const { return n_total > 0 ? group_max : n_rob; }
+  // stale plans. shift: [n_rob] steps by which every instance but k's own reads record k advanced (last state held), read where the
+  // plans are packed — d_shift (hdsm_set_plan_shift, [n_rob_max], allocated by the first call) or a borrowed device array
+  // (hdsm_set_plan_shift_device); null = none. own_plans / own_has: borrowed, where instance a takes its own previous plan and flag
+  // from instead of plans_all[a] / has_plan[a] (hdsm_set_own_plans_device); null = the call's arrays.
+  DevBuf<int32_t> d_shift;
+  const int32_t* shift = nullptr;
+  const double* own_plans = nullptr;
+  const uint8_t* own_has = nullptr;
   // words in mapped pinned memory the kernels raise (Args::ovf_flag, tree_flag, item_total): an instance ended on a staging overflow;
   // an instance met a deep tree; items queued by the last split launch (the merge writes it)
   hdsm_mem::MappedWord ovf_flag, tree_flag, item_total;

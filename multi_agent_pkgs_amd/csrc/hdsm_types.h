@@ -192,6 +192,10 @@ struct Args {
   // neighbour groups (hdsm_set_groups): [n_rob_max][2] = the id range [lo, hi) agent k takes its neighbours from ((0, 0) for ids behind
   // the partition); null = [0, n_rob) for everybody. The last member, and null by default: code that fills Args member by member stays as it is.
   const int32_t* range = nullptr;
+  // the own-plan override (hdsm_set_own_plans_device): [n_rob] the flag instance a takes for ITS OWN previous plan, in place of
+  // has_plan[a]; null = has_plan. (The own plan itself needs no field: `plans` is read for the instance's own record only — the
+  // neighbours come packed through `pos` / `bounds` — so the host points it at the override.) Null by default, like `range`.
+  const uint8_t* own_has = nullptr;
 };
 
 }  // namespace hdsm

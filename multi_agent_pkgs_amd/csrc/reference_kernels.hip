@@ -10,6 +10,7 @@
 #include "../../include/hdsm.h"
 #include "hdsm_core.h"
 #include "hdsm_entry.h"
+#include "link_core.h"
 #include "plan_pack.h"
 
 using namespace hdsm_entry;
@@ -36,6 +37,12 @@ struct RefArgs {
   const double* rpos;  // [n_rob][N + 1][3] positions of steps 0..N, packed (k_ref_pack)
   const double* rsph;  // [n_rob][4] enclosing sphere of those positions (radius < 0: no plan)
   const int32_t* range;  // neighbour groups (hdsm_set_groups): [.][2] id range per agent, null = [0, n_rob)
+  // stale plans, resolved by the host: where the instance's OWN plan and flag come from (hdsm_set_own_plans_device, else plans / has_plan)
+  // and the step shift of the neighbours' records (hdsm_set_plan_shift*, null = none) for the scan that reads them directly
+  const double* own_plans;
+  const uint8_t* own_has;
+  const int32_t* shift;
+  int32_t own_local;  // a shift or an override is set: rsph[self] is not the sphere of the instance's own plan (k_reference forms it)
   double wocc[hdsm::MAXH + 1];  // GetVelocityLimit's weight of step i (AC:1791-1795, 1805-1817): config only, evaluated by the host's libm
 };
 
@@ -45,11 +52,13 @@ struct RefArgs {
 // In the device-resident loop (one stream, same plans buffer for the reference and the solve of a round) this kernel also leaves
 // what k_plan_prepass would compute a few microseconds later from the same records — positions of steps 1..N (`pos`), their
 // bounding sphere (`bounds`, may be null), the launch order of the solve (one extra workgroup) — and the solve skips its pre-pass.
+// shift (null = none): record k is packed advanced by shift[k] steps, last state held (hdsm_link::shifted_step); the spheres are
+// those of the shifted positions.
 __global__ __launch_bounds__(256) void k_ref_pack(int N, int n_rob, const double* __restrict__ plans,
                                                    const uint8_t* __restrict__ has_plan, double* __restrict__ rpos,
                                                    double* __restrict__ rsph, double* __restrict__ pos, double* __restrict__ bounds,
                                                    int n_order, const int32_t* __restrict__ key_prev, const int32_t* __restrict__ agent_id,
-                                                   int32_t* __restrict__ order) {
+                                                   int32_t* __restrict__ order, const int32_t* __restrict__ shift) {
   if (order != nullptr && blockIdx.x == gridDim.x - 1) {
     launch_order_block(n_order, key_prev, agent_id, order);
     return;
@@ -58,6 +67,7 @@ __global__ __launch_bounds__(256) void k_ref_pack(int N, int n_rob, const double
   const int k = (int)blockIdx.x * 16 + (tid >> 4);
   const bool live = k < n_rob;
   const bool has = live && has_plan[k];
+  const int sk = (has && shift != nullptr) ? shift[k] : 0;
   double p[2][3] = {{0, 0, 0}, {0, 0, 0}};
   bool on[2];
 #pragma unroll
@@ -65,7 +75,7 @@ __global__ __launch_bounds__(256) void k_ref_pack(int N, int n_rob, const double
     const int st = i + 16 * u;
     on[u] = has && st <= N && (u == 0 || i == 0);
     if (on[u]) {
-      const double* rec = plans + ((int64_t)k * (N + 1) + st) * 9;
+      const double* rec = plans + ((int64_t)k * (N + 1) + hdsm_link::shifted_step(st, sk, N)) * 9;
       p[u][0] = rec[0], p[u][1] = rec[1], p[u][2] = rec[2];
     }
     if (live && st <= N && (u == 0 || i == 0)) {
@@ -107,7 +117,7 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   const int inst = blockIdx.x, tid = threadIdx.x, N = a.N;
   const int self = a.agent_id[inst];
   const int np = min(max(a.n_path[inst], 1), a.pmax);  // the host wrapper rejects counts outside [1, pmax]; device callers are clamped
-  const bool own_has = self >= 0 && self < a.n_rob && a.has_plan[self];
+  const bool own_has = self >= 0 && self < a.n_rob && a.own_has[self];
   // the ids the three neighbour scans below run over (the same for the whole workgroup: scalar loads, scalar loop bounds)
   int g_lo = 0, g_hi = a.n_rob;
   if (a.range != nullptr) {
@@ -122,7 +132,7 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
     for (int e = tid; e < np * 3; e += NT) spath[e] = pth_g[e];
   const double* pth = path_fits ? spath : pth_g;
   if (tid <= N) {
-    for (int c = 0; c < 3; ++c) own[tid][c] = own_has ? a.plans[((int64_t)self * (N + 1) + tid) * 9 + c] : 0.0;
+    for (int c = 0; c < 3; ++c) own[tid][c] = own_has ? a.own_plans[((int64_t)self * (N + 1) + tid) * 9 + c] : 0.0;
     wocc[tid] = a.wocc[tid];
   }
   __syncthreads();
@@ -135,7 +145,34 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   const bool monotone = a.cfg.sens_dist >= 0 && a.cfg.path_vel_max >= a.cfg.path_vel_min;
   if (own_has && np >= 2 && monotone) {
     // (1) the neighbour whose sphere is closest: its exact squared distances bound the minima from above
-    const double4 ss = *reinterpret_cast<const double4*>(a.rsph + (int64_t)self * 4);
+    double4 ss;
+    if (a.own_local) {
+      // Stale plans: rsph[self] is the sphere of the record the OTHERS read (shifted, or the stale copy of an own-plan override), not
+      // of the plan this instance flies. Wave 0 forms the own one from `own` (box centre, largest distance, as plan_sphere16 does;
+      // any sphere that holds the N + 1 points gives the same minima). A non-finite plan gets the never-culling radius.
+      if (tid < 64) {
+        const bool in = tid <= N;
+        double c3[3], r2 = 0.0;
+        for (int ax = 0; ax < 3; ++ax) {
+          const double v = in ? own[tid][ax] : 0.0;
+          const bool fin = v - v == 0.0;
+          const double lo = ref_wave_min((in && fin) ? v : DBL_MAX), hi = hdsm::wave_max64((in && fin) ? v : -DBL_MAX);
+          c3[ax] = 0.5 * (lo + hi);
+          r2 += fin ? (v - c3[ax]) * (v - c3[ax]) : DBL_MAX;
+        }
+        r2 = hdsm::wave_max64((in && r2 == r2) ? r2 : (in ? DBL_MAX : 0.0));
+        if (tid == 0) {
+          double w = sqrt(r2) * (1.0 + 1e-9);
+          if (!(w >= 0.0) || !(w < 1e299)) w = 1e300;
+          red[0] = c3[0], red[1] = c3[1], red[2] = c3[2], red[3] = w;
+        }
+      }
+      __syncthreads();
+      ss = double4{red[0], red[1], red[2], red[3]};
+      __syncthreads();  // (red is reused by the reductions below)
+    } else {
+      ss = *reinterpret_cast<const double4*>(a.rsph + (int64_t)self * 4);
+    }
     // Only a FINITE gap is a candidate (g < +inf, false for a NaN): the centre of a non-finite plan's sphere may be infinite (g = +inf)
     // or NaN (a plan with +inf and -inf on one axis). Taken as a lane's first candidate, a NaN lost to nobody, and every neighbour
     // the lane met after it was missing from the bound: with no other candidate the bound became 0 and neighbours whose sphere did
@@ -259,8 +296,10 @@ __global__ __launch_bounds__(NT) void k_reference(RefArgs a) {
   } else if (own_has && np >= 2) {  // (a configuration whose limit is not monotone in the distance: every pair is evaluated)
     for (int j = g_lo + tid; j < g_hi; j += NT) {
       if (j == self || !a.has_plan[j]) continue;
-      const double* rec = a.plans + (int64_t)j * (N + 1) * 9;
+      const double* rec0 = a.plans + (int64_t)j * (N + 1) * 9;
+      const int sj = a.shift != nullptr ? a.shift[j] : 0;
       for (int i = 0; i <= N; ++i) {
+        const double* rec = rec0 + 9 * (hdsm_link::shifted_step(i, sj, N) - i);  // (rec[9 i] is the neighbour's shifted step i)
         const double dx = own[i][0] - rec[9 * i], dy = own[i][1] - rec[9 * i + 1], dz = own[i][2] - rec[9 * i + 2];
         const double d = sqrt(dx * dx + dy * dy + dz * dz);
         const double alpha = (1 - wocc[i] * (1 / exp(a.cfg.sens_dist * d)));
@@ -353,6 +392,9 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
   a.has_plan = has_plan, a.ref_full = ref_full, a.ref = ref, a.path_vel = path_vel;
   hdsm_handle::Prepass& pp = h->pre;
   a.rpos = pp.d_rpos.get(), a.rsph = pp.d_rsph.get(), a.range = h->range();
+  a.own_plans = h->own_plans != nullptr ? h->own_plans : plans_all;
+  a.own_has = h->own_plans != nullptr && h->own_has != nullptr ? h->own_has : has_plan;
+  a.shift = h->shift, a.own_local = (h->shift != nullptr || h->own_plans != nullptr) ? 1 : 0;
   for (int i = 0; i <= hdsm::MAXH; ++i) {
     double occ = 100 * std::pow(cfg->sens_other_agents, (double)i);  // AC:1791-1795
     occ = occ < 0 ? 0 : (occ > 100 ? 100 : occ);
@@ -369,7 +411,7 @@ int hdsm_reference_device(void* handle, const hdsm_ref_config* cfg, int32_t n_in
     const bool pre = h->prefilter_agents(n_rob) >= h->bounds_min;
     hipLaunchKernelGGL(k_ref_pack, dim3((n_rob + 15) / 16 + (ordered ? 1 : 0)), dim3(256), 0, st, h->N, n_rob, plans_all, has_plan, pp.d_rpos.get(), pp.d_rsph.get(),
                        with_pre ? pp.d_pos.get() : nullptr, with_pre && pre ? pp.d_bounds.get() : nullptr, n_inst, h->d_stats.get() + 7 * h->max_inst, agent_id,
-                       ordered ? pp.d_order.get() : nullptr);
+                       ordered ? pp.d_order.get() : nullptr, h->shift);
     pp.plans = with_pre ? plans_all : nullptr, pp.n_rob = n_rob, pp.n_inst = n_inst, pp.ordered = ordered;
   }
   HIP_TRY(hipGetLastError());

@@ -20,6 +20,7 @@
 #include "../../include/hdsm_swarm.h"
 #include "audit_core.h"
 #include "hdsm_internal.h"
+#include "link_core.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -1013,6 +1014,15 @@ int hdsm_swarm_view(void* swarm, int32_t k, double* traj_curr, int32_t* n_traj, 
   if (pos)
     for (int c = 0; c < 3; ++c) pos[c] = ag.state_curr[c];
   return HDSM_OK;
+}
+
+// One link round of the device loop's per-sender link model on host arrays: the source k_deliver runs (link_core.h).
+int hdsm_link_deliver_host(int32_t n_slots, int32_t n_rob, int32_t n_hor, int32_t step_plan, int32_t n_rounds, const int8_t* fate,
+                           int32_t max_delay, int32_t time_aware, int32_t link_round, const double* truth, double* ring, double* seen,
+                           uint8_t* seen_has, int32_t* seen_round, int32_t* shift, int32_t* counters) {
+  const hdsm_link::Round a{n_slots, n_rob, n_hor, step_plan, n_rounds, max_delay, time_aware, link_round, fate, truth,
+                           ring,    seen,  seen_has, seen_round, shift,  counters};
+  return hdsm_link::deliver_round_host(a);
 }
 
 }  // extern "C"

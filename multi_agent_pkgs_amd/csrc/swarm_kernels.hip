@@ -28,6 +28,7 @@
 #include "audit_device.h"
 #include "device_mem.h"
 #include "hdsm_internal.h"
+#include "link_core.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -650,6 +651,28 @@ struct WorldEdits {
   DevBuf<unsigned long long> d_dropped;
 };
 
+// link faults (hdsm_dswarm_set_links; nothing is allocated or launched before the first call): the fate table, the ring of the last
+// rounds' published records ([MAX_DELAY + 1][G][rec], allocated once at the longest a table may ask for; D + 1 of them are in use),
+// the view the next round's reference and solve read in place of the plans buffer, and the per-slot counters
+struct Links {
+  bool on = false;
+  int n_rounds = 0, D = 0, time_aware = 0;
+  int round = 0;  // the link round the next k_deliver closes (0: the first round after hdsm_dswarm_set_links)
+  hdsm_mem::GrowBuf<int8_t> d_fate;
+  DevBuf<double> d_ring, d_seen;
+  DevBuf<uint8_t> d_seen_has;
+  DevBuf<int32_t> d_seen_round, d_shift, d_cnt;
+  bool ready() const { return (bool)d_cnt; }
+};
+
+// One link round (link_core.h, deliver_slot): a wavefront per slot of the plans buffer, four per workgroup. No LDS, no atomics: a
+// slot is touched by its own wavefront alone.
+__global__ __launch_bounds__(256) void k_deliver(hdsm_link::Round a) {
+  const int k = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (k >= a.G) return;
+  hdsm_link::deliver_slot(a, k, (int)threadIdx.x & 63, 64);
+}
+
 // ---- neighbour groups: the per-group flight summary (hdsm_dswarm_group_report) ----
 // One wavefront per group over the group's LOCAL agents [max(lo, first), min(hi, first + n_local)), 64 at a time; groups larger than
 // a wavefront loop. Every figure is an integer sum, a minimum or a maximum, reduced over the wave by butterflies: the result does not
@@ -732,6 +755,7 @@ struct DSwarm {
   Audit audit;
   History hist;
   WorldEdits edits;
+  Links links;
   // neighbour groups (taken from the mirror by hdsm_dswarm_create; one group = the whole swarm without a partition): the
   // partition, the id range per record of the plans buffer ([per * world][2], for the audit; null without a partition), the report
   std::vector<int32_t> group_start;
@@ -976,8 +1000,25 @@ int corridor_to_solve(DSwarm& d, hipStream_t st) {
     HIP_TRY(hipGetLastError());
   }
   PHASE_MARK(2);
+  // Link faults: the OTHER agents are read from the view k_deliver keeps (seen / seen_has, advanced by shift), every agent's own plan
+  // from the plans buffer, which stays the truth. The handle borrows the three arrays for the two launches of this round only.
+  const Links& lk = d.links;
+  const double* const plans = lk.on ? lk.d_seen.get() : d.d_plans.get();
+  const uint8_t* const has = lk.on ? lk.d_seen_has.get() : d.d_has.get();
+  struct Borrow {
+    void* solver;
+    bool on;
+    ~Borrow() {
+      if (on) (void)hdsm_set_plan_shift_device(solver, nullptr), (void)hdsm_set_own_plans_device(solver, nullptr, nullptr);
+    }
+  } borrow{d.solver, lk.on};
+  if (lk.on) {
+    int lrc = hdsm_set_plan_shift_device(d.solver, lk.d_shift.get());
+    if (lrc == HDSM_OK) lrc = hdsm_set_own_plans_device(d.solver, d.d_plans.get(), d.d_has.get());
+    if (lrc) return fail(lrc, std::string("link faults: ") + hdsm_last_error());
+  }
   int rc = hdsm_reference_device(d.solver, &d.rcfg, n, G, d.d_id.get(), d.d_path.get(), d.d_npath.get(), PTS, d.c.has_world ? d.d_cap.get() : nullptr,
-                                 d.d_plans.get(), d.d_has.get(), d.d_ref_full.get(), d.d_ref.get(), d.d_pv.get(), st);
+                                 plans, has, d.d_ref_full.get(), d.d_ref.get(), d.d_pv.get(), st);
   if (rc) return fail(rc, std::string("hdsm_reference_device: ") + hdsm_last_error());
   PHASE_MARK(3);
   if (d.c.has_world) {
@@ -987,7 +1028,7 @@ int corridor_to_solve(DSwarm& d, hipStream_t st) {
   }
   PHASE_MARK(4);
   rc = hdsm_replan_device(d.solver, n, G, d.d_id.get(), d.d_state.get(), d.d_ref.get(), d.d_npoly.get(), d.d_nrows.get(), d.d_A.get(), d.d_b.get(),
-                          d.d_plans.get(), d.d_has.get(), d.d_traj.get(), d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), d.d_obj.get(), st);
+                          plans, has, d.d_traj.get(), d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), d.d_obj.get(), st);
   if (rc) return fail(rc, std::string("hdsm_replan_device: ") + hdsm_last_error());
   return HDSM_OK;
 }
@@ -1028,6 +1069,22 @@ int exchange(DSwarm& d, void* comm, void* local, hipStream_t st) {
   return HDSM_OK;
 }
 #undef PHASE_MARK
+
+// link faults: the records the exchange has just left in the plans buffer meet their fates (k_deliver; only while links are on)
+hdsm_link::Round link_round(const DSwarm& d) {
+  const Links& l = d.links;
+  return hdsm_link::Round{d.per * d.world, d.n_rob, d.c.N, d.c.step_plan, l.n_rounds, l.D, l.time_aware, l.round, l.d_fate.get(), d.d_plans.get(),
+                          l.d_ring.get(), l.d_seen.get(), l.d_seen_has.get(), l.d_seen_round.get(), l.d_shift.get(), l.d_cnt.get()};
+}
+int deliver(DSwarm& d, hipStream_t st) {
+  Links& l = d.links;
+  const int G = d.per * d.world;
+  if (!l.on || G == 0) return HDSM_OK;
+  hipLaunchKernelGGL(k_deliver, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, st, link_round(d));
+  HIP_TRY(hipGetLastError());
+  ++l.round;
+  return HDSM_OK;
+}
 
 // the flight audit and the history row, on this round's records of all agents (only when one of them is on)
 int audit_and_history(DSwarm& d, hipStream_t st) {
@@ -1074,6 +1131,7 @@ int round_front(DSwarm& d, void* local, hipStream_t st) {
 }
 int round_back(DSwarm& d, void* comm, void* local, hipStream_t st) {
   if (int rc = exchange(d, comm, local, st)) return rc;
+  if (int rc = deliver(d, st)) return rc;
   if (int rc = audit_and_history(d, st)) return rc;
   if (d.phase_timing) d.phase_valid = true;
   ++d.rounds;
@@ -1307,6 +1365,79 @@ int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* co
     HIP_TRY(hipSetDevice(d->device));
     if (int rc = round_back(*d, comms[r], comms[r], static_cast<hipStream_t>(hip_streams ? hip_streams[r] : nullptr))) return rc;
   }
+  return HDSM_OK;
+}
+
+// Link faults (include/hdsm_swarm.h). The call starts a new link history: the view is the plans buffer as it stands (every slot
+// delivered on time, held round -1, shift 0), the counters are zero, link round 0 is the next round.
+int hdsm_dswarm_set_links(void* dswarm, int32_t n_rounds, const int8_t* fate, int32_t time_aware) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (n_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: negative n_rounds");
+  Links& l = d->links;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (n_rounds == 0 || fate == nullptr) {
+    l.on = false;
+    return HDSM_OK;
+  }
+  const int D = hdsm_link::table_max_delay(n_rounds, d->n_rob, fate);
+  if (D < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: a delay above HDSM_LINK_MAX_DELAY");
+  const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9, cells = (size_t)n_rounds * (size_t)d->n_rob;
+  l.on = false;
+  if (!l.ready()) {  // the first call: everything but the table, whose size is the caller's
+    hdsm_mem::FirstError ok;
+    ok(l.d_ring.alloc_zeroed((size_t)(hdsm_link::MAX_DELAY + 1) * G * rec)), ok(l.d_seen.alloc_zeroed(G * rec)), ok(l.d_seen_has.alloc_zeroed(G));
+    ok(l.d_seen_round.alloc(G)), ok(l.d_shift.alloc(G)), ok(l.d_cnt.alloc(G * hdsm_link::COUNTERS));
+    if (!ok.ok()) {
+      l.d_cnt.reset();
+      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_links: ") + hipGetErrorString(ok.e));
+    }
+  }
+  HIP_TRY(l.d_fate.ensure(cells, nullptr));
+  if (cells) HIP_TRY(hipMemcpy(l.d_fate.get(), fate, cells, hipMemcpyHostToDevice));
+  if (G) {
+    HIP_TRY(hipMemcpy(l.d_seen.get(), d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(l.d_seen_has.get(), d->d_has.get(), G, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemset(l.d_seen_round.get(), 0xff, G * sizeof(int32_t)));  // -1
+    HIP_TRY(hipMemset(l.d_shift.get(), 0, G * sizeof(int32_t)));
+    HIP_TRY(hipMemset(l.d_cnt.get(), 0, G * hdsm_link::COUNTERS * sizeof(int32_t)));
+  }
+  l.n_rounds = n_rounds, l.D = D, l.time_aware = time_aware != 0, l.round = 0, l.on = true;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_link_stats(void* dswarm, int64_t out[4]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!d->links.ready()) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t G = (size_t)d->per * d->world, have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;  // (the padded tail publishes nothing)
+  std::vector<int32_t> cnt(have * hdsm_link::COUNTERS + 1);
+  if (have) HIP_TRY(hipMemcpy(cnt.data(), d->links.d_cnt.get(), have * hdsm_link::COUNTERS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < have; ++k) {
+    const int32_t* c = &cnt[k * hdsm_link::COUNTERS];
+    out[1] += c[0], out[2] += c[1];
+    out[3] = c[2] > out[3] ? c[2] : out[3], out[0] = c[3] > out[0] ? c[3] : out[0];
+  }
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_seen(void* dswarm, double* seen_raw, uint8_t* seen_has, int32_t* seen_round, int32_t* shift) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (!d->links.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_download_seen: no hdsm_dswarm_set_links yet");
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const Links& l = d->links;
+  const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
+  if (G == 0) return HDSM_OK;
+  if (seen_raw) HIP_TRY(hipMemcpy(seen_raw, l.d_seen.get(), G * rec * 8, hipMemcpyDeviceToHost));
+  if (seen_has) HIP_TRY(hipMemcpy(seen_has, l.d_seen_has.get(), G, hipMemcpyDeviceToHost));
+  if (seen_round) HIP_TRY(hipMemcpy(seen_round, l.d_seen_round.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (shift) HIP_TRY(hipMemcpy(shift, l.d_shift.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
   return HDSM_OK;
 }
 

@@ -115,7 +115,7 @@ EXPORTS = tuple(SIGNATURES)
 # the functions that report their own name.
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
-              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_", "hdsm_last_error"))
+              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_", "hdsm_last_error"))
 
 _lib = None
 
@@ -293,6 +293,25 @@ class Solver:
         else:
             call("hdsm_set_groups", self.h, gs.size - 1, gs)
 
+    # ---- stale plans (include/hdsm.h) ----
+    def set_plan_shift(self, shift=None):
+        """hdsm_set_plan_shift: shift [n_rob] >= 0 — every instance but k's own reads record k advanced by shift[k] steps with its
+        last state held (values above n_hor behave as n_hor). None (or an empty list) clears it. Honoured by replan*, reference* and
+        tasc_planes. Synchronises the handle."""
+        sh = _i32([] if shift is None else shift)
+        call("hdsm_set_plan_shift", self.h, sh.size, sh if sh.size else None)
+
+    def set_plan_shift_device(self, d_shift=None):
+        """hdsm_set_plan_shift_device: a BORROWED int32 device tensor [n_rob], read by every later launch; None clears it. Keep the
+        tensor alive while it is set."""
+        call("hdsm_set_plan_shift_device", self.h, d_shift)
+
+    def set_own_plans_device(self, d_own_plans=None, d_own_has=None):
+        """hdsm_set_own_plans_device: BORROWED device tensors in the layouts of plans / has_plan; the instance of agent a takes its
+        own previous plan and flag from there instead of plans[a] / has_plan[a] (d_own_has None: the flag stays has_plan[a]). None
+        clears the override. Keep the tensors alive while they are set."""
+        call("hdsm_set_own_plans_device", self.h, d_own_plans, d_own_has)
+
     def reset_warm_start(self):
         call("hdsm_reset_warm_start", self.h)
 
@@ -447,6 +466,36 @@ def local_path_dmp_batch(world, ldim, off, ground_k, origin, start, goal, search
 def local_path_dmp_host(world, ldim, off, ground_k, origin, start, goal, search_rad=1.8, res=0.3, pmax=PATH_PTS):
     """hdsm_local_path_dmp_host: the same batch on the CPU (bit for bit what local_path_dmp_batch returns)."""
     return _local_path("hdsm_local_path_dmp_host", (), world, ldim, off, ground_k, origin, start, goal, res, pmax, search_rad=float(search_rad))
+
+
+LINK_MAX_DELAY = 7  # HDSM_LINK_MAX_DELAY (include/hdsm_swarm.h)
+
+
+class LinkView:
+    """The per-sender link model of the device loop on host arrays (hdsm_link_deliver_host, the source k_deliver runs): the ring of
+    the last max_delay + 1 rounds of published records and the view — seen, seen_has, seen_round, shift, counters [n_slots][4] —
+    starting, like hdsm_dswarm_set_links, from the records plans0 / has0 held at round -1. deliver(truth) is one link round."""
+
+    def __init__(self, fate, n_slots, n_hor, step_plan, time_aware, plans0, has0):
+        self.fate = _i8(fate)
+        assert self.fate.ndim == 2
+        self.n_rounds, self.n_rob = self.fate.shape
+        self.n_slots, self.n_hor, self.step_plan, self.time_aware = int(n_slots), int(n_hor), int(step_plan), 1 if time_aware else 0
+        self.max_delay = int(max(0, self.fate.max())) if self.fate.size else 0
+        self.ring = np.zeros((self.max_delay + 1, self.n_slots, n_hor + 1, 9))
+        self.seen = np.array(plans0, dtype=np.float64, order="C", copy=True).reshape(self.n_slots, n_hor + 1, 9)
+        self.seen_has = np.array(has0, dtype=np.uint8, order="C", copy=True).reshape(self.n_slots)
+        self.seen_round = np.full(self.n_slots, -1, np.int32)
+        self.shift = np.zeros(self.n_slots, np.int32)
+        self.counters = np.zeros((self.n_slots, 4), np.int32)
+        self.round = 0
+
+    def deliver(self, truth):
+        """One link round: truth [n_slots][n_hor+1][9] are the records published in it (raw: a NaN in front = no plan)."""
+        truth = _f64(truth).reshape(self.n_slots, self.n_hor + 1, 9)
+        call("hdsm_link_deliver_host", self.n_slots, self.n_rob, self.n_hor, self.step_plan, self.n_rounds, self.fate, self.max_delay,
+             self.time_aware, self.round, truth, self.ring, self.seen, self.seen_has, self.seen_round, self.shift, self.counters)
+        self.round += 1
 
 
 def _flight_audit(fn, lead, plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world, worigin, voxel_size):

@@ -50,6 +50,24 @@ def repeat_scenario(starts, goals, copies, offset=(0.0, 0.0, 0.0)):
     return np.tile(starts, (copies, 1)) + shift, np.tile(goals, (copies, 1)) + shift, (n * np.arange(copies + 1)).astype(np.int32)
 
 
+def link_table(n_rounds, n_rob, loss=0.0, delay_min=0, delay_max=0, seed=0, dark=()):
+    """A fate table for DeviceSwarm.set_links (hdsm_dswarm_set_links), int8 [n_rounds][n_rob], read cyclically by the flight: entry
+    (q, k) is the fate of the record agent k publishes in link round q — -1 lost for everyone, d >= 0 it arrives d rounds late.
+    Every entry is lost with probability `loss`, else its delay is uniform in delay_min..delay_max (at most 7), from numpy's
+    default_rng(seed). dark: (agent, first_round, last_round) outages, rounds inclusive — that agent's records of those rounds are
+    lost. The reference has no such model (its com_latency parameter is never read): this is the project's own, per sender."""
+    if not (0 <= delay_min <= delay_max <= 7) or not (0.0 <= loss <= 1.0) or n_rounds < 1 or n_rob < 1:
+        raise ValueError("link_table: need 0 <= delay_min <= delay_max <= 7, 0 <= loss <= 1, n_rounds >= 1, n_rob >= 1")
+    rng = np.random.default_rng(seed)
+    fate = rng.integers(delay_min, delay_max + 1, size=(n_rounds, n_rob)).astype(np.int8)
+    fate[rng.random((n_rounds, n_rob)) < loss] = -1
+    for agent, first, last in dark:
+        if not (0 <= agent < n_rob and 0 <= first <= last < n_rounds):
+            raise ValueError(f"link_table: outage {(agent, first, last)} outside the table")
+        fate[first:last + 1, agent] = -1
+    return fate
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

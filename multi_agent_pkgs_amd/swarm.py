@@ -413,6 +413,34 @@ class DeviceSwarm:
         updates, voxels, dropped, raw = self._counters("hdsm_dswarm_world_stats", 4)
         return {"updates": updates, "voxels": voxels, "dropped": dropped, "raw_resident": bool(raw)}
 
+    # ---- link faults (include/hdsm_swarm.h) ----
+    def set_links(self, fate=None, time_aware=True):
+        """hdsm_dswarm_set_links: fate int8 [n_rounds][n_rob] (scenarios.link_table), read cyclically — entry (q mod n_rounds, k) is
+        the fate of the record agent k publishes in link round q: < 0 lost for everyone, d in 0..7 it arrives d rounds late. Link
+        round 0 is the next round. time_aware: a stale record is read advanced by its age (else as it is, like the reference).
+        None (or an empty table) turns links off. Per sender: every receiver sees the same thing. Synchronises."""
+        if fate is None or np.size(fate) == 0:
+            call("hdsm_dswarm_set_links", self.h, 0, None, 0)
+            return
+        fate = _i8(fate)
+        if fate.ndim != 2 or fate.shape[1] != self.shard.n_rob:
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "set_links: a table [n_rounds][n_rob] expected")
+        call("hdsm_dswarm_set_links", self.h, fate.shape[0], fate, 1 if time_aware else 0)
+
+    def link_stats(self):
+        """hdsm_dswarm_link_stats: link rounds since set_links, records delivered into views, broadcasts lost, the largest age (in
+        rounds) any agent's slot reached. Synchronises."""
+        return dict(zip(("rounds", "delivered", "lost", "max_age"), self._counters("hdsm_dswarm_link_stats", 4)))
+
+    def download_seen(self):
+        """hdsm_dswarm_download_seen: the view the next round reads — (seen_raw [G][N+1][9] with the sentinel of a slot without a plan,
+        seen_has [G], seen_round [G] (-1: the view of the set_links call), shift [G]), G = world_size * per. Synchronises."""
+        N, G = self.shard.prm.n_hor, self.per * self.world_size
+        seen, has = np.zeros((G, N + 1, 9)), np.zeros(G, np.uint8)
+        seen_round, shift = np.zeros(G, np.int32), np.zeros(G, np.int32)
+        call("hdsm_dswarm_download_seen", self.h, seen, has, seen_round, shift)
+        return seen, has, seen_round, shift
+
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
         call("hdsm_dswarm_set_audit", self.h, 1 if on else 0, sep_warn)
