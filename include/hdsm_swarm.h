@@ -243,7 +243,8 @@ const char* hdsm_dswarm_last_error(void);
  * with timing on, hdsm_dswarm_round records HIP events on its stream between its launches; hdsm_dswarm_last_phase_ms waits for the
  * last timed round and returns milliseconds of [0] k_corridor (GenerateSafeCorridor, AC:1236-1447), [1] k_vel_cap (ComputePathVelocity's
  * voxel term, AC:1709-1766), [2] hdsm_reference_device (AC:1449-1553), [3] k_keep_free (AC:1665-1693), [4] hdsm_replan_device
- * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238), [6] the exchange (AC:610-677; one rank: nothing).
+ * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238; with scripted agents, below, k_script behind it), [6] the exchange
+ * (AC:610-677; one rank: nothing).
  * Every record is a barrier packet in front of the next launch: a timed round is a few microseconds longer than a plain one. */
 int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on);
 int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]);
@@ -456,6 +457,52 @@ int hdsm_dswarm_download_seen(void* dswarm, double* seen_raw, uint8_t* seen_has,
 int hdsm_link_deliver_host(int32_t n_slots, int32_t n_rob, int32_t n_hor, int32_t step_plan, int32_t n_rounds, const int8_t* fate,
                            int32_t max_delay, int32_t time_aware, int32_t link_round, const double* truth, double* ring, double* seen,
                            uint8_t* seen_has, int32_t* seen_round, int32_t* shift, int32_t* counters);
+
+/* ---- scripted agents in the device loop: movers and dropouts (no new ABI minor; discover by symbol) ------------------------------------
+ * At the solver's boundary a neighbour need not be a flown agent: any record of plans_all gets a separating plane, as whoever
+ * publishes on agent_<id>/traj_full does in the reference (AC:1113-1206). A SCRIPTED agent of the device loop is not planned for: it
+ * follows a track and publishes the record the track gives (csrc/script_core.h, one source for the host form and k_script).
+ *   track    n_knots >= 1 knots (t, x, y, z), t in seconds, finite and strictly increasing. S(tau) = (p, v, a): p_0 at rest for
+ *            tau <= t_0, p_last at rest for tau >= t_last, else on the segment t_j <= tau < t_{j+1}: w = (p_{j+1} - p_j) / (t_{j+1} - t_j),
+ *            p = p_j + (tau - t_j) w, v = w, a = 0 (at a knot the right-hand segment's slope).
+ *   record   in script round q (0 = the first round after the call) state i of the N + 1 has the time tau_i = (double)(q * step_plan + i)
+ *            * dt; tau = 0 is the start of the next round. predict = 0: states[i] = S(tau_i), the prediction is the truth.
+ *            predict = 1: S(tau_i) up to i = step_plan, then the state of i = step_plan continued at constant velocity
+ *            (p + ((double)(i - step_plan) * dt) v, v, a = 0) — what an observer without the track would broadcast. Either way the
+ *            first step_plan segments are the true motion, which is what the flight audit judges.
+ *   which    the LAST n_script ids of the shard's block. No kernel is re-indexed for it: the path step, the corridor, the reference
+ *            and the solve run on the n_local - n_script agents in front of them, k_commit pads the tail's slots, and k_script — one
+ *            wavefront per scripted agent, right behind k_commit on the same stream, inside entry [5] of the phase timing —
+ *            overwrites exactly those slots: of the plans buffer and the flags on a single rank without a local communicator, of the
+ *            send buffer otherwise (before the "published" event or the all-gather). It also writes the agent's traj_curr,
+ *            state_curr = states[step_plan], has_traj = 1, the status HDSM_OK and the goal (the last knot), so the history,
+ *            hdsm_dswarm_download, the audit (scripted agents are subjects and partners) and hdsm_dswarm_group_report need nothing
+ *            of their own. Everything behind the publish point treats the record like any other: the exchange and k_gather_local move
+ *            it, k_deliver applies its fate (a lost broadcast of a mover is a missed observation). Neighbour groups: a scripted
+ *            agent is a neighbour of the range that covers its id — with a partition on one rank only the last ranges can hold
+ *            movers; with local ranks every rank's block has a tail of its own. n_script = n_local is legal: the rank solves
+ *            nothing. The ellipsoid is hdsm_params' for everyone.
+ *   hdsm_dswarm_set_script    knots [n_script][n_knots][4] (host, copied). Synchronises, like hdsm_dswarm_set_goals. n_script may stay
+ *                             (the tracks are replaced, tau starts at 0 again) or grow — the dropout: the last agents stop being
+ *                             flown and go where their tracks say from the next round on. HDSM_ERR_BAD_ARG, before anything is
+ *                             touched: a shrinking n_script (a scripted agent has no planner state to resume from), n_script >
+ *                             n_local, n_knots outside 1..256, times that do not increase, a non-finite entry, predict outside {0, 1}.
+ *                             n_script = 0 on an unscripted dswarm is a no-op. Device memory is allocated by the first call that
+ *                             scripts somebody; a flight that never calls it allocates and launches nothing new. Scripting is NOT
+ *                             carried into the host mirror by hdsm_dswarm_download (the mirror receives the scripted agents' states as
+ *                             they stand and would plan for them): after a takeover the caller sets the script again.
+ *   hdsm_dswarm_script_stats  out[0] script rounds since the last hdsm_dswarm_set_script, out[1] n_script, out[2] launches of k_script
+ *                             since hdsm_dswarm_create. Host counters: it does not synchronise.
+ *   hdsm_script_records_host  the records [n_script][n_hor + 1][9] of script round `round` (0 .. 2^40), pure: no device, no state.
+ *   hdsm_script_records_batch the same through k_script on `device` (host pointers, copied in and out); the two agree bit for bit.
+ *                             Both: HDSM_ERR_BAD_ARG for the track refusals above, n_hor outside 1..HDSM_MAX_HOR, step_plan outside
+ *                             1..n_hor, dt not positive and finite. */
+int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, const double* knots, int32_t predict);
+int hdsm_dswarm_script_stats(void* dswarm, int64_t out[3]);
+int hdsm_script_records_host(int32_t n_script, int32_t n_knots, const double* knots, int32_t n_hor, int32_t step_plan, double dt,
+                             int32_t predict, int64_t round, double* records);
+int hdsm_script_records_batch(int32_t device, int32_t n_script, int32_t n_knots, const double* knots, int32_t n_hor, int32_t step_plan,
+                              double dt, int32_t predict, int64_t round, double* records);
 
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between

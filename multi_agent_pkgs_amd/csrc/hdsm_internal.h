@@ -57,6 +57,9 @@ int hdsm_internal_audit_args(int32_t n_rob, const double* plans_all, const uint8
 int hdsm_internal_audit_host_grouped(int32_t n_rob, const double* plans_all, const uint8_t* has_plan, int32_t n_hor, int32_t step_plan, int32_t first,
                                      int32_t n_local, double drone_radius, double drone_z_offset, const int8_t* world, const int32_t wdim[3],
                                      const double worigin[3], double voxel_size, const int32_t* range, hdsm_audit_round* out);
+// (script_host.cpp) the argument checks shared by hdsm_script_records_host / _batch
+int hdsm_internal_script_args(int32_t n_script, int32_t n_knots, const double* knots, int32_t n_hor, int32_t step_plan, double dt, int32_t predict,
+                              int64_t round, const double* records);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

@@ -7,6 +7,8 @@
 //   k_replan     planes + MIQP (the hot path)                                                   hdsm_replan_device
 //   k_commit     the new reference into the agent state, read-back, shift fallback, increment check, state advance, published
 //                record                                                                          one wavefront per agent
+//   k_script     (only with scripted agents, hdsm_dswarm_set_script) the records of the shard's scripted tail, over the slots
+//                k_commit has just padded (script_kernels.hip)                                   one wavefront per scripted agent
 //   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
 //                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
@@ -30,6 +32,7 @@
 #include "hdsm_internal.h"
 #include "link_core.h"
 #include "path_core.h"
+#include "script_device.h"
 #include "swarm_core.h"
 
 #ifdef CD_PROFILE
@@ -665,6 +668,16 @@ struct Links {
   bool ready() const { return (bool)d_cnt; }
 };
 
+// scripted agents (hdsm_dswarm_set_script; nothing is allocated or launched before the first call that scripts somebody): the LAST n
+// ids of the shard's block are not flown — every kernel in front of k_commit runs on the n_local - n agents before them — and k_script
+// publishes their records from the tracks ([n_local][MAX_KNOTS][4] on the device, allocated once; n x n_knots of them in use).
+struct Script {
+  int n = 0, n_knots = 0, predict = 0;
+  long long round = 0;  // the script round the next k_script publishes (0: the first round after hdsm_dswarm_set_script)
+  long long launches = 0;
+  DevBuf<double> d_knots;
+};
+
 // One link round (link_core.h, deliver_slot): a wavefront per slot of the plans buffer, four per workgroup. No LDS, no atomics: a
 // slot is touched by its own wavefront alone.
 __global__ __launch_bounds__(256) void k_deliver(hdsm_link::Round a) {
@@ -756,6 +769,8 @@ struct DSwarm {
   History hist;
   WorldEdits edits;
   Links links;
+  Script script;
+  int n_fly() const { return n_local - script.n; }  // the agents this shard plans for: all but its scripted tail
   // neighbour groups (taken from the mirror by hdsm_dswarm_create; one group = the whole swarm without a partition): the
   // partition, the id range per record of the plans buffer ([per * world][2], for the audit; null without a partition), the report
   std::vector<int32_t> group_start;
@@ -962,7 +977,11 @@ int hand_back(DSwarm& d, void* swarm) {
 int path_step(DSwarm& d, hipStream_t st) {
   PathStep& p = d.path;
   const bool all = p.period > 0 && p.round % p.period == 0;
-  const int n_plan = all ? d.n_local : p.n_due;
+  int n_plan = all ? d.n_fly() : p.n_due;
+  if (!all && d.script.n > 0) {  // (the list of the due agents ascends: the flown ones come first)
+    n_plan = 0;
+    for (int k = 0; k < d.n_fly(); ++k) n_plan += p.due[(size_t)k] != 0;
+  }
   p.timed.valid = false;
   if (n_plan > 0) {
     if (d.phase_timing) HIP_TRY(p.timed.record_start(st));
@@ -984,7 +1003,7 @@ int path_step(DSwarm& d, hipStream_t st) {
 
 // k_corridor, k_vel_cap, the reference, k_keep_free and the solve (marks 0 to 4)
 int corridor_to_solve(DSwarm& d, hipStream_t st) {
-  const int n = d.n_local, G = d.per * d.world;
+  const int n = d.n_fly(), G = d.per * d.world;
   PHASE_MARK(0);
   if (n == 0) {
     for (int k = 1; k <= 4; ++k) PHASE_MARK(k);
@@ -1043,10 +1062,19 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
   const bool direct = d.world == 1 && local == nullptr;
   if (local)
     if (int rc = hdsm_internal_local_commit_gate(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
-  hipLaunchKernelGGL(k_commit, dim3((unsigned)(d.per > 0 ? d.per : 1)), dim3(64), 0, st, d.c, d.n_local, d.per, d.d_agents.get(), d.d_traj.get(),
+  const int n_fly = d.n_fly();
+  hipLaunchKernelGGL(k_commit, dim3((unsigned)(d.per > 0 ? d.per : 1)), dim3(64), 0, st, d.c, n_fly, d.per, d.d_agents.get(), d.d_traj.get(),
                      d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), direct ? d.d_plans.get() : d.d_local.get(), d.d_fails.get(),
                      direct ? d.d_has.get() : nullptr, d.d_ref_full.get(), d.d_pv.get());
   HIP_TRY(hipGetLastError());
+  if (Script& s = d.script; s.n > 0) {  // the scripted tail, over the slots k_commit has just padded (and inside its phase [5])
+    const size_t rec = (size_t)(d.c.N + 1) * 9;
+    HIP_TRY(hdsm_script::launch(hdsm_script::Round{s.n, s.n_knots, d.c.N, d.c.step_plan, s.predict, s.round, d.prm.dt, s.d_knots.get(),
+                                                   (direct ? d.d_plans.get() : d.d_local.get()) + (size_t)n_fly * rec,
+                                                   direct ? d.d_has.get() + n_fly : nullptr, d.d_status.get() + n_fly, d.d_agents.get() + n_fly},
+                                st));
+    ++s.round, ++s.launches;
+  }
   if (local) {
     if (int rc = hdsm_internal_local_published(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
   } else {
@@ -1404,6 +1432,47 @@ int hdsm_dswarm_set_links(void* dswarm, int32_t n_rounds, const int8_t* fate, in
     HIP_TRY(hipMemset(l.d_cnt.get(), 0, G * hdsm_link::COUNTERS * sizeof(int32_t)));
   }
   l.n_rounds = n_rounds, l.D = D, l.time_aware = time_aware != 0, l.round = 0, l.on = true;
+  return HDSM_OK;
+}
+
+// Scripted agents (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, const double* knots, int32_t predict) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  Script& s = d->script;
+  if (n_script < s.n) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: n_script may stay or grow (a scripted agent has no planner state to resume from)");
+  if (n_script > d->n_local) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: more scripted agents than the shard has");
+  if (predict != 0 && predict != 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: predict is 0 or 1");
+  if (!hdsm_script::tracks_valid(n_script, n_knots, knots))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: 1 .. 256 knots per track, every entry finite, times strictly increasing");
+  if (n_script == 0) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!s.d_knots) HIP_TRY(s.d_knots.alloc((size_t)d->n_local * hdsm_script::MAX_KNOTS * 4));
+  HIP_TRY(hipMemcpy(s.d_knots.get(), knots, (size_t)n_script * n_knots * 4 * sizeof(double), hipMemcpyHostToDevice));
+  // a scripted agent's goal is its last knot, and it plans no path: the flown agents that are due stay due
+  PathStep& p = d->path;
+  const int n_fly = d->n_local - n_script;
+  std::vector<int32_t> idx;
+  for (int k = 0; k < d->n_local; ++k) {
+    if (k >= n_fly) {
+      const double* last = knots + ((size_t)(k - n_fly) * n_knots + (n_knots - 1)) * 4;
+      for (int q = 0; q < 3; ++q) p.goals[3 * (size_t)k + q] = last[1 + q];
+      p.due[(size_t)k] = 0;
+    }
+    if (p.due[(size_t)k]) idx.push_back(k);
+  }
+  p.n_due = (int)idx.size();
+  HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), p.goals.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  s.n = n_script, s.n_knots = n_knots, s.predict = predict, s.round = 0;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_script_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->script.round, out[1] = d->script.n, out[2] = d->script.launches;
   return HDSM_OK;
 }
 

@@ -68,7 +68,7 @@ class ArrayPtr:
         return C.c_void_p.from_param(a)
 
 
-CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "double": C.c_double, "size_t": C.c_size_t, "void*": C.c_void_p,
+CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double, "size_t": C.c_size_t, "void*": C.c_void_p,
           "void**": C.POINTER(C.c_void_p), "char*": C.c_char_p}
 CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32_t", np.int32), ("int8_t", np.int8), ("uint8_t", np.uint8),
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
@@ -115,7 +115,7 @@ EXPORTS = tuple(SIGNATURES)
 # the functions that report their own name.
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
-              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_", "hdsm_last_error"))
+              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_", "hdsm_last_error"))
 
 _lib = None
 
@@ -496,6 +496,28 @@ class LinkView:
         call("hdsm_link_deliver_host", self.n_slots, self.n_rob, self.n_hor, self.step_plan, self.n_rounds, self.fate, self.max_delay,
              self.time_aware, self.round, truth, self.ring, self.seen, self.seen_has, self.seen_round, self.shift, self.counters)
         self.round += 1
+
+
+def _tracks(knots):
+    """knots [n_script][n_knots][4] (a single track [n_knots][4] is one agent's) as a contiguous float64 array"""
+    knots = _f64(knots)
+    if knots.ndim == 2:
+        knots = knots[None]
+    if knots.ndim != 3 or knots.shape[2] != 4:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "tracks [n_script][n_knots][4] of (t, x, y, z) expected")
+    return _f64(knots)
+
+
+def script_records(knots, n_hor, step_plan=1, dt=0.1, predict=0, round=0, device=None):
+    """hdsm_script_records_host: the records [n_script][n_hor+1][9] scripted agents on the tracks knots [n_script][n_knots][4] of
+    (t, x, y, z) publish in script round `round` (csrc/script_core.h: piecewise linear between the knots, at rest before the first
+    and after the last; predict=1: beyond state step_plan the state continues at constant velocity). device given:
+    hdsm_script_records_batch, the same through k_script on that device, bit for bit."""
+    knots = _tracks(knots)
+    records = np.zeros((knots.shape[0], int(n_hor) + 1, 9))
+    lead, fn = ((), "hdsm_script_records_host") if device is None else ((int(device),), "hdsm_script_records_batch")
+    call(fn, *lead, knots.shape[0], knots.shape[1], knots, int(n_hor), int(step_plan), float(dt), int(predict), int(round), records)
+    return records
 
 
 def _flight_audit(fn, lead, plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world, worigin, voxel_size):

@@ -68,6 +68,36 @@ def link_table(n_rounds, n_rob, loss=0.0, delay_min=0, delay_max=0, seed=0, dark
     return fate
 
 
+def hold_track(p):
+    """The track of a scripted agent (DeviceSwarm.set_script) that stays at p: one knot, float64 [1][4] = (t, x, y, z)."""
+    p = np.asarray(p, dtype=np.float64).reshape(3)
+    return np.array([[0.0, p[0], p[1], p[2]]])
+
+
+def line_track(p0, p1, speed, t0=0.0):
+    """The track of a scripted agent that waits at p0 until t0, flies to p1 at `speed` m/s and stays there: two knots, float64
+    [2][4] = (t, x, y, z). The project's own scenario class (the reference has no scripted vehicles)."""
+    p0, p1 = np.asarray(p0, dtype=np.float64).reshape(3), np.asarray(p1, dtype=np.float64).reshape(3)
+    dist = float(np.linalg.norm(p1 - p0))
+    if not (speed > 0) or not (dist > 0):
+        raise ValueError("line_track: need speed > 0 and p1 != p0 (hold_track stays in place)")
+    return np.array([[t0, *p0], [t0 + dist / speed, *p1]])
+
+
+def stack_tracks(*tracks):
+    """Tracks of different lengths as one array [n_script][n_knots][4] for DeviceSwarm.set_script, which takes one knot count for
+    all: a shorter track is continued with copies of its last position, one second apart — the same states (behind its last knot a
+    track rests there anyway)."""
+    tracks = [np.asarray(t, dtype=np.float64).reshape(-1, 4) for t in tracks]
+    n = max(t.shape[0] for t in tracks)
+    out = np.zeros((len(tracks), n, 4))
+    for k, t in enumerate(tracks):
+        out[k, :t.shape[0]] = t
+        out[k, t.shape[0]:] = t[-1]
+        out[k, t.shape[0]:, 0] = t[-1, 0] + np.arange(1, n - t.shape[0] + 1)
+    return out
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

@@ -441,6 +441,19 @@ class DeviceSwarm:
         call("hdsm_dswarm_download_seen", self.h, seen, has, seen_round, shift)
         return seen, has, seen_round, shift
 
+    # ---- scripted agents (include/hdsm_swarm.h) ----
+    def set_script(self, knots, predict=0):
+        """hdsm_dswarm_set_script: the LAST n_script agents of the shard follow the tracks knots [n_script][n_knots][4] of (t, x, y, z)
+        (scenarios.hold_track / line_track; tau = 0 is the start of the next round) instead of being planned for, and publish the
+        records of lib.script_records; predict=1: beyond the round's end the record continues at constant velocity. n_script may
+        stay (new tracks) or grow (a dropout), never shrink. Synchronises."""
+        knots = _lib._tracks(knots)
+        call("hdsm_dswarm_set_script", self.h, knots.shape[0], knots.shape[1], knots, int(predict))
+
+    def script_stats(self):
+        """hdsm_dswarm_script_stats: script rounds since the last set_script, scripted agents, launches of k_script."""
+        return dict(zip(("rounds", "n_script", "launches"), self._counters("hdsm_dswarm_script_stats", 3)))
+
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
         call("hdsm_dswarm_set_audit", self.h, 1 if on else 0, sep_warn)
