@@ -173,6 +173,14 @@ __device__ __forceinline__ void keep_here(double& v) {
 #endif
 }
 
+__device__ __forceinline__ void keep_here(float& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#else
+  (void)v;
+#endif
+}
+
 // ... and the same for a pointer
 template <class T>
 __device__ __forceinline__ T* keep_in_loop(T* p) {
@@ -343,7 +351,11 @@ struct WaveGI {
       const bool on = lane + 64 * e < n_sb;
       R.sb_id[e] = on ? ((q.ii[e] << 5) | (q.comp[e] << 3) | (q.axs[e] << 1)) : -1;
       R.sb_w[e] = (float)q.sb_w[e];
+      if constexpr (SPLIT) keep_here(R.sb_w[e]), keep_in_loop(R.sb_id[e]);
     }
+    // (formed HERE: the conversions used to sink to the first scan, and the doubles and index triples of the request — fourteen
+    // registers against five — stayed alive across the warm start, where they were spilled once it kept a few values of its own)
+    if constexpr (SPLIT) keep_here(R.wu);
   }
 
   // trajectory from s.x: lane (ax, m-1) evaluates p, v, a of step m (zero-padded Toeplitz table gz in LDS)
@@ -815,6 +827,9 @@ struct WaveGI {
   //      t = U^T v,   lambda = U t,   x_W = x0 + J1 t,   f_W = f(x0) + |t|^2 / 2        (v = violations at x0)
   // and entries with a negative multiplier are dropped until (x_W, W) is a valid S-pair. The regular loop then
   // continues from there; the result is the same optimum, reached in fewer iterations.
+  // NV = 32: t is kept while the rows go in (R^T is lower triangular: a new row adds one entry), which gives every row
+  // the multiplier it would get on the set as it stands BEFORE it is installed — a row that would come in with a
+  // negative one is left out, and the closed form above starts at lambda = U t.
   // size of a snapshot of the solver state (hdsm_wave_gib.h writes it: J slots, U rows, multipliers, ids, x, f, q)
   static constexpr int SNAP_DOUBLES = (2 * NV + 3) * NV + 2;
 };

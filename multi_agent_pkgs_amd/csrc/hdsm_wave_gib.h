@@ -22,10 +22,24 @@
 //     for a drop) gathered from its column-distributed form, so column q (or t) needs no special treatment and no register of
 //     J is ever addressed by a run-time index (the old layout paid a 16-deep select chain per access).
 //
+// Warm start (warm_start below; NV = 32): the trajectory at x0 and the violations of the guessed rows are formed in front of the
+// install loop, t (R^T t = v) is carried through it in position layout, and a row is probed before it is installed — its multiplier
+// on the set as it stands is (v_g - sum_{pos < q} d_pos t_pos) / rho^2; an inequality that would come in negative is left out.
+//
 // Everything that does not touch J's layout (state evaluation, violation scan, helper waves, neighbour sweep, residuals) is
 // inherited from WaveGI<NV, CMAX>. NV = 48 (H > 10): the same source with one lane per row and three blocks of slots (below).
 #pragma once
 #include "hdsm_wave_gi.h"
+
+// What the warm start does with the rows of a guess, for the CPU execution of this source (tests/warm_probe_emu defines the two
+// hooks and counts); everywhere else they are empty. HDSM_WARM_AUDIT_CHECK(probe, full) also makes the install loop form the
+// multiplier of every accepted row the long way (t = U^T v, lambda = U t on the set as it stands) next to the probe's.
+#ifndef HDSM_WARM_AUDIT
+#define HDSM_WARM_AUDIT(event)
+#endif
+namespace hdsm {
+enum WarmEvent { WARM_EV_REJECT = 0, WARM_EV_ACCEPT, WARM_EV_DROP_NEW, WARM_EV_DROP_OLD, WARM_EV_BOX_ROW, WARM_EV_COUNT };
+}
 
 namespace hdsm {
 
@@ -156,6 +170,22 @@ struct WaveGIB : WaveGI<NVT, CMAX, SMALL> {
       r0 += u.x * d.x, r1 += u.y * d.y;
     }
     return psum(r0 + r1);
+  }
+
+  // t = U^T v, both in position layout: column pos of U, this lane's share of the rows (rows >= q of U are zero), halves summed
+  static __device__ __forceinline__ double ut_dot(S& s, double vk, int lane) {
+    const int pos = pos_of(lane), pa = pos_addr(lane), c0 = ucol0(lane);
+    if (first_copy(lane)) s.dvec[pos] = vk;
+    wsync();
+    double p0 = 0, p1 = 0;
+#pragma unroll
+    for (int k = 0; k < NC; k += 2) {
+      const D2 vk2 = *reinterpret_cast<const D2*>(&s.dvec[c0 + k]);
+      p0 += s.U[(c0 + k) * LDT + pa] * vk2.x, p1 += s.U[(c0 + k + 1) * LDT + pa] * vk2.y;
+    }
+    const double tj = psum(p0 + p1);
+    wsync();  // (the caller may write s.dvec again)
+    return tj;
   }
 
   // ---- hand-over between wave 0 and the scanner (wave 1): workgroup barriers with a command word. (Words in LDS polled by the
@@ -320,72 +350,20 @@ struct WaveGIB : WaveGI<NVT, CMAX, SMALL> {
   // closed form  t = U^T v, lambda = U t, x_W = x0 + J1 t, f_W = f(x0) + |t|^2 / 2
   using WarmPre = typename Base::WarmPre;
   using Base::warm_prefetch;
-  // `conc`: wave 1 sweeps the neighbour rows while this wave installs the guess (hdsm_core.h): ONE workgroup barrier, on every path,
-  // right after the rows of the guess have taken their staging slots — from there on this function no longer touches the counters
-  // of the staging area, and the sweep may add its rows behind them.
-  static __device__ __forceinline__ void warm_start(S& s, const Consts& c, const Args& a, Regs& R, int inst, int self, int& iters,
-                                                    const WarmPre& wpre, bool conc = false) {
-    const int lane = (int)HDSM_TX;
-    const int N = c.N, n = c.n;
-    int nw = uni(wpre.head) & ~WARM_CERT;
-    if (nw <= 0) {
-      if (conc) {
-        if (lane == 0) s.warm_ncand = s.ncand;
-        __syncthreads();
-      }
-      return;
-    }
-    if (nw > NV) nw = NV;
+  // WARM_PROBE: the trajectory at x0 in front of the install loop, t carried through it, a row tested before it is installed, the
+  // fix-up without its first evaluation. NV = 32 only: the kernels of the larger factor fill the register file (256 + 256, J in the
+  // accumulation half) and spill with the few values this keeps across the loop; they install every independent row and let the
+  // fix-up sort them out, as both layouts did before.
+  // (One body for both, the probe's pieces under `if constexpr (WARM_PROBE)` and the fix-up told whether t is there, was built
+  // first: with WARM_PROBE = false the NV = 48 kernels still came out with 120-132 B of scratch per lane, 112-124 B with the probe
+  // on — the parent's text as a function of its own, install_plain, is what gives them 0. Hence two copies of the fix-up.)
+  static constexpr bool WARM_PROBE = SPLIT;
+  // The install loop and the fix-up as NV = 48 runs them (WARM_PROBE = false): every independent row of the guess is installed, the
+  // trajectory at x0 and t = U^T v are formed afterwards, and the fix-up drops what came in with a negative multiplier.
+  static __device__ __forceinline__ void install_plain(S& s, const Consts& c, Regs& R, int lane, int nw, int pre, const double (&my_row)[4],
+                                                       int q, int& iters) {
+    const int N = c.N, n = c.n, q_in = q;
     PROF_DECL
-    int pre = -1, my_m = 0, my_src = 0;  // pre: >= 0 a ready id, -2 a neighbour row held in my_row, -1 nothing usable
-    double my_row[4] = {0.0, 0.0, 0.0, 0.0};
-    if (lane < nw) {
-      const int code = wpre.code;
-      const int kind = id_kind(code), p = id_payload(code);
-      if (kind == K_U) {
-        const int var = p >> 1;
-        if (var % N >= 1) pre = mk_id(K_U, ((var - 1) << 1) | (p & 1));
-      } else if (kind == K_S) {
-        const int i = p >> 5;
-        if (i - 1 >= 1) pre = mk_id(K_S, ((i - 1) << 5) | (p & 31));
-      } else if (kind == K_C && a.l1_rows == nullptr) {
-        const int e = p & 1, i = ((p >> 1) & 31) - 1, k = p >> 6;
-        // (k inside the instance's neighbour range — [0, n_rob) without a partition: a guess kept from before hdsm_set_groups may name others)
-        if (i >= 0 && i + e > c.pinned_steps && k != self && k >= s.grp[0] && k < s.grp[1] && wpre.has) {
-          const double op[3] = {wpre.ox, wpre.oy, wpre.oz};
-          if (tasc_plane_eval(c, s.cprev[i], op, my_row)) pre = -2, my_m = i + e, my_src = (k << 6) | (i << 1) | e;
-        }
-      }
-    }
-    int q = uni(s.q);
-    const int q_in = q;
-    load_pos(s, R, lane);
-    {  // the neighbour rows of the guess go into the staging area in ONE step: every lane that holds one takes the next free slot
-      const unsigned long long want = __ballot(pre == -2);
-      if (want != 0ull) {
-        const int base = uni(s.ncand), room = CMAX - uni(s.ncold) - base;
-        const int rank = __popcll(want & ((1ull << lane) - 1ull));
-        if (pre == -2) {
-          if (rank < room) {
-            const int slot = base + rank;
-            s.cand[slot][0] = my_row[0], s.cand[slot][1] = my_row[1], s.cand[slot][2] = my_row[2], s.cand[slot][3] = my_row[3];
-            s.cand_mw[slot] = mk_mw(s.kap, my_row[0], my_row[1], my_row[2], my_m);
-            s.cand_src[slot] = my_src;
-            pre = mk_kc(slot, my_m);
-          } else {
-            pre = -1;
-          }
-        }
-        const int cnt = __popcll(want);
-        if (lane == 0) s.ncand = base + (cnt < room ? cnt : (room > 0 ? room : 0));
-        wsync();
-      }
-    }
-    if (conc) {
-      if (lane == 0) s.warm_ncand = s.ncand;
-      __syncthreads();
-    }
-    WS_PROF(16)
     for (int g = 0; g < nw && q < n; ++g) {
       const int id = __builtin_amdgcn_readlane(pre, g);
       if (id < 0) continue;
@@ -459,6 +437,181 @@ struct WaveGIB : WaveGI<NVT, CMAX, SMALL> {
       }
       const int l = pos_of(uni(__ffsll((long long)__ballot(ineq && lk == worst)) - 1));
       WS_PROF(21)
+      drop(s, R, l, q, lane);
+      WS_PROF(22)
+      --q;
+      ++iters;
+    }
+  }
+
+  // `conc`: wave 1 sweeps the neighbour rows while this wave installs the guess (hdsm_core.h): ONE workgroup barrier, on every path,
+  // right after the rows of the guess have taken their staging slots — from there on this function no longer touches the counters
+  // of the staging area, and the sweep may add its rows behind them.
+  static __device__ __forceinline__ void warm_start(S& s, const Consts& c, const Args& a, Regs& R, int inst, int self, int& iters,
+                                                    const WarmPre& wpre, bool conc = false) {
+    const int lane = (int)HDSM_TX;
+    const int N = c.N, n = c.n;
+    int nw = uni(wpre.head) & ~WARM_CERT;
+    if (nw <= 0) {
+      if (conc) {
+        if (lane == 0) s.warm_ncand = s.ncand;
+        __syncthreads();
+      }
+      return;
+    }
+    if (nw > NV) nw = NV;
+    PROF_DECL
+    int pre = -1, my_m = 0, my_src = 0;  // pre: >= 0 a ready id, -2 a neighbour row held in my_row, -1 nothing usable
+    double my_row[4] = {0.0, 0.0, 0.0, 0.0};
+    if (lane < nw) {
+      const int code = wpre.code;
+      const int kind = id_kind(code), p = id_payload(code);
+      if (kind == K_U) {
+        const int var = p >> 1;
+        if (var % N >= 1) pre = mk_id(K_U, ((var - 1) << 1) | (p & 1));
+      } else if (kind == K_S) {
+        const int i = p >> 5;
+        if (i - 1 >= 1) pre = mk_id(K_S, ((i - 1) << 5) | (p & 31));
+      } else if (kind == K_C && a.l1_rows == nullptr) {
+        const int e = p & 1, i = ((p >> 1) & 31) - 1, k = p >> 6;
+        // (k inside the instance's neighbour range — [0, n_rob) without a partition: a guess kept from before hdsm_set_groups may name others)
+        if (i >= 0 && i + e > c.pinned_steps && k != self && k >= s.grp[0] && k < s.grp[1] && wpre.has) {
+          const double op[3] = {wpre.ox, wpre.oy, wpre.oz};
+          if (tasc_plane_eval(c, s.cprev[i], op, my_row)) pre = -2, my_m = i + e, my_src = (k << 6) | (i << 1) | e;
+        }
+      }
+    }
+    int q = uni(s.q);
+    const int q_in = q;
+    load_pos(s, R, lane);
+    {  // the neighbour rows of the guess go into the staging area in ONE step: every lane that holds one takes the next free slot
+      const unsigned long long want = __ballot(pre == -2);
+      if (want != 0ull) {
+        const int base = uni(s.ncand), room = CMAX - uni(s.ncold) - base;
+        const int rank = __popcll(want & ((1ull << lane) - 1ull));
+        if (pre == -2) {
+          if (rank < room) {
+            const int slot = base + rank;
+            s.cand[slot][0] = my_row[0], s.cand[slot][1] = my_row[1], s.cand[slot][2] = my_row[2], s.cand[slot][3] = my_row[3];
+            s.cand_mw[slot] = mk_mw(s.kap, my_row[0], my_row[1], my_row[2], my_m);
+            s.cand_src[slot] = my_src;
+            pre = mk_kc(slot, my_m);
+          } else {
+            pre = -1;
+          }
+        }
+        const int cnt = __popcll(want);
+        if (lane == 0) s.ncand = base + (cnt < room ? cnt : (room > 0 ? room : 0));
+        wsync();
+      }
+    }
+    if (conc) {
+      if (lane == 0) s.warm_ncand = s.ncand;
+      __syncthreads();
+    }
+    WS_PROF(16)
+    if constexpr (!WARM_PROBE) {
+      install_plain(s, c, R, lane, nw, pre, my_row, q, iters);
+      return;
+    }
+    // trajectory at the unconstrained minimiser x0 and the violation there of every row of the guess, BEFORE the install loop: each
+    // lane evaluates the row it holds (one pass, all rows at once) and leaves the value in Shm::w (free between the set-up and the
+    // first run), entry g for row g of the guess. (R.xi is the iterate of the set-up, s.x[lane]: it is put back if nothing is installed.)
+    const int pos = pos_of(lane);
+    if (lane < NV) s.x[lane] = s.x0[lane];
+    wsync();
+    Base::states(s, R, lane, N);
+    if (pre >= 0) s.w[lane] = Base::resid(s, c, pre, N);
+    if (pre >= 0 && id_kind(pre) != K_C) { HDSM_WARM_AUDIT(WARM_EV_BOX_ROW) }
+    // t = U^T v of the rows that are in already (the equalities): the solution of R^T t = v, kept in position layout and extended by
+    // one entry per installed row (R^T is lower triangular: the entries before it do not change)
+    double tj = ut_dot(s, (pos < q) ? Base::resid(s, c, R.act, N) : 0.0, lane);
+    for (int g = 0; g < nw && q < n; ++g) {
+      const int id = __builtin_amdgcn_readlane(pre, g);
+      if (id < 0) continue;
+      WS_PROF(17)
+      const double vg = s.w[g];  // (asked for here, used by the probe: behind the direction)
+      double ai;
+      if (id_kind(id) == K_C) {  // the row is in lane g's registers: its normal needs one LDS read (the impulse response), not two in a chain
+        const double nx = bcast64(my_row[0], g), ny = bcast64(my_row[1], g), nz = bcast64(my_row[2], g);
+        const int m = kc_m(id_payload(id)), var = Base::row_of(lane);
+        const double nax = R.ax == 0 ? nx : (R.ax == 1 ? ny : nz);
+        ai = (var < n && R.kk < m) ? nax * s.gz[R.ax][0][MAXH + m - 1 - R.kk] : 0.0;
+      } else {
+        ai = Base::normal_entry(s, R, id, Base::row_of(lane), N, n);
+      }
+      WS_PROF(18)
+      double dj, dz, dd, zz, dq, zi, ri;
+      direction<false>(s, R, ai, q, lane, dj, dz, dd, zz, dq, zi, ri);
+      WS_PROF(19)
+      ++iters;
+      // The probe: column q of R would be (d_0 .. d_{q-1}, rho), so row q of R^T t = v gives the new entry of t, and the row's
+      // multiplier on the set as it stands is lambda_q = t_q / rho — what the fix-up's lambda = U t would find for it. A row
+      // that would come in with a negative multiplier is not installed: the fix-up would only throw it out again.
+      // (rho^2 = ||d2||^2 = zz: the test needs no reflection scalars — a rejected row stops here)
+      const double num = vg - pos_sum(pos < q ? dj * tj : 0.0, lane);
+      // (one way out of the iteration for both tests: with a second one the compiler kept two copies of J around the loop)
+      if (!(zz > 1e-8 * dd) || (id_kind(id) != K_E && num < -1e-12 * zz)) {  // (nearly) dependent on what is already in, or not wanted
+        if (zz > 1e-8 * dd) { HDSM_WARM_AUDIT(WARM_EV_REJECT) }
+        continue;
+      }
+      const Refl refl = reflection(zz, dq);
+      const double tq = num * refl.inv_rho;
+      householder_add(s, R, id, 0.0, q, lane, dz, zz, dq, ri, &refl);
+      if (pos == q) tj = tq;
+      WS_PROF(20)
+      ++q;
+      HDSM_WARM_AUDIT(WARM_EV_ACCEPT)
+#ifdef HDSM_WARM_AUDIT_CHECK
+      {  // (CPU execution only) the multiplier the fix-up's full evaluation gives the row just installed, against the probe's
+        const double tf = ut_dot(s, (pos < q) ? Base::resid(s, c, R.act, N) : 0.0, lane);
+        if (first_copy(lane)) s.dvec[pos] = tf;
+        wsync();
+        const double lf = u_row_dot(s, lane);
+        if (lane == lane_of_pos(q - 1)) { HDSM_WARM_AUDIT_CHECK(tq * refl.inv_rho, lf) }
+        wsync();
+      }
+#endif
+    }
+    if (q == q_in) {  // nothing usable (multipliers / ids in LDS are untouched)
+      if (lane < NV) s.x[lane] = R.xi;
+      wsync();
+      return;
+    }
+    store_pos(s, R, lane);  // resid() of K_P rows and the hand-over read act[] from LDS
+    wsync();
+    for (bool first = true;; first = false) {
+      // (first pass: t came out of the install loop; after a drop the violations at x0 and t = U^T v are formed again)
+      if (!first) tj = ut_dot(s, (pos < q) ? Base::resid(s, c, R.act, N) : 0.0, lane);
+      if (first_copy(lane)) s.dvec[pos] = tj;
+      wsync();
+      const double lk = u_row_dot(s, lane);  // lambda = U t
+      // most negative multiplier among the inequalities
+      const bool ineq = pos < q && id_kind(R.act) != K_E;
+      const double worst = -wave_max64(ineq ? -lk : -DINF);
+      if (!(worst < -1e-12) || q <= 6) {
+        double xw;  // x_W = x0 + J1 t (t is zero beyond q): only the pair that is kept needs it
+        {
+          double g[NC];
+          gather_cols(tj, g);
+          double x0 = 0, x1 = 0;
+#pragma unroll
+          for (int k = 0; k < NC; k += 2) x0 += R.Jr[k] * g[k], x1 += R.Jr[k + 1] * g[k + 1];
+          xw = s.x0[row_addr(lane)] + Base::hsum(x0 + x1);
+        }
+        const double tt = pos_sum(tj * tj, lane);
+        R.lam = (pos < q) ? lk : 0.0;
+        if (lane < n) R.xi = xw, s.x[lane] = xw;
+        else if (lane < 64 && Base::row_ok(lane) && Base::row_of(lane) < n) R.xi = xw;
+        if (lane == 0) s.f = s.fx0 + 0.5 * tt, s.q = q;
+        store_pos(s, R, lane);
+        wsync();
+        WS_PROF(21)
+        return;
+      }
+      const int l = pos_of(uni(__ffsll((long long)__ballot(ineq && lk == worst)) - 1));
+      WS_PROF(21)
+      HDSM_WARM_AUDIT(l >= q_in ? WARM_EV_DROP_NEW : WARM_EV_DROP_OLD)
       drop(s, R, l, q, lane);
       WS_PROF(22)
       --q;
