@@ -243,7 +243,7 @@ const char* hdsm_dswarm_last_error(void);
  * with timing on, hdsm_dswarm_round records HIP events on its stream between its launches; hdsm_dswarm_last_phase_ms waits for the
  * last timed round and returns milliseconds of [0] k_corridor (GenerateSafeCorridor, AC:1236-1447), [1] k_vel_cap (ComputePathVelocity's
  * voxel term, AC:1709-1766), [2] hdsm_reference_device (AC:1449-1553), [3] k_keep_free (AC:1665-1693), [4] hdsm_replan_device
- * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238; with scripted agents, below, k_script behind it), [6] the exchange
+ * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238; with a tracking model k_track, with scripted agents k_script behind it, both below), [6] the exchange
  * (AC:610-677; one rank: nothing).
  * Every record is a barrier packet in front of the next launch: a timed round is a few microseconds longer than a plain one. */
 int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on);
@@ -503,6 +503,80 @@ int hdsm_script_records_host(int32_t n_script, int32_t n_knots, const double* kn
                              int32_t predict, int64_t round, double* records);
 int hdsm_script_records_batch(int32_t device, int32_t n_script, int32_t n_knots, const double* knots, int32_t n_hor, int32_t step_plan,
                               double dt, int32_t predict, int64_t round, double* records);
+
+/* ---- imperfect tracking: disturbed and measured states in the loop (no new ABI minor; discover by symbol) --------------------------------
+ * The loop is closed on the reference's assumption that the vehicle arrives where its plan said: after every commit state_curr =
+ * traj_curr[step_plan] (AC:233-238). Two ways to fly something else, both opt-in (csrc/track_core.h, one source for the host forms and
+ * k_track): a disturbance MODEL applied right behind every commit, and a state taken from OUTSIDE (a simulator, odometry) between two
+ * rounds. The published record is never touched: an agent broadcasts its plan before it flies it, so the records, and with them the
+ * device audit, stay what was INTENDED; what was FLOWN is in state_curr, the state history and the next round's corridor,
+ * reference and x_0.
+ *   draws    a counter hash, no state and no libm. mix(z), uint64 with wrap-around: z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *            z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^ (z >> 31). h = mix(mix(mix(seed ^ 0x9E3779B97F4A7C15) + id) + q), id the
+ *            agent's GLOBAL id, q the tracking round (0 = the first round after hdsm_*_set_tracking; it restarts at every call).
+ *            Draw c of 0..5: s_c = 2.0 * ((double)(mix(h + c + 1) >> 11) * 0x1p-53) - 1.0, in [-1, 1), every step exact. Keyed by the
+ *            global id, a sharded flight draws what the one-rank flight draws.
+ *   model    x = traj_curr[step_plan] = (p, v, a), T = (double)step_plan * dt. Per axis: w = wind + gust * s_ax; tw = T * w;
+ *            p' = (p + 0.5 * (T * tw)) + jitter * s_{3+ax}; v' = v + tw; a' = a — a disturbance acceleration held over the flown
+ *            interval plus a position jitter. No memory: the vehicle's own controller is taken to recover the plan up to this
+ *            round's disturbance, also after a shift-by-one fallback. wind, gust in m/s^2, jitter in m; gust and jitter are
+ *            amplitudes >= 0; every entry finite.
+ *   record   per agent (hdsm_track_record): d = sqrt(dx*dx + dy*dy + dz*dz) of the stored p' - p and the same norm of v' - v.
+ *            A model round: rounds += 1; a state taken from outside: external += 1, d and the velocity norm against the state it
+ *            replaces. Both: dist_sum += d, dist_sq_sum += d*d, dist_max and dvel_max by comparison — over rounds + external samples
+ *            the sum, the sum of squares and the maximum that planner_crazyswarm_bridge/scripts/tracking_error.py reports.
+ *   who      an agent without a plan (has_traj == 0) has nothing to deviate from: the model leaves it alone and does not count it.
+ *            Scripted agents are never touched, by the model or from outside: their state is the track's.
+ *   hdsm_track_states_host    flown [n][9] (and dist [n], or NULL) of the n agents agent_id (global ids) in tracking round `round` from
+ *                             planned [n][9] and the flown interval T = step_plan * dt; pure. hdsm_track_states_batch: the same through
+ *                             k_track on `device` (host pointers), bit for bit. HDSM_ERR_BAD_ARG before anything is touched: a NULL
+ *                             where a pointer is needed, a non-finite model entry, a negative gust or jitter, n < 0, T not positive
+ *                             and finite, round outside 0..2^40.
+ *   hdsm_swarm_set_tracking   the host mirror: hdsm_swarm_commit applies the model behind commit_one (the state history of the planner
+ *                             records holds flown states). NULL switches it off and keeps the records.
+ *   hdsm_swarm_set_states     states [n_local][9] from outside, mask [n_local] (NULL: all): a masked row whose nine values are finite
+ *                             replaces state_curr; a row with a non-finite value is skipped and counted nowhere.
+ *   hdsm_dswarm_set_tracking  the device loop: k_track, one lane per flown agent, right behind k_commit and in front of k_script, inside
+ *                             entry [5] of the phase timing and before the history row is taken. Synchronises, like
+ *                             hdsm_dswarm_set_script. NULL: off, records kept. Device memory for the records is allocated by the first
+ *                             call that needs it; a flight that never calls any of these allocates and launches nothing new.
+ *   hdsm_dswarm_set_states    host pointers; synchronises. hdsm_dswarm_set_states_device: device pointers, asynchronous on hip_stream,
+ *                             which MUST be the stream the rounds run on (as for hdsm_dswarm_update_world_raw_device); keep the arrays
+ *                             alive until the stream has passed the call. It applies between two rounds: the next round's corridor,
+ *                             reference and x_0 see it, and while the history is on the agent's entry of the row the last round
+ *                             left takes the state too (a row hdsm_dswarm_download_history has already handed to the mirror stays).
+ *   hdsm_dswarm_track_stats   out[0] tracking rounds since the model was set, out[1] model launches of k_track, out[2] external
+ *                             launches, both since hdsm_dswarm_create. Host counters: it does not synchronise.
+ *   hdsm_dswarm_plans_device  the device addresses of the plans buffer [world * per][N + 1][9] and its flags [world * per]: read-only
+ *                             for the caller, valid for the dswarm's life. With them a simulator on the same GPU reads what to execute
+ *                             without a download (on the rounds' stream, or after synchronising with it).
+ * The model is carried neither from the mirror into a new dswarm nor back by hdsm_dswarm_download, and neither are the track
+ * records; the states travel with the agents as they do now. The caller sets the model on both sides. */
+typedef struct hdsm_tracking {
+  uint64_t seed;
+  double wind[3], gust[3], jitter[3];
+} hdsm_tracking;
+
+typedef struct hdsm_track_record {
+  int64_t rounds;    /* model rounds counted for this agent */
+  int64_t external;  /* states taken from outside */
+  double dist_sum, dist_sq_sum, dist_max; /* over rounds + external samples */
+  double dvel_max;
+} hdsm_track_record;
+
+int hdsm_track_states_host(const hdsm_tracking* m, int32_t n, const int32_t* agent_id, const double* planned, double T, int64_t round,
+                           double* flown, double* dist);
+int hdsm_track_states_batch(int32_t device, const hdsm_tracking* m, int32_t n, const int32_t* agent_id, const double* planned, double T,
+                            int64_t round, double* flown, double* dist);
+int hdsm_swarm_set_tracking(void* swarm, const hdsm_tracking* m);
+int hdsm_swarm_set_states(void* swarm, const double* states, const uint8_t* mask);
+int hdsm_swarm_track_records(void* swarm, hdsm_track_record* out);
+int hdsm_dswarm_set_tracking(void* dswarm, const hdsm_tracking* m);
+int hdsm_dswarm_set_states(void* dswarm, const double* states, const uint8_t* mask);
+int hdsm_dswarm_set_states_device(void* dswarm, const double* d_states, const uint8_t* d_mask, void* hip_stream);
+int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out);
+int hdsm_dswarm_track_stats(void* dswarm, int64_t out[3]);
+int hdsm_dswarm_plans_device(void* dswarm, void** d_plans, void** d_has);
 
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between

@@ -60,6 +60,9 @@ int hdsm_internal_audit_host_grouped(int32_t n_rob, const double* plans_all, con
 // (script_host.cpp) the argument checks shared by hdsm_script_records_host / _batch
 int hdsm_internal_script_args(int32_t n_script, int32_t n_knots, const double* knots, int32_t n_hor, int32_t step_plan, double dt, int32_t predict,
                               int64_t round, const double* records);
+// (track_host.cpp) the argument checks shared by hdsm_track_states_host / _batch
+int hdsm_internal_track_args(const hdsm_tracking* m, int32_t n, const int32_t* agent_id, const double* planned, double T, int64_t round,
+                             const double* flown);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

@@ -23,6 +23,7 @@
 #include "link_core.h"
 #include "path_core.h"
 #include "swarm_core.h"
+#include "track_core.h"
 
 namespace {
 
@@ -88,6 +89,15 @@ struct Swarm {
   std::vector<hdsm_audit_round> audit_last;
   // neighbour groups (hdsm_swarm_set_groups): the partition as given (empty: none) and the id range per agent, [n_rob][2]
   std::vector<int32_t> group_start, range;
+  // imperfect tracking (track_core.h; hdsm_swarm_set_tracking / _set_states): the model while it is on, the tracking round the next
+  // commit flies, the record per agent (empty until the first call that needs it)
+  bool track_on = false;
+  hdsm_tracking track{};
+  long long track_q = 0;
+  std::vector<hdsm_track_record> track_rec;
+  void track_ready() {
+    if (track_rec.size() != (size_t)n_local) track_rec.assign((size_t)n_local, hdsm_track_record{});
+  }
   void neighbour_range(int id, int* lo, int* hi) const {
     *lo = range.empty() ? 0 : range[2 * (size_t)id], *hi = range.empty() ? n_rob : range[2 * (size_t)id + 1];
   }
@@ -500,6 +510,19 @@ int hdsm_swarm_commit(void* swarm, const double* traj_out, const double* ctrl_ou
       for (int c = 0; c < 9; ++c)
         plans_local[((size_t)k * (N + 1) + i) * 9 + c] = have_plan ? ag.traj_curr[i][c] : 0.0;
   }
+  if (sw->track_on) {  // the state flown in place of traj_curr[step_plan] (track_core.h); the published record stays the plan
+    const double T = (double)sw->cfg.step_plan * sw->prm.dt;
+    for (int k = 0; k < sw->n_local; ++k) {
+      AgentS& ag = sw->agents[k];
+      if (!ag.has_traj) continue;
+      double from[9], to[9];
+      for (int c = 0; c < 9; ++c) from[c] = ag.traj_curr[sw->cfg.step_plan][c];
+      hdsm_track::flown_state(sw->track, ag.id, sw->track_q, T, from, to);
+      for (int c = 0; c < 9; ++c) ag.state_curr[c] = to[c];
+      hdsm_track::book(sw->track_rec[(size_t)k], hdsm_track::pos_dist(from, to), hdsm_track::vel_dist(from, to), false);
+    }
+    ++sw->track_q;
+  }
   // f3: the records Agent::TrajPlanningIteration keeps (AC:193-245). The separating planes are generated inside the fused
   // launch: its duration (hdsm_swarm_record_solve_ms) is booked as comp_time_opt_, comp_time_tasc_ is 0.
   const double wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sw->t_round).count();
@@ -514,6 +537,37 @@ int hdsm_swarm_commit(void* swarm, const double* traj_out, const double* ctrl_ou
     hdsm_stats_add_state(x.stats, stamp, sw->agents[k].state_curr, 9);
   }
   ++sw->round_idx;
+  return HDSM_OK;
+}
+
+// Imperfect tracking on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_swarm_set_tracking(void* swarm, const hdsm_tracking* m) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || (m && !hdsm_track::model_valid(m))) return HDSM_ERR_BAD_ARG;
+  sw->track_on = m != nullptr;
+  if (m) sw->track = *m, sw->track_q = 0, sw->track_ready();
+  return HDSM_OK;
+}
+
+int hdsm_swarm_set_states(void* swarm, const double* states, const uint8_t* mask) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || (!states && sw->n_local)) return HDSM_ERR_BAD_ARG;
+  sw->track_ready();
+  for (int k = 0; k < sw->n_local; ++k) {
+    const double* to = states + (size_t)k * 9;
+    if ((mask && !mask[k]) || !hdsm_track::finite9(to)) continue;
+    AgentS& ag = sw->agents[k];
+    double from[9];
+    for (int c = 0; c < 9; ++c) from[c] = ag.state_curr[c], ag.state_curr[c] = to[c];
+    hdsm_track::book(sw->track_rec[(size_t)k], hdsm_track::pos_dist(from, to), hdsm_track::vel_dist(from, to), true);
+  }
+  return HDSM_OK;
+}
+
+int hdsm_swarm_track_records(void* swarm, hdsm_track_record* out) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || (!out && sw->n_local)) return HDSM_ERR_BAD_ARG;
+  for (int k = 0; k < sw->n_local; ++k) out[k] = (size_t)k < sw->track_rec.size() ? sw->track_rec[(size_t)k] : hdsm_track_record{};
   return HDSM_OK;
 }
 

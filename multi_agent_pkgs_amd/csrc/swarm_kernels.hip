@@ -7,6 +7,8 @@
 //   k_replan     planes + MIQP (the hot path)                                                   hdsm_replan_device
 //   k_commit     the new reference into the agent state, read-back, shift fallback, increment check, state advance, published
 //                record                                                                          one wavefront per agent
+//   k_track      (only with a tracking model, hdsm_dswarm_set_tracking) the state flown in place of traj_curr[step_plan] and the record
+//                of the difference (track_kernels.hip); also launched between rounds by hdsm_dswarm_set_states*   one lane per flown agent
 //   k_script     (only with scripted agents, hdsm_dswarm_set_script) the records of the shard's scripted tail, over the slots
 //                k_commit has just padded (script_kernels.hip)                                   one wavefront per scripted agent
 //   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
@@ -34,6 +36,7 @@
 #include "path_core.h"
 #include "script_device.h"
 #include "swarm_core.h"
+#include "track_device.h"
 
 #ifdef CD_PROFILE
 // development builds only: the phase counters of the corridor kernel's decompositions (read and cleared); [12] cycles of the whole
@@ -639,6 +642,7 @@ struct Audit {
 struct History {
   DevBuf<double> d_rows;
   int cap = 0, n = 0, dropped = 0, delivered = 0;
+  bool last = false;  // the last round wrote row n - 1 (a state taken from outside behind that round replaces the agent's entry of it)
 };
 
 // map updates in flight (nothing is allocated or launched before the first hdsm_dswarm_update_world* / _set_raw_world): the
@@ -676,6 +680,18 @@ struct Script {
   long long round = 0;  // the script round the next k_script publishes (0: the first round after hdsm_dswarm_set_script)
   long long launches = 0;
   DevBuf<double> d_knots;
+};
+
+// imperfect tracking (hdsm_dswarm_set_tracking / _set_states*; nothing is allocated or launched before the first call that needs it): the
+// model while it is on, the tracking round the next k_track flies, the launches of the two forms, the record per agent ([n_local],
+// zeros at first) and the staging of the host-pointer form of a state from outside
+struct Track {
+  bool on = false;
+  hdsm_tracking model{};
+  long long q = 0, model_launches = 0, external_launches = 0;
+  DevBuf<hdsm_track_record> d_rec;
+  DevBuf<double> d_stage;
+  DevBuf<uint8_t> d_stage_mask;
 };
 
 // One link round (link_core.h, deliver_slot): a wavefront per slot of the plans buffer, four per workgroup. No LDS, no atomics: a
@@ -770,6 +786,7 @@ struct DSwarm {
   WorldEdits edits;
   Links links;
   Script script;
+  Track track;
   int n_fly() const { return n_local - script.n; }  // the agents this shard plans for: all but its scripted tail
   // neighbour groups (taken from the mirror by hdsm_dswarm_create; one group = the whole swarm without a partition): the
   // partition, the id range per record of the plans buffer ([per * world][2], for the audit; null without a partition), the report
@@ -1067,6 +1084,15 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
                      d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), direct ? d.d_plans.get() : d.d_local.get(), d.d_fails.get(),
                      direct ? d.d_has.get() : nullptr, d.d_ref_full.get(), d.d_pv.get());
   HIP_TRY(hipGetLastError());
+  if (Track& t = d.track; t.on) {  // the flown agents fly something else than they planned (inside phase [5]; the records above stay the plans)
+    if (n_fly > 0) {
+      HIP_TRY(hdsm_track::launch(hdsm_track::Launch{n_fly, d.c.step_plan, t.q, (double)d.c.step_plan * d.prm.dt, t.model, d.d_agents.get(), t.d_rec.get(),
+                                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                                 st));
+      ++t.model_launches;
+    }
+    ++t.q;
+  }
   if (Script& s = d.script; s.n > 0) {  // the scripted tail, over the slots k_commit has just padded (and inside its phase [5])
     const size_t rec = (size_t)(d.c.N + 1) * 9;
     HIP_TRY(hdsm_script::launch(hdsm_script::Round{s.n, s.n_knots, d.c.N, d.c.step_plan, s.predict, s.round, d.prm.dt, s.d_knots.get(),
@@ -1134,6 +1160,7 @@ int audit_and_history(DSwarm& d, hipStream_t st) {
     if (a.on) ++a.rounds;
   }
   if (hist) ++h.n;
+  h.last = hist;
   return HDSM_OK;
 }
 
@@ -1476,6 +1503,105 @@ int hdsm_dswarm_script_stats(void* dswarm, int64_t out[3]) {
   return HDSM_OK;
 }
 
+// Imperfect tracking (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+namespace {
+// the records, allocated by the first call that needs them (the caller has set the device)
+int track_records_ready(DSwarm* d) {
+  if (!d->track.d_rec) {
+    HIP_TRY(d->track.d_rec.alloc_zeroed((size_t)d->n_local));
+    HIP_TRY(hipDeviceSynchronize());  // (the fill is done before a kernel of any stream books into them)
+  }
+  return HDSM_OK;
+}
+// a state from outside into the flown agents: k_track's external form over device arrays, on st
+int track_external(DSwarm* d, const double* d_states, const uint8_t* d_mask, hipStream_t st) {
+  Track& t = d->track;
+  const History& h = d->hist;
+  const int n_fly = d->n_fly();
+  if (n_fly > 0) {
+    // the state measured behind a round IS the state after that round: the row the round left in the history takes it too
+    double* const row = h.last && h.n > 0 ? h.d_rows.get() + (size_t)(h.n - 1) * d->n_local * 9 : nullptr;
+    HIP_TRY(hdsm_track::launch(hdsm_track::Launch{n_fly, d->c.step_plan, 0, 0.0, hdsm_tracking{}, d->d_agents.get(), t.d_rec.get(), d_states, d_mask, nullptr,
+                                                  nullptr, nullptr, nullptr, row},
+                               st));
+    ++t.external_launches;
+  }
+  return HDSM_OK;
+}
+}  // namespace
+
+int hdsm_dswarm_set_tracking(void* dswarm, const hdsm_tracking* m) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (m && !hdsm_track::model_valid(m))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_tracking: every entry of the model finite, gust and jitter not negative");
+  Track& t = d->track;
+  if (!m && !t.on) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (m) {
+    if (int rc = track_records_ready(d)) return rc;
+    t.model = *m, t.q = 0;
+  }
+  t.on = m != nullptr;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_states(void* dswarm, const double* states, const uint8_t* mask) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (!states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  Track& t = d->track;
+  const size_t n = (size_t)d->n_local;
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (int rc = track_records_ready(d)) return rc;
+  if (!t.d_stage) HIP_TRY(t.d_stage.alloc(n * 9));
+  if (mask && !t.d_stage_mask) HIP_TRY(t.d_stage_mask.alloc(n));
+  HIP_TRY(hipMemcpy(t.d_stage.get(), states, n * 9 * sizeof(double), hipMemcpyHostToDevice));
+  if (mask) HIP_TRY(hipMemcpy(t.d_stage_mask.get(), mask, n, hipMemcpyHostToDevice));
+  if (int rc = track_external(d, t.d_stage.get(), mask ? t.d_stage_mask.get() : nullptr, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_states_device(void* dswarm, const double* d_states, const uint8_t* d_mask, void* hip_stream) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (!d_states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states_device: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  if (int rc = track_records_ready(d)) return rc;
+  return track_external(d, d_states, d_mask, static_cast<hipStream_t>(hip_stream));
+}
+
+int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || (!out && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_track_records: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  if (!d->track.d_rec) {
+    for (int k = 0; k < d->n_local; ++k) out[k] = hdsm_track_record{};
+    return HDSM_OK;
+  }
+  HIP_TRY(hipSetDevice(d->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d->track.d_rec.get(), (size_t)d->n_local * sizeof(hdsm_track_record), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_track_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->track.q, out[1] = d->track.model_launches, out[2] = d->track.external_launches;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_plans_device(void* dswarm, void** d_plans, void** d_has) {
+  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  if (!d || !d_plans || !d_has) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  *d_plans = d->d_plans.get(), *d_has = d->d_has.get();
+  return HDSM_OK;
+}
+
 int hdsm_dswarm_link_stats(void* dswarm, int64_t out[4]) {
   DSwarm* d = static_cast<DSwarm*>(dswarm);
   if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
@@ -1607,7 +1733,7 @@ int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds) {
   HIP_TRY(hipDeviceSynchronize());
   History& h = d->hist;
   h.d_rows.reset();
-  h.cap = 0, h.n = h.dropped = h.delivered = 0;
+  h.cap = 0, h.n = h.dropped = h.delivered = 0, h.last = false;
   if (capacity_rounds > 0) {
     if (int rc = audit_setup(d, nullptr)) return rc;
     HIP_TRY(h.d_rows.alloc((size_t)capacity_rounds * d->n_local * 9 + 1));

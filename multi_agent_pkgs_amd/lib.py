@@ -16,7 +16,7 @@ import re
 
 import numpy as np
 
-from .params import HdsmParams, MapConfig, RefConfig, SwarmConfig
+from .params import HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("HDSM_LIBRARY") or os.path.join(_HERE, "libhdsm.so")  # (HDSM_LIBRARY: a development build, e.g. -DCD_PROFILE)
@@ -38,7 +38,10 @@ GROUP_REPORT = np.dtype([("first", "<i4"), ("count", "<i4"), ("n_local", "<i4"),
                          ("unknown", "<i8"), ("crossed", "<i8"), ("pot_sum", "<i8"), ("sep2_min", "<f8"), ("sep_agent", "<i4"),
                          ("sep_partner", "<i4"), ("sep_substep", "<i4"), ("reserved0", "<i4"), ("sep_round", "<i8"),
                          ("speed_max", "<f8")])                                                            # hdsm_group_report
+TRACK_RECORD = np.dtype([("rounds", "<i8"), ("external", "<i8"), ("dist_sum", "<f8"), ("dist_sq_sum", "<f8"), ("dist_max", "<f8"),
+                         ("dvel_max", "<f8")])                                                             # hdsm_track_record
 assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104 and GROUP_REPORT.itemsize == 128
+assert TRACK_RECORD.itemsize == 48 == C.sizeof(TrackRecord) and C.sizeof(Tracking) == 80
 
 
 class HdsmError(RuntimeError):
@@ -73,9 +76,9 @@ CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": 
 CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32_t", np.int32), ("int8_t", np.int8), ("uint8_t", np.uint8),
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
                                                   ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
-                                                  ("hdsm_group_report", GROUP_REPORT))})
+                                                  ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
-                                                  ("hdsm_swarm_config", SwarmConfig))})
+                                                  ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking))})
 
 
 def parse_declarations(text):
@@ -115,7 +118,8 @@ EXPORTS = tuple(SIGNATURES)
 # the functions that report their own name.
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
-              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_", "hdsm_last_error"))
+              ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_track_", None),
+              ("hdsm_", "hdsm_last_error"))
 
 _lib = None
 
@@ -518,6 +522,20 @@ def script_records(knots, n_hor, step_plan=1, dt=0.1, predict=0, round=0, device
     lead, fn = ((), "hdsm_script_records_host") if device is None else ((int(device),), "hdsm_script_records_batch")
     call(fn, *lead, knots.shape[0], knots.shape[1], knots, int(n_hor), int(step_plan), float(dt), int(predict), int(round), records)
     return records
+
+
+def track_states(model, ids, planned, T, round=0, device=None):
+    """hdsm_track_states_host: (flown [n][9], dist [n]) — the states the agents `ids` (global ids) fly in tracking round `round` in place
+    of planned [n][9] = (p, v, a) under the model (params.Tracking, scenarios.gust_model) over the flown interval T = step_plan * dt
+    (csrc/track_core.h), and the distance between the two positions. device given: hdsm_track_states_batch, the same through k_track
+    on that device, bit for bit."""
+    ids, planned = _i32(ids).reshape(-1), _f64(planned)
+    if planned.ndim != 2 or planned.shape != (ids.size, 9):
+        raise HdsmError(HDSM_ERR_BAD_ARG, "track_states: planned [n][9] for ids [n] expected")
+    flown, dist = np.zeros_like(planned), np.zeros(ids.size)
+    lead, fn = ((), "hdsm_track_states_host") if device is None else ((int(device),), "hdsm_track_states_batch")
+    call(fn, *lead, model, ids.size, ids, planned, float(T), int(round), flown, dist)
+    return flown, dist
 
 
 def _flight_audit(fn, lead, plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world, worigin, voxel_size):

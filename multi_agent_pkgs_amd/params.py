@@ -134,3 +134,17 @@ class SwarmConfig(C.Structure):
         ("grid_z_min", C.c_double), ("n_it_decomp", C.c_int32), ("step_plan", C.c_int32),
         ("use_cvx_new", C.c_int32), ("reserved0", C.c_int32),
     ]
+
+
+class Tracking(C.Structure):
+    """hdsm_tracking (include/hdsm_swarm.h): the disturbance model of imperfect tracking — the seed of the draws, a constant wind and
+    a gust amplitude (m/s^2, an acceleration held over the flown interval) and a position jitter amplitude (m), per axis."""
+    _fields_ = [("seed", C.c_uint64), ("wind", C.c_double * 3), ("gust", C.c_double * 3), ("jitter", C.c_double * 3)]
+
+
+class TrackRecord(C.Structure):
+    """hdsm_track_record: per agent the model rounds and the states taken from outside that were counted, over those samples the sum,
+    the sum of squares and the maximum of the distance between the planned and the flown position, and the largest velocity
+    difference. lib.TRACK_RECORD is the numpy dtype of the same layout."""
+    _fields_ = [("rounds", C.c_int64), ("external", C.c_int64), ("dist_sum", C.c_double), ("dist_sq_sum", C.c_double),
+                ("dist_max", C.c_double), ("dvel_max", C.c_double)]

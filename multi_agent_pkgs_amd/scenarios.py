@@ -98,6 +98,20 @@ def stack_tracks(*tracks):
     return out
 
 
+def gust_model(seed=0, wind=(0.0, 0.0, 0.0), gust=(0.0, 0.0, 0.0), jitter=(0.0, 0.0, 0.0)):
+    """A disturbance model for SwarmShard.set_tracking / DeviceSwarm.set_tracking (params.Tracking): a constant wind and a gust amplitude
+    per axis in m/s^2 — an acceleration w = wind + gust * s, s uniform in [-1, 1) per agent and round, held over the flown interval —
+    and a position jitter amplitude per axis in m. The project's own scenario class (the reference assumes perfect tracking)."""
+    from .params import Tracking
+    m = Tracking()
+    m.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for name, v in (("wind", wind), ("gust", gust), ("jitter", jitter)):
+        v = np.asarray(v, dtype=np.float64).reshape(3)
+        for ax in range(3):
+            getattr(m, name)[ax] = v[ax]
+    return m
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

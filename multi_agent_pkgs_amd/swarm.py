@@ -193,6 +193,24 @@ class SwarmShard:
         call("hdsm_swarm_flight_report", self.h, rep)
         return rep
 
+    # ---- imperfect tracking (include/hdsm_swarm.h) ----
+    def set_tracking(self, model=None):
+        """hdsm_swarm_set_tracking: from the next commit on every agent with a plan flies lib.track_states of traj_curr[step_plan]
+        under the model (params.Tracking, scenarios.gust_model) instead of arriving where it planned; the tracking round starts at
+        0. None: off, the records are kept. Not carried into a DeviceSwarm: set it there too."""
+        call("hdsm_swarm_set_tracking", self.h, model)
+
+    def set_states(self, states, mask=None):
+        """hdsm_swarm_set_states: states [n_local][9] measured outside (a simulator, odometry) replace state_curr of the masked agents
+        (mask [n_local], None: all); a row with a non-finite value is skipped."""
+        call("hdsm_swarm_set_states", self.h, _f64(states).reshape(self.n_local, 9), None if mask is None else _u8(mask).reshape(self.n_local))
+
+    def track_records(self):
+        """hdsm_swarm_track_records: the tracking record per local agent (lib.TRACK_RECORD; tracking_summary folds them)."""
+        rec = np.zeros(self.n_local, _lib.TRACK_RECORD)
+        call("hdsm_swarm_track_records", self.h, rec)
+        return rec
+
     def state(self):
         pos = np.zeros((self.n_local, 3))
         dist = np.zeros(self.n_local)
@@ -454,6 +472,42 @@ class DeviceSwarm:
         """hdsm_dswarm_script_stats: script rounds since the last set_script, scripted agents, launches of k_script."""
         return dict(zip(("rounds", "n_script", "launches"), self._counters("hdsm_dswarm_script_stats", 3)))
 
+    # ---- imperfect tracking (include/hdsm_swarm.h) ----
+    def set_tracking(self, model=None):
+        """hdsm_dswarm_set_tracking: from the next round on k_track, right behind k_commit, makes every flown agent with a plan fly
+        lib.track_states of traj_curr[step_plan] under the model (params.Tracking, scenarios.gust_model); the published records stay
+        the plans, the history holds the flown states. The tracking round starts at 0. None: off, records kept. Synchronises."""
+        call("hdsm_dswarm_set_tracking", self.h, model)
+
+    def set_states(self, states, mask=None, stream=None):
+        """States [n_local][9] measured outside replace state_curr of the masked flown agents (mask [n_local] of uint8, None: all; a row
+        with a non-finite value is skipped) before the next round. A numpy array: hdsm_dswarm_set_states, copied in, synchronises.
+        Anything with data_ptr() (a float64 device tensor; the mask a uint8 one): hdsm_dswarm_set_states_device, asynchronous on
+        `stream` — which must be the stream the rounds run on; keep the tensors alive until the stream has passed the call."""
+        n = self.shard.n_local
+        if hasattr(states, "data_ptr"):
+            assert states.is_cuda and states.numel() == n * 9 and (mask is None or (mask.is_cuda and mask.numel() == n))
+            call("hdsm_dswarm_set_states_device", self.h, states, mask, _stream(stream))
+        else:
+            call("hdsm_dswarm_set_states", self.h, _f64(states).reshape(n, 9), None if mask is None else _u8(mask).reshape(n))
+
+    def track_records(self):
+        """hdsm_dswarm_track_records: the tracking record per local agent (lib.TRACK_RECORD). Synchronises."""
+        rec = np.zeros(self.shard.n_local, _lib.TRACK_RECORD)
+        call("hdsm_dswarm_track_records", self.h, rec)
+        return rec
+
+    def track_stats(self):
+        """hdsm_dswarm_track_stats: tracking rounds since the model was set, launches of k_track's model form and of its external form."""
+        return dict(zip(("rounds", "model_launches", "external_launches"), self._counters("hdsm_dswarm_track_stats", 3)))
+
+    def plans_device(self):
+        """hdsm_dswarm_plans_device: the device addresses (plans buffer [world * per][N+1][9] of float64, flags [world * per] of uint8),
+        read-only and valid for the dswarm's life — what a simulator on the same GPU reads to know what to execute."""
+        plans, has = C.c_void_p(), C.c_void_p()
+        call("hdsm_dswarm_plans_device", self.h, C.byref(plans), C.byref(has))
+        return plans.value, has.value
+
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
         call("hdsm_dswarm_set_audit", self.h, 1 if on else 0, sep_warn)
@@ -595,3 +649,31 @@ def flight_summary(reports, first_id=0):
         out.update(sigma_min=float(np.sqrt(rep["sep2_min"][k])), sigma_min_agent=int(first_id + k), sigma_min_partner=int(rep["sep_partner"][k]),
                    sigma_min_substep=int(rep["sep_substep"][k]), sigma_min_round=int(rep["sep_round"][k]))
     return out
+
+
+def tracking_summary(records):
+    """Folds per-agent tracking records (lib.TRACK_RECORD, of one shard or concatenated) into the three figures of the reference's
+    planner_crazyswarm_bridge/scripts/tracking_error.py over all samples (model rounds + states taken from outside): the mean, the
+    standard deviation (population, as numpy.std) and the maximum of the distance between the planned and the flown position; with
+    them the number of samples and the largest velocity difference."""
+    rec = np.asarray(records)
+    n = int(rec["rounds"].sum() + rec["external"].sum())
+    if n == 0:
+        return dict(samples=0, mean=0.0, std=0.0, max=0.0, dvel_max=0.0)
+    mean = float(rec["dist_sum"].sum()) / n
+    var = max(float(rec["dist_sq_sum"].sum()) / n - mean * mean, 0.0)
+    return dict(samples=n, mean=mean, std=float(np.sqrt(var)), max=float(rec["dist_max"].max()), dvel_max=float(rec["dvel_max"].max()))
+
+
+def flown_records(hist, starts):
+    """From a state history hist [rounds][n][9] (DeviceSwarm.history; starts [n][3] or [n][9]: where the agents stood before round 0)
+    the two-state records [rounds][n][2][9] = (state before the round, state after it) that lib.flight_audit_host / flight_audit_batch
+    accept with n_hor = 1 and step_plan = 1: the motion actually FLOWN judged with the audit that exists, where the device audit
+    judges the published plans. The audit joins the two states by a straight segment: for step_plan > 1 that is the chord of the
+    flown interval, not its sub-steps."""
+    hist = np.asarray(hist, dtype=np.float64)
+    starts = np.asarray(starts, dtype=np.float64)
+    first = np.zeros((1,) + hist.shape[1:])
+    first[0, :, :starts.shape[1]] = starts
+    before = np.concatenate([first, hist[:-1]])
+    return np.ascontiguousarray(np.stack([before, hist], axis=2))
