@@ -219,7 +219,7 @@ int hdsm_swarm_prepare_corridor(void* swarm);
 /* ---- the device-resident closed loop ------------------------------------------------------------------------------------------
  * The planner state of the shard moves into HBM (hdsm_dswarm_create copies it out of a host mirror that has been set up —
  * starts, goals, world, paths — and possibly flown for some rounds) and one replan round becomes a chain of launches on one
- * stream with no host round trip (csrc/swarm_kernels.hip):
+ * stream with no host round trip (csrc/swarm_kernels.hip; the calls between rounds: csrc/dswarm_*):
  *   corridor (AC:1236-1447, row f2 on the device) -> reference (row f1) -> solver inputs -> hdsm_replan_device -> commit
  *   (AC:960-1019, 569-585, 233-238) -> published records -> ONE RCCL all-gather (hdsm_exchange_device; a copy on a single rank).
  * `solver` is an hdsm handle with max_instances >= the shard and n_rob_max >= world_size * ceil(n_rob / world_size); `comm` an

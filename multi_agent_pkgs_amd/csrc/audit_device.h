@@ -1,5 +1,5 @@
 // audit_device.h — the launch interface of the flight audit's kernels (audit_kernels.hip), used by hdsm_flight_audit_batch and
-// by the device-resident loop (swarm_kernels.hip).
+// by the device-resident loop (the launch: swarm_kernels.hip; the scratch: dswarm_audit.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

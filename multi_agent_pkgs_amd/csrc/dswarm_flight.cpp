@@ -1,0 +1,193 @@
+// dswarm_flight.cpp — the flight in and out of the device-resident loop: the host mirror's state onto the device at hdsm_dswarm_create
+// (take_over) and back (hdsm_dswarm_download, hand_back), the plans buffer up and down, and the goals a caller sets between rounds.
+// Copies and bookkeeping only: nothing here launches a kernel.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "dswarm.h"
+#include "hdsm_internal.h"
+#include "path_core.h"
+
+using namespace hdsm_dswarm;
+
+int hdsm_dswarm::upload_goals_and_due(DSwarm* d) {
+  PathStep& p = d->path;
+  std::vector<int32_t> idx;
+  for (int k = 0; k < d->n_local; ++k)
+    if (p.due[(size_t)k]) idx.push_back(k);
+  p.n_due = (int)idx.size();
+  HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), p.goals.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return HDSM_OK;
+}
+
+// The mirror's flight becomes the device's (hdsm_dswarm_create, after alloc_round_buffers): the path step's phase and pending agents,
+// the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the audit's setting and record.
+int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
+  const size_t n = (size_t)d.n_local;
+  PathStep& p = d.path;
+  const auto refused = [](int rc) { return fail(rc, "hdsm_dswarm_create: export failed"); };
+  p.due.assign(n, 0), p.goals.assign(n * 3, 0.0);
+  int32_t period = 0;
+  int64_t round = 0;
+  if (int rc = hdsm_swarm_export_path_state(swarm, &period, &round, p.due.data())) return refused(rc);
+  p.period = period, p.round = round;
+  double rad = 0;
+  if (int rc = hdsm_swarm_export_path_clearance(swarm, &rad)) return refused(rc);
+  if (rad != 0) {
+    hdsm_path::DmpMask mask{};
+    if (!hdsm_path::dmp_build_mask(rad, d.cfg.voxel_size, &mask)) return refused(HDSM_ERR_BAD_ARG);
+    p.dmp = true, p.dmp_rn = mask.rn;
+    HIP_TRY(p.d_dmp_rows.alloc_zeroed(sizeof mask.rows / sizeof mask.rows[0]));
+    HIP_TRY(hipMemcpy(p.d_dmp_rows.get(), mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
+  }
+  if (n) {
+    std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
+    if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
+    if (int rc = hdsm_swarm_export_state(swarm, tmp.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return refused(rc);
+    HIP_TRY(hipMemcpy(d.d_agents.get(), tmp.get(), n * sizeof(AgentS), hipMemcpyHostToDevice));
+    // the agent ids of the shard (a contiguous block), the goals, and the agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
+    std::vector<int32_t> ids(n, 0);
+    for (size_t k = 0; k < n; ++k) {
+      for (int q = 0; q < 3; ++q) p.goals[3 * k + q] = tmp[k].goal[q];
+      ids[k] = d.first + (int)k;
+    }
+    HIP_TRY(hipMemcpy(d.d_id.get(), ids.data(), n * 4, hipMemcpyHostToDevice));
+    if (int rc = upload_goals_and_due(&d)) return rc;
+  }
+  if (hworld) HIP_TRY(hipMemcpy(d.d_world.get(), hworld, d.voxels(), hipMemcpyHostToDevice));
+  d.c.world = d.d_world.get();
+  {  // the mirror's partition goes onto the solver handle (none: the handle's is cleared) and, for the audit, into a range table
+    int32_t ng = 0;
+    if (int rc = hdsm_swarm_export_groups(swarm, &ng, nullptr)) return refused(rc);
+    d.grouped = ng > 0;
+    d.group_start.assign((size_t)(d.grouped ? ng + 1 : 2), 0);
+    if (d.grouped) {
+      if (int rc = hdsm_swarm_export_groups(swarm, &ng, d.group_start.data())) return refused(rc);
+    } else {
+      d.group_start[1] = d.n_rob;
+    }
+    if (int rc = hdsm_set_groups(d.solver, d.grouped ? ng : 0, d.grouped ? d.group_start.data() : nullptr))
+      return fail(rc, std::string("hdsm_set_groups: ") + hdsm_last_error());
+    HIP_TRY(hipSetDevice(d.device));  // (the handle may live on another device)
+    if (d.grouped) {
+      const size_t G = (size_t)d.slots();
+      std::vector<int32_t> table(2 * G + 2, 0);
+      for (int g = 0; g < ng; ++g)
+        for (int k = d.group_start[g]; k < d.group_start[g + 1]; ++k) table[2 * (size_t)k] = d.group_start[g], table[2 * (size_t)k + 1] = d.group_start[g + 1];
+      HIP_TRY(d.d_range.alloc(table.size()));
+      HIP_TRY(hipMemcpy(d.d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+  }
+  int32_t on = 0, ever = 0;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
+  if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, nullptr)) return refused(rc);
+  if (ever) {
+    std::vector<hdsm_flight_report> rep(n);
+    if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, rep.data())) return refused(rc);
+    d.audit.on = on != 0;
+    if (int rc = audit_setup(&d, rep.data())) return rc;
+  }
+  return HDSM_OK;
+}
+
+// The device's flight back into the mirror (hdsm_dswarm_download; the device is idle): the agent states, the path step's phase,
+// pending agents and goals, the audit's setting and record.
+int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
+  const size_t n = (size_t)d.n_local;
+  std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
+  if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
+  int rc = hipMemcpy(tmp.get(), d.d_agents.get(), n * sizeof(AgentS), hipMemcpyDeviceToHost) == hipSuccess
+               ? hdsm_swarm_import_state(swarm, tmp.get(), d.n_local)
+               : HDSM_ERR_DEVICE;
+  if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d.path.period, d.path.round, d.path.due.data(), d.path.goals.data());
+  if (rc == HDSM_OK && d.audit.ever) {
+    std::vector<hdsm_flight_report> rep(n);
+    if (hipMemcpy(rep.data(), d.audit.d_report.get(), n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
+    else rc = hdsm_swarm_import_audit(swarm, d.audit.on ? 1 : 0, d.audit.sep_warn, rep.data());
+  }
+  return rc ? fail(rc, "state download failed") : HDSM_OK;
+}
+
+extern "C" {
+
+// GoalCallback (AC:2380-2388) for the shard: goals [n_local][3]; the agents whose goal changed plan a new path at the start of
+// the next round (k_path). Synchronises the device.
+int hdsm_dswarm_set_goals(void* dswarm, const double* goals) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!goals && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  PathStep& p = d->path;
+  for (int k = 0; k < d->n_local; ++k) {
+    double* g = &p.goals[3 * (size_t)k];
+    const double* ng = goals + 3 * (size_t)k;
+    if (g[0] == ng[0] && g[1] == ng[1] && g[2] == ng[2]) continue;
+    g[0] = ng[0], g[1] = ng[1], g[2] = ng[2];
+    p.due[k] = 1;
+  }
+  return upload_goals_and_due(d);
+}
+
+// out[0] agents planned by k_path since hdsm_dswarm_create, out[1] of them without a new path, out[2] launches of k_path.
+// Synchronises the device.
+int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (int rc = device_idle(d)) return rc;
+  unsigned long long cnt[2] = {0, 0};
+  HIP_TRY(hipMemcpy(cnt, d->path.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
+  out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path.launches;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_plans_device(void* dswarm, void** d_plans, void** d_has) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !d_plans || !d_has) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  *d_plans = d->d_plans.get(), *d_has = d->d_has.get();
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_raw(void* dswarm, double* plans_all_raw, double* send_raw) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (int rc = device_idle(d)) return rc;
+  const size_t L = (size_t)d->per, G = (size_t)d->slots(), rec = (size_t)d->rec();
+  if (plans_all_raw && G) HIP_TRY(hipMemcpy(plans_all_raw, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
+  if (send_raw && L) HIP_TRY(hipMemcpy(send_raw, d->d_local.get(), L * rec * 8, hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_upload_plans(void* dswarm, const double* plans_all, const uint8_t* has_plan) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !plans_all || !has_plan) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (int rc = device_idle(d)) return rc;
+  const size_t G = (size_t)d->slots(), rec = (size_t)d->rec(), have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;
+  HIP_TRY(hipMemset(d->d_has.get(), 0, G));
+  HIP_TRY(hipMemcpy(d->d_plans.get(), plans_all, have * rec * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d->d_has.get(), has_plan, have, hipMemcpyHostToDevice));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* has_plan, int32_t* status, int32_t* failed_total) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (int rc = device_idle(d)) return rc;
+  const size_t n = (size_t)d->n_local, G = (size_t)d->slots(), rec = (size_t)d->rec();
+  if (swarm && n)
+    if (int rc = hand_back(*d, swarm)) return rc;
+  if (plans_all) {
+    HIP_TRY(hipMemcpy(plans_all, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < G; ++k)
+      if (plans_all[k * rec] != plans_all[k * rec]) plans_all[k * rec] = 0.0;  // the sentinel is for the wire only
+  }
+  if (has_plan) HIP_TRY(hipMemcpy(has_plan, d->d_has.get(), G, hipMemcpyDeviceToHost));
+  if (status && n) HIP_TRY(hipMemcpy(status, d->d_status.get(), n * 4, hipMemcpyDeviceToHost));
+  if (failed_total) HIP_TRY(hipMemcpy(failed_total, d->d_fails.get(), 4, hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+}  // extern "C"

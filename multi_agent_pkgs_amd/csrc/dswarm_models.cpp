@@ -1,0 +1,214 @@
+// dswarm_models.cpp — what a caller puts between the plans and the flight of the device-resident loop, set between rounds: link faults
+// (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip) and imperfect tracking (k_track, track_kernels.hip),
+// each with its counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
+// (hdsm_dswarm_set_states*), through track_device.h.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "dswarm.h"
+#include "link_core.h"
+#include "script_device.h"
+#include "track_device.h"
+
+using namespace hdsm_dswarm;
+
+namespace {
+
+// the records, allocated by the first call that needs them (the caller has set the device)
+int track_records_ready(DSwarm* d) {
+  if (!d->track.d_rec) {
+    HIP_TRY(d->track.d_rec.alloc_zeroed((size_t)d->n_local));
+    HIP_TRY(hipDeviceSynchronize());  // (the fill is done before a kernel of any stream books into them)
+  }
+  return HDSM_OK;
+}
+// a state from outside into the flown agents: k_track's external form over device arrays, on st
+int track_external(DSwarm* d, const double* d_states, const uint8_t* d_mask, hipStream_t st) {
+  Track& t = d->track;
+  const History& h = d->hist;
+  const int n_fly = d->n_fly();
+  if (n_fly > 0) {
+    // the state measured behind a round IS the state after that round: the row the round left in the history takes it too
+    double* const row = h.last && h.n > 0 ? h.d_rows.get() + (size_t)(h.n - 1) * d->n_local * 9 : nullptr;
+    HIP_TRY(hdsm_track::launch(hdsm_track::Launch{n_fly, d->c.step_plan, 0, 0.0, hdsm_tracking{}, d->d_agents.get(), t.d_rec.get(), d_states, d_mask, nullptr,
+                                                  nullptr, nullptr, nullptr, row},
+                               st));
+    ++t.external_launches;
+  }
+  return HDSM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Link faults (include/hdsm_swarm.h). The call starts a new link history: the view is the plans buffer as it stands (every slot
+// delivered on time, held round -1, shift 0), the counters are zero, link round 0 is the next round.
+int hdsm_dswarm_set_links(void* dswarm, int32_t n_rounds, const int8_t* fate, int32_t time_aware) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (n_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: negative n_rounds");
+  Links& l = d->links;
+  if (int rc = device_idle(d)) return rc;
+  if (n_rounds == 0 || fate == nullptr) {
+    l.on = false;
+    return HDSM_OK;
+  }
+  const int D = hdsm_link::table_max_delay(n_rounds, d->n_rob, fate);
+  if (D < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: a delay above HDSM_LINK_MAX_DELAY");
+  const size_t G = (size_t)d->slots(), rec = (size_t)d->rec(), cells = (size_t)n_rounds * (size_t)d->n_rob;
+  l.on = false;
+  if (!l.ready()) {  // the first call: everything but the table, whose size is the caller's
+    hdsm_mem::FirstError ok;
+    ok(l.d_ring.alloc_zeroed((size_t)(hdsm_link::MAX_DELAY + 1) * G * rec)), ok(l.d_seen.alloc_zeroed(G * rec)), ok(l.d_seen_has.alloc_zeroed(G));
+    ok(l.d_seen_round.alloc(G)), ok(l.d_shift.alloc(G)), ok(l.d_cnt.alloc(G * hdsm_link::COUNTERS));
+    if (!ok.ok()) {
+      l.d_cnt.reset();
+      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_links: ") + hipGetErrorString(ok.e));
+    }
+  }
+  HIP_TRY(l.d_fate.ensure(cells, nullptr));
+  if (cells) HIP_TRY(hipMemcpy(l.d_fate.get(), fate, cells, hipMemcpyHostToDevice));
+  if (G) {
+    HIP_TRY(hipMemcpy(l.d_seen.get(), d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(l.d_seen_has.get(), d->d_has.get(), G, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemset(l.d_seen_round.get(), 0xff, G * sizeof(int32_t)));  // -1
+    HIP_TRY(hipMemset(l.d_shift.get(), 0, G * sizeof(int32_t)));
+    HIP_TRY(hipMemset(l.d_cnt.get(), 0, G * hdsm_link::COUNTERS * sizeof(int32_t)));
+  }
+  l.n_rounds = n_rounds, l.D = D, l.time_aware = time_aware != 0, l.round = 0, l.on = true;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_link_stats(void* dswarm, int64_t out[4]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (!d->links.ready()) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  const size_t G = (size_t)d->slots(), have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;  // (the padded tail publishes nothing)
+  std::vector<int32_t> cnt(have * hdsm_link::COUNTERS + 1);
+  if (have) HIP_TRY(hipMemcpy(cnt.data(), d->links.d_cnt.get(), have * hdsm_link::COUNTERS * sizeof(int32_t), hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < have; ++k) {
+    const int32_t* c = &cnt[k * hdsm_link::COUNTERS];
+    out[1] += c[0], out[2] += c[1];
+    out[3] = c[2] > out[3] ? c[2] : out[3], out[0] = c[3] > out[0] ? c[3] : out[0];
+  }
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_download_seen(void* dswarm, double* seen_raw, uint8_t* seen_has, int32_t* seen_round, int32_t* shift) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (!d->links.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_download_seen: no hdsm_dswarm_set_links yet");
+  if (int rc = device_idle(d)) return rc;
+  const Links& l = d->links;
+  const size_t G = (size_t)d->slots(), rec = (size_t)d->rec();
+  if (G == 0) return HDSM_OK;
+  if (seen_raw) HIP_TRY(hipMemcpy(seen_raw, l.d_seen.get(), G * rec * 8, hipMemcpyDeviceToHost));
+  if (seen_has) HIP_TRY(hipMemcpy(seen_has, l.d_seen_has.get(), G, hipMemcpyDeviceToHost));
+  if (seen_round) HIP_TRY(hipMemcpy(seen_round, l.d_seen_round.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (shift) HIP_TRY(hipMemcpy(shift, l.d_shift.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+// Scripted agents (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, const double* knots, int32_t predict) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  Script& s = d->script;
+  if (n_script < s.n) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: n_script may stay or grow (a scripted agent has no planner state to resume from)");
+  if (n_script > d->n_local) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: more scripted agents than the shard has");
+  if (predict != 0 && predict != 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: predict is 0 or 1");
+  if (!hdsm_script::tracks_valid(n_script, n_knots, knots))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: 1 .. 256 knots per track, every entry finite, times strictly increasing");
+  if (n_script == 0) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  if (!s.d_knots) HIP_TRY(s.d_knots.alloc((size_t)d->n_local * hdsm_script::MAX_KNOTS * 4));
+  HIP_TRY(hipMemcpy(s.d_knots.get(), knots, (size_t)n_script * n_knots * 4 * sizeof(double), hipMemcpyHostToDevice));
+  // a scripted agent's goal is its last knot, and it plans no path: the flown agents that are due stay due
+  PathStep& p = d->path;
+  const int n_fly = d->n_local - n_script;
+  for (int k = n_fly; k < d->n_local; ++k) {
+    const double* last = knots + ((size_t)(k - n_fly) * n_knots + (n_knots - 1)) * 4;
+    for (int q = 0; q < 3; ++q) p.goals[3 * (size_t)k + q] = last[1 + q];
+    p.due[(size_t)k] = 0;
+  }
+  if (int rc = upload_goals_and_due(d)) return rc;
+  s.n = n_script, s.n_knots = n_knots, s.predict = predict, s.round = 0;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_script_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->script.round, out[1] = d->script.n, out[2] = d->script.launches;
+  return HDSM_OK;
+}
+
+// Imperfect tracking (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_tracking(void* dswarm, const hdsm_tracking* m) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (m && !hdsm_track::model_valid(m))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_tracking: every entry of the model finite, gust and jitter not negative");
+  Track& t = d->track;
+  if (!m && !t.on) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  if (m) {
+    if (int rc = track_records_ready(d)) return rc;
+    t.model = *m, t.q = 0;
+  }
+  t.on = m != nullptr;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_states(void* dswarm, const double* states, const uint8_t* mask) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  Track& t = d->track;
+  const size_t n = (size_t)d->n_local;
+  if (int rc = device_idle(d)) return rc;
+  if (int rc = track_records_ready(d)) return rc;
+  if (!t.d_stage) HIP_TRY(t.d_stage.alloc(n * 9));
+  if (mask && !t.d_stage_mask) HIP_TRY(t.d_stage_mask.alloc(n));
+  HIP_TRY(hipMemcpy(t.d_stage.get(), states, n * 9 * sizeof(double), hipMemcpyHostToDevice));
+  if (mask) HIP_TRY(hipMemcpy(t.d_stage_mask.get(), mask, n, hipMemcpyHostToDevice));
+  if (int rc = track_external(d, t.d_stage.get(), mask ? t.d_stage_mask.get() : nullptr, nullptr)) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_set_states_device(void* dswarm, const double* d_states, const uint8_t* d_mask, void* hip_stream) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!d_states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states_device: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  HIP_TRY(hipSetDevice(d->device));
+  if (int rc = track_records_ready(d)) return rc;
+  return track_external(d, d_states, d_mask, static_cast<hipStream_t>(hip_stream));
+}
+
+int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!out && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_track_records: null argument");
+  if (d->n_local == 0) return HDSM_OK;
+  if (!d->track.d_rec) {
+    for (int k = 0; k < d->n_local; ++k) out[k] = hdsm_track_record{};
+    return HDSM_OK;
+  }
+  if (int rc = device_idle(d)) return rc;
+  HIP_TRY(hipMemcpy(out, d->track.d_rec.get(), (size_t)d->n_local * sizeof(hdsm_track_record), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_track_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->track.q, out[1] = d->track.model_launches, out[2] = d->track.external_launches;
+  return HDSM_OK;
+}
+
+}  // extern "C"

@@ -906,7 +906,7 @@ int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows)
   return HDSM_OK;
 }
 
-// ---- hooks of the device-resident loop (swarm_kernels.hip; declared and described in hdsm_internal.h) ----
+// ---- hooks of the device-resident loop (dswarm_flight.cpp take_over / hand_back, dswarm_audit.hip; declared and described in hdsm_internal.h) ----
 int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id, hdsm_params* prm,
                             hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3], double worigin[3]) {
   Swarm* sw = static_cast<Swarm*>(swarm);

@@ -15,11 +15,12 @@
 //                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
 // tests/test_gpu_configs.py. AC = multi_agent_planner/src/agent_class.cpp of the reference.
+// This file is the round and nothing else: its kernels, its phases, hdsm_dswarm_create / _destroy / _round / _round_ranks and the phase
+// timing. What runs BETWEEN rounds lives in dswarm_world.hip, dswarm_audit.hip, dswarm_flight.cpp and dswarm_models.cpp (dswarm.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cfloat>
-#include <cstddef>
 #include <cstdlib>
 #include <memory>
 #include <new>
@@ -27,15 +28,11 @@
 #include <type_traits>
 #include <vector>
 
-#include "../../include/hdsm.h"
-#include "../../include/hdsm_swarm.h"
-#include "audit_device.h"
-#include "device_mem.h"
+#include "dswarm.h"
 #include "hdsm_internal.h"
 #include "link_core.h"
 #include "path_core.h"
 #include "script_device.h"
-#include "swarm_core.h"
 #include "track_device.h"
 
 #ifdef CD_PROFILE
@@ -51,24 +48,26 @@ extern "C" int hdsm_swarm_corridor_profile(unsigned long long out[16]) {
 }
 #endif
 
+using namespace hdsm_dswarm;
+
 namespace {
-
-using hdsm_sw::AgentS;
-using hdsm_sw::Cfg;
-using hdsm_sw::V3;
-
 thread_local std::string g_err;
-int fail(int code, const std::string& m) {
+}
+int hdsm_dswarm::fail(int code, const std::string& m) {
   g_err = m;
   return code;
 }
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) return fail(HDSM_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
-constexpr int PTS = hdsm_sw::PATH_PTS + 1;  // points of a reference polyline handed to k_reference
+// every event a timed round records (hdsm_dswarm_set_phase_timing; _set_audit and _set_history when the timing is already on)
+int hdsm_dswarm::timing_events(DSwarm* d) {
+  for (hdsm_mem::DevEvent& e : d->ev) HIP_TRY(e.create());
+  HIP_TRY(d->path.timed.create());
+  HIP_TRY(d->audit.timed.create());
+  return HDSM_OK;
+}
+
+namespace {
+
 // scratch of one agent's voxel decompositions, in LDS (dynamic shared memory of k_corridor): the workspace, the overlay bits and
 // the 2-bit cache of the world under the overlay. The decomposition is one lane's chain of small dependent accesses — in global
 // memory every one of them was a round trip (33 ms per round for 256 agents in the pillar forest).
@@ -76,27 +75,6 @@ constexpr size_t SLAB = hdsm_cd::WAVE_LDS_MAX;  // (the launch asks for what its
 // k_corridor also has static __shared__ state (the walk's rows and flags, < 4 KB); together they must stay inside the 64 KB a
 // kernel may use without hipFuncAttributeMaxDynamicSharedMemorySize — a growth of Work / the overlay fails HERE, not at launch
 static_assert(SLAB + 4096 <= 64 * 1024, "k_corridor: dynamic + static LDS exceed the default 64 KB limit");
-
-// The polyhedra an agent's last decompositions produced. The corridor keeps only the polyhedra the last plan used, so the ones
-// further down the path are dropped and asked for again round after round with the same seed voxel — more than half of all
-// decompositions of a forest flight. What a decomposition yields depends on the (constant) world and configuration, on the seed,
-// and on the local grid only where the growth meets the grid's border or the ground plane moves; so an entry holds the
-// polyhedron as INTEGERS relative to the seed (hdsm_cd::PolyStruct) with the seed's world voxel, the grid's offset in the world,
-// the ground plane's world level and whether everything a decomposition can look at (the seed +- wave_map_radius) lay inside the
-// grid's interior in x and y. A request for the same world voxel from a grid at the same height with that property too (or from
-// the same grid) gets its rows
-// formed from the entry — with the arithmetic a decomposition in ITS grid would use, origin included (rows_from_structure), so the
-// host mirror, which grows the polyhedron again, gets the same bits.
-constexpr int CACHE_POLYS = 6;
-constexpr int32_t kCacheHole = INT32_MIN;  // seed_w[.][0] of an entry a map update dropped (k_cache_invalidate): no request has it
-struct PolyCache {
-  hdsm_cd::PolyStruct ps[CACHE_POLYS];
-  int32_t seed_w[CACHE_POLYS][3], off[CACHE_POLYS][3], ground_w[CACHE_POLYS], interior[CACHE_POLYS];
-  int32_t n, next;
-  // what the cache did for this agent (hdsm_dswarm_cache_stats; written by lane 0 of the agent's own wavefront): polyhedra asked
-  // for, found with the same grid, found through the interior rule (another grid at the same height)
-  int32_t asked, hits_same_grid, hits_interior, pad_;
-};
 
 // GenerateSafeCorridor (AC:1236-1447), ONE WAVEFRONT PER AGENT. The walk along the path (steps of voxel / 10: hundreds of
 // them per round) tests every sample against every row of the kept polyhedra; with one thread per agent each test was a chain of
@@ -573,127 +551,6 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t
     for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.p.out[t / 3][t % 3];
 }
 
-// ---- map updates in flight (ABI 1.7) ----
-// values [bdim[2]][bdim[1]][bdim[0]] into the box lo .. lo + bdim of a grid [.][ny][nx]: thread <-> up to four voxels of one row
-__global__ __launch_bounds__(256) void k_box_put(const int8_t* __restrict__ vals, int8_t* __restrict__ grid, int nx, int ny, int lx, int ly, int lz,
-                                                 int bx, int by, int bz) {
-  const int qpr = (bx + 3) / 4, rows = by * bz;
-  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < qpr * rows; q += gridDim.x * blockDim.x) {
-    const int row = q / qpr, x0 = (q - row * qpr) * 4, z = row / by, y = row - z * by;
-    const int n = bx - x0 < 4 ? bx - x0 : 4;
-    const int8_t* in = vals + (size_t)row * bx + x0;
-    int8_t* out = grid + ((size_t)(lz + z) * ny + (ly + y)) * nx + (lx + x0);
-    if (n == 4) __builtin_memcpy(out, in, 4);
-    else
-      for (int k = 0; k < n; ++k) out[k] = in[k];
-  }
-}
-
-// The polyhedron cache after voxels lo .. hi (inclusive, world voxels) were written: one lane per (agent, entry). An entry whose
-// decomposition could have looked at a written voxel — its seed +- (rad + 1): wave_map_radius and one voxel of margin — is dropped,
-// the others stay. A dropped entry becomes a hole: its seed voxel is set to kCacheHole, so it is never found again, and the agent's
-// n / next are left as they are; the next polyhedron k_corridor records goes into the first hole, so the agent keeps its six slots.
-// (An entry is read only through the comparison of its seed voxel, so nothing else of it needs clearing.)
-__global__ __launch_bounds__(256) void k_cache_invalidate(PolyCache* cache, int n_agents, int rad, int lx, int ly, int lz, int hx, int hy, int hz,
-                                                          unsigned long long* dropped) {
-  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (t >= n_agents * CACHE_POLYS) return;
-  PolyCache& pc = cache[t / CACHE_POLYS];
-  const int e = t % CACHE_POLYS;
-  if (e >= pc.n || pc.seed_w[e][0] == kCacheHole) return;
-  const int sx = pc.seed_w[e][0], sy = pc.seed_w[e][1], sz = pc.seed_w[e][2];
-  const bool meets = sx + rad >= lx && sx - rad <= hx && sy + rad >= ly && sy - rad <= hy && sz + rad >= lz && sz - rad <= hz;
-  if (!meets) return;
-  pc.seed_w[e][0] = kCacheHole;
-  atomicAdd(dropped, 1ull);
-}
-
-using hdsm_mem::DevBuf;
-
-// the path step (k_path): period and round phase of the host mirror, the agents due at the next round (hdsm_dswarm_set_goals) and
-// their list on the device, every agent's goal (host copy + device), counters [planned, failed], launches, the timed interval
-struct PathStep {
-  int period = 0;
-  long long round = 0, launches = 0;
-  std::vector<uint8_t> due;
-  std::vector<double> goals;
-  int n_due = 0;
-  DevBuf<int32_t> d_due;
-  DevBuf<double> d_goals;
-  DevBuf<unsigned long long> d_cnt;
-  hdsm_mem::TimedInterval timed;
-  // the clearance mode (hdsm_swarm_set_path_clearance before hdsm_dswarm_create): k_dmp instead of k_path, the mask's rows on the device
-  bool dmp = false;
-  int dmp_rn = 0;
-  DevBuf<uint32_t> d_dmp_rows;
-};
-
-// the flight audit (audit_kernels.hip; opt-in: nothing is allocated or launched while it and the history are off)
-struct Audit {
-  bool on = false, ever = false;
-  long long rounds = 0;  // rounds audited by this dswarm (hdsm_dswarm_last_audit_round needs one)
-  double sep_warn = 1.0;
-  hdsm_audit::DeviceBufs buf;
-  DevBuf<hdsm_flight_report> d_report;
-  hdsm_mem::TimedInterval timed;  // the audit's launches of a round, the history write included
-};
-
-// the state history (opt-in, written by the audit's last kernel): rows [cap][n_local][9]
-struct History {
-  DevBuf<double> d_rows;
-  int cap = 0, n = 0, dropped = 0, delivered = 0;
-  bool last = false;  // the last round wrote row n - 1 (a state taken from outside behind that round replaces the agent's entry of it)
-};
-
-// map updates in flight (nothing is allocated or launched before the first hdsm_dswarm_update_world* / _set_raw_world): the
-// resident raw grid with the map configuration and the scratch of the region pre-processing, the staging buffer of the
-// host-pointer forms, updates applied, voxels written, and the device's count of cache entries dropped
-struct WorldEdits {
-  DevBuf<int8_t> d_raw;
-  DevBuf<uint8_t> d_map_scr;
-  hdsm_map_config mcfg{};
-  DevBuf<int8_t> d_edit;
-  size_t edit_cap = 0;
-  long long updates = 0, voxels = 0;
-  DevBuf<unsigned long long> d_dropped;
-};
-
-// link faults (hdsm_dswarm_set_links; nothing is allocated or launched before the first call): the fate table, the ring of the last
-// rounds' published records ([MAX_DELAY + 1][G][rec], allocated once at the longest a table may ask for; D + 1 of them are in use),
-// the view the next round's reference and solve read in place of the plans buffer, and the per-slot counters
-struct Links {
-  bool on = false;
-  int n_rounds = 0, D = 0, time_aware = 0;
-  int round = 0;  // the link round the next k_deliver closes (0: the first round after hdsm_dswarm_set_links)
-  hdsm_mem::GrowBuf<int8_t> d_fate;
-  DevBuf<double> d_ring, d_seen;
-  DevBuf<uint8_t> d_seen_has;
-  DevBuf<int32_t> d_seen_round, d_shift, d_cnt;
-  bool ready() const { return (bool)d_cnt; }
-};
-
-// scripted agents (hdsm_dswarm_set_script; nothing is allocated or launched before the first call that scripts somebody): the LAST n
-// ids of the shard's block are not flown — every kernel in front of k_commit runs on the n_local - n agents before them — and k_script
-// publishes their records from the tracks ([n_local][MAX_KNOTS][4] on the device, allocated once; n x n_knots of them in use).
-struct Script {
-  int n = 0, n_knots = 0, predict = 0;
-  long long round = 0;  // the script round the next k_script publishes (0: the first round after hdsm_dswarm_set_script)
-  long long launches = 0;
-  DevBuf<double> d_knots;
-};
-
-// imperfect tracking (hdsm_dswarm_set_tracking / _set_states*; nothing is allocated or launched before the first call that needs it): the
-// model while it is on, the tracking round the next k_track flies, the launches of the two forms, the record per agent ([n_local],
-// zeros at first) and the staging of the host-pointer form of a state from outside
-struct Track {
-  bool on = false;
-  hdsm_tracking model{};
-  long long q = 0, model_launches = 0, external_launches = 0;
-  DevBuf<hdsm_track_record> d_rec;
-  DevBuf<double> d_stage;
-  DevBuf<uint8_t> d_stage_mask;
-};
-
 // One link round (link_core.h, deliver_slot): a wavefront per slot of the plans buffer, four per workgroup. No LDS, no atomics: a
 // slot is touched by its own wavefront alone.
 __global__ __launch_bounds__(256) void k_deliver(hdsm_link::Round a) {
@@ -702,183 +559,15 @@ __global__ __launch_bounds__(256) void k_deliver(hdsm_link::Round a) {
   hdsm_link::deliver_slot(a, k, (int)threadIdx.x & 63, 64);
 }
 
-// ---- neighbour groups: the per-group flight summary (hdsm_dswarm_group_report) ----
-// One wavefront per group over the group's LOCAL agents [max(lo, first), min(hi, first + n_local)), 64 at a time; groups larger than
-// a wavefront loop. Every figure is an integer sum, a minimum or a maximum, reduced over the wave by butterflies: the result does not
-// depend on the order. The separation minimum orders (sep2_min, agent id) — a total order: ties go to the lower agent id. No atomics,
-// no LDS. report == nullptr (the audit was never on): the audit fields are zeros and -1. With the audit on, a group without a pair
-// (one agent) has sep2_min = DBL_MAX and sep_agent = -1, as in an empty hdsm_flight_report.
-template <class T>
-__device__ __forceinline__ T wave_xor(T v, int m) {
-  return __shfl_xor(v, m, 64);
-}
-__global__ __launch_bounds__(64) void k_group_report(int first, int n_local, const int32_t* __restrict__ gstart, const AgentS* __restrict__ agents,
-                                                     const int32_t* __restrict__ status, const hdsm_flight_report* __restrict__ report,
-                                                     hdsm_group_report* __restrict__ out) {
-  const int g = (int)blockIdx.x, lane = (int)threadIdx.x;
-  const int lo = gstart[g], hi = gstart[g + 1];
-  const int l0 = lo > first ? lo : first, l1 = hi < first + n_local ? hi : first + n_local;
-  long long no_sol = 0, failed = 0, rounds = 0, positions = 0, close_r = 0, occupied = 0, unknown = 0, crossed = 0, pot = 0;
-  double dist_goal = 0.0, speed_max = 0.0, q = DBL_MAX;
-  int q_agent = -1, q_partner = -1, q_sub = 0;
-  long long q_round = -1;
-  for (int a = l0 + lane; a < l1; a += 64) {
-    const int k = a - first;
-    const AgentS& ag = agents[k];
-    no_sol += status[k] == HDSM_NO_SOLUTION, failed += ag.n_fail;
-    const double dg = hdsm_sw::norm(hdsm_sw::sub(V3{{ag.state_curr[0], ag.state_curr[1], ag.state_curr[2]}}, ag.goal));
-    dist_goal = dg > dist_goal ? dg : dist_goal;
-    if (report != nullptr) {
-      const hdsm_flight_report r = report[k];
-      rounds = r.rounds > rounds ? r.rounds : rounds;
-      positions += r.positions, close_r += r.close_rounds, occupied += r.occupied, unknown += r.unknown, crossed += r.crossed, pot += r.pot_sum;
-      speed_max = r.speed_max > speed_max ? r.speed_max : speed_max;
-      if (r.sep_partner >= 0 && (q_agent < 0 || r.sep2_min < q))  // (ids ascend within a lane: '<' keeps the lower one)
-        q = r.sep2_min, q_agent = a, q_partner = r.sep_partner, q_sub = r.sep_substep, q_round = r.sep_round;
-    }
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    no_sol += wave_xor(no_sol, m), failed += wave_xor(failed, m), positions += wave_xor(positions, m), close_r += wave_xor(close_r, m);
-    occupied += wave_xor(occupied, m), unknown += wave_xor(unknown, m), crossed += wave_xor(crossed, m), pot += wave_xor(pot, m);
-    const long long o_rounds = wave_xor(rounds, m);
-    rounds = o_rounds > rounds ? o_rounds : rounds;
-    const double o_dg = wave_xor(dist_goal, m), o_sp = wave_xor(speed_max, m);
-    dist_goal = o_dg > dist_goal ? o_dg : dist_goal, speed_max = o_sp > speed_max ? o_sp : speed_max;
-    const double o_q = wave_xor(q, m);
-    const int o_agent = wave_xor(q_agent, m), o_partner = wave_xor(q_partner, m), o_sub = wave_xor(q_sub, m);
-    const long long o_round = wave_xor(q_round, m);
-    if (o_agent >= 0 && (q_agent < 0 || o_q < q || (o_q == q && o_agent < q_agent)))
-      q = o_q, q_agent = o_agent, q_partner = o_partner, q_sub = o_sub, q_round = o_round;
-  }
-  if (lane == 0) {
-    hdsm_group_report r;
-    r.first = lo, r.count = hi - lo, r.n_local = l1 > l0 ? l1 - l0 : 0, r.no_solution_last = (int32_t)no_sol;
-    r.failed_total = failed, r.dist_goal_max = dist_goal;
-    r.rounds = rounds, r.positions = positions, r.close_rounds = close_r, r.occupied = occupied, r.unknown = unknown, r.crossed = crossed;
-    r.pot_sum = pot, r.sep2_min = report != nullptr ? q : 0.0, r.sep_agent = q_agent, r.sep_partner = q_partner, r.sep_substep = q_sub, r.reserved0 = 0;
-    r.sep_round = q_round, r.speed_max = speed_max;
-    out[g] = r;
-  }
-}
-
-struct DSwarm {
-  void* solver = nullptr;
-  int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
-  hdsm_params prm{};
-  hdsm_swarm_config cfg{};
-  hdsm_ref_config rcfg{};
-  Cfg c{};
-  DevBuf<AgentS> d_agents;
-  DevBuf<PolyCache> d_cache;  // [n_local], worlds only (HDSM_POLY_CACHE=0: none)
-  DevBuf<int8_t> d_world;
-  DevBuf<double> d_cap, d_path, d_ref_full, d_ref, d_pv, d_state, d_A, d_b, d_traj, d_ctrl, d_obj, d_local, d_plans;
-  DevBuf<int32_t> d_npath, d_id, d_npoly, d_nrows, d_status, d_fails;
-  DevBuf<uint8_t> d_used, d_has;
-  long long rounds = 0;
-  // hdsm_dswarm_set_phase_timing: HIP events between the launches of a round (development / bench aid: every record is a barrier
-  // packet in front of the next kernel, so a timed round is a few us longer than a plain one — ms_per_round is never taken from it)
-  bool phase_timing = false, phase_valid = false;
-  hdsm_mem::DevEvent ev[8];
-  PathStep path;
-  Audit audit;
-  History hist;
-  WorldEdits edits;
-  Links links;
-  Script script;
-  Track track;
-  int n_fly() const { return n_local - script.n; }  // the agents this shard plans for: all but its scripted tail
-  // neighbour groups (taken from the mirror by hdsm_dswarm_create; one group = the whole swarm without a partition): the
-  // partition, the id range per record of the plans buffer ([per * world][2], for the audit; null without a partition), the report
-  std::vector<int32_t> group_start;
-  bool grouped = false;
-  DevBuf<int32_t> d_gstart, d_range;
-  DevBuf<hdsm_group_report> d_greport;
-};
-
-// every event a timed round records (hdsm_dswarm_set_phase_timing; _set_audit and _set_history when the timing is already on)
-int timing_events(DSwarm* d) {
-  for (hdsm_mem::DevEvent& e : d->ev) HIP_TRY(e.create());
-  HIP_TRY(d->path.timed.create());
-  HIP_TRY(d->audit.timed.create());
-  return HDSM_OK;
-}
-
-// the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports
-int audit_setup(DSwarm* d, const hdsm_flight_report* init) {
-  Audit& a = d->audit;
-  if (!a.buf.d_round) {
-    if (hdsm_audit::device_alloc(&a.buf, d->per * d->world, d->n_local, d->c.step_plan) != hipSuccess)
-      return fail(HDSM_ERR_DEVICE, "flight audit: allocation failed");
-  }
-  if (!a.d_report && (init != nullptr || a.on)) {
-    std::vector<hdsm_flight_report> rep((size_t)d->n_local);
-    for (int k = 0; k < d->n_local; ++k) {
-      if (init) rep[k] = init[k];
-      else hdsm_audit::empty_report(&rep[k]);
-    }
-    HIP_TRY(a.d_report.alloc(rep.size() + 1));
-    if (!rep.empty()) HIP_TRY(hipMemcpy(a.d_report.get(), rep.data(), rep.size() * sizeof(hdsm_flight_report), hipMemcpyHostToDevice));
-    a.ever = true;
-  }
-  return HDSM_OK;
-}
-
-// the box lo .. lo + bdim inside the device world? (0 empty, 1 yes, < 0 an error)
-int world_box(DSwarm* d, const int32_t* lo, const int32_t* bdim) {
-  if (!d || !lo || !bdim) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world (hdsm_swarm_set_world before hdsm_dswarm_create)");
-  for (int ax = 0; ax < 3; ++ax)
-    if (bdim[ax] < 0 || lo[ax] < 0 || lo[ax] > d->c.wdim[ax] || bdim[ax] > d->c.wdim[ax] - lo[ax])
-      return fail(HDSM_ERR_BAD_ARG, "the box does not lie inside the world");
-  return (bdim[0] == 0 || bdim[1] == 0 || bdim[2] == 0) ? 0 : 1;
-}
-
-// values (device) into the box of `grid` (the device world or the resident raw grid), on st
-int put_box(DSwarm* d, const int8_t* d_vals, int8_t* grid, const int32_t lo[3], const int32_t bdim[3], hipStream_t st) {
-  const int quads = ((bdim[0] + 3) / 4) * bdim[1] * bdim[2];
-  hipLaunchKernelGGL(k_box_put, dim3((unsigned)std::min((quads + 255) / 256, 4096)), dim3(256), 0, st, d_vals, grid, d->c.wdim[0], d->c.wdim[1], lo[0],
-                     lo[1], lo[2], bdim[0], bdim[1], bdim[2]);
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
-
-// drops the cache entries that could have looked at the written voxels wlo .. wlo + wdim (NULL: every entry), on st, and books the update
-int invalidate(DSwarm* d, const int32_t* wlo, const int32_t* wdim, hipStream_t st) {
-  if (!d->edits.d_dropped) HIP_TRY(d->edits.d_dropped.alloc_zeroed(1));
-  if (!d->d_cache || d->n_local == 0) return HDSM_OK;
-  const int rad = hdsm_cd::wave_map_radius(d->c.n_it_decomp) + 1;
-  const int big = 1 << 29;
-  const int l[3] = {wlo ? wlo[0] : -big, wlo ? wlo[1] : -big, wlo ? wlo[2] : -big};
-  const int h[3] = {wlo ? wlo[0] + wdim[0] - 1 : big, wlo ? wlo[1] + wdim[1] - 1 : big, wlo ? wlo[2] + wdim[2] - 1 : big};
-  hipLaunchKernelGGL(k_cache_invalidate, dim3((unsigned)((d->n_local * CACHE_POLYS + 255) / 256)), dim3(256), 0, st, d->d_cache.get(), d->n_local, rad, l[0],
-                     l[1], l[2], h[0], h[1], h[2], d->edits.d_dropped.get());
-  HIP_TRY(hipGetLastError());
-  return HDSM_OK;
-}
-
-// the host values of a box into the staging buffer (the device is idle: the callers have synchronised)
-int stage_box(DSwarm* d, const int8_t* values, const int32_t bdim[3]) {
-  WorldEdits& w = d->edits;
-  const size_t bytes = (size_t)bdim[0] * bdim[1] * bdim[2];
-  if (bytes > w.edit_cap) {
-    w.edit_cap = 0;
-    HIP_TRY(w.d_edit.alloc(bytes));
-    w.edit_cap = bytes;
-  }
-  HIP_TRY(hipMemcpy(w.d_edit.get(), values, bytes, hipMemcpyHostToDevice));
-  return HDSM_OK;
-}
-
 // every buffer a round of n_local agents in a world of hworld's size needs, zero-filled
 hipError_t alloc_round_buffers(DSwarm* d, const int8_t* hworld) {
   const Cfg& c = d->c;
-  const size_t n = (size_t)d->n_local, L = (size_t)d->per, G = (size_t)d->per * d->world, N = (size_t)c.N, P = (size_t)c.P, RS = (size_t)c.RS,
-               REC = (N + 1) * 9;
+  const size_t n = (size_t)d->n_local, L = (size_t)d->per, G = (size_t)d->slots(), N = (size_t)c.N, P = (size_t)c.P, RS = (size_t)c.RS,
+               REC = (size_t)d->rec();
   hdsm_mem::FirstError ok;
   ok(d->d_agents.alloc_zeroed(n));
   if (hworld) {
-    ok(d->d_world.alloc_zeroed((size_t)c.wdim[0] * c.wdim[1] * c.wdim[2]));
+    ok(d->d_world.alloc_zeroed(d->voxels()));
     bool cache_on = true;  // development switch (A/B): HDSM_POLY_CACHE=0 grows every polyhedron again
     if (const char* pcenv = std::getenv("HDSM_POLY_CACHE")) cache_on = !(pcenv[0] == '0' && pcenv[1] == 0);
     if (cache_on) ok(d->d_cache.alloc_zeroed(n));
@@ -891,96 +580,6 @@ hipError_t alloc_round_buffers(DSwarm* d, const int8_t* hworld) {
   ok(d->d_local.alloc_zeroed(L * REC)), ok(d->d_plans.alloc_zeroed(G * REC)), ok(d->d_has.alloc_zeroed(G)), ok(d->d_fails.alloc_zeroed(1));
   ok(d->path.d_due.alloc_zeroed(n)), ok(d->path.d_goals.alloc_zeroed(n * 3)), ok(d->path.d_cnt.alloc_zeroed(2));
   return ok.e;
-}
-
-// The mirror's flight becomes the device's (hdsm_dswarm_create, after alloc_round_buffers): the path step's phase and pending agents,
-// the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the audit's setting and record.
-int take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
-  const size_t n = (size_t)d.n_local;
-  PathStep& p = d.path;
-  const auto refused = [](int rc) { return fail(rc, "hdsm_dswarm_create: export failed"); };
-  p.due.assign(n, 0), p.goals.assign(n * 3, 0.0);
-  int32_t period = 0;
-  int64_t round = 0;
-  if (int rc = hdsm_swarm_export_path_state(swarm, &period, &round, p.due.data())) return refused(rc);
-  p.period = period, p.round = round;
-  double rad = 0;
-  if (int rc = hdsm_swarm_export_path_clearance(swarm, &rad)) return refused(rc);
-  if (rad != 0) {
-    hdsm_path::DmpMask mask{};
-    if (!hdsm_path::dmp_build_mask(rad, d.cfg.voxel_size, &mask)) return refused(HDSM_ERR_BAD_ARG);
-    p.dmp = true, p.dmp_rn = mask.rn;
-    HIP_TRY(p.d_dmp_rows.alloc_zeroed(sizeof mask.rows / sizeof mask.rows[0]));
-    HIP_TRY(hipMemcpy(p.d_dmp_rows.get(), mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
-  }
-  if (n) {
-    std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
-    if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
-    if (int rc = hdsm_swarm_export_state(swarm, tmp.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return refused(rc);
-    HIP_TRY(hipMemcpy(d.d_agents.get(), tmp.get(), n * sizeof(AgentS), hipMemcpyHostToDevice));
-    // the agent ids of the shard (a contiguous block), the goals, and the agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
-    std::vector<int32_t> ids(n, 0), idx;
-    for (size_t k = 0; k < n; ++k) {
-      for (int q = 0; q < 3; ++q) p.goals[3 * k + q] = tmp[k].goal[q];
-      ids[k] = d.first + (int)k;
-      if (p.due[k]) idx.push_back((int32_t)k);
-    }
-    p.n_due = (int)idx.size();
-    HIP_TRY(hipMemcpy(d.d_id.get(), ids.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), n * 3 * sizeof(double), hipMemcpyHostToDevice));
-    if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  }
-  if (hworld) HIP_TRY(hipMemcpy(d.d_world.get(), hworld, (size_t)d.c.wdim[0] * d.c.wdim[1] * d.c.wdim[2], hipMemcpyHostToDevice));
-  d.c.world = d.d_world.get();
-  {  // the mirror's partition goes onto the solver handle (none: the handle's is cleared) and, for the audit, into a range table
-    int32_t ng = 0;
-    if (int rc = hdsm_swarm_export_groups(swarm, &ng, nullptr)) return refused(rc);
-    d.grouped = ng > 0;
-    d.group_start.assign((size_t)(d.grouped ? ng + 1 : 2), 0);
-    if (d.grouped) {
-      if (int rc = hdsm_swarm_export_groups(swarm, &ng, d.group_start.data())) return refused(rc);
-    } else {
-      d.group_start[1] = d.n_rob;
-    }
-    if (int rc = hdsm_set_groups(d.solver, d.grouped ? ng : 0, d.grouped ? d.group_start.data() : nullptr))
-      return fail(rc, std::string("hdsm_set_groups: ") + hdsm_last_error());
-    HIP_TRY(hipSetDevice(d.device));  // (the handle may live on another device)
-    if (d.grouped) {
-      const size_t G = (size_t)d.per * d.world;
-      std::vector<int32_t> table(2 * G + 2, 0);
-      for (int g = 0; g < ng; ++g)
-        for (int k = d.group_start[g]; k < d.group_start[g + 1]; ++k) table[2 * (size_t)k] = d.group_start[g], table[2 * (size_t)k + 1] = d.group_start[g + 1];
-      HIP_TRY(d.d_range.alloc(table.size()));
-      HIP_TRY(hipMemcpy(d.d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-  }
-  int32_t on = 0, ever = 0;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
-  if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, nullptr)) return refused(rc);
-  if (ever) {
-    std::vector<hdsm_flight_report> rep(n);
-    if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, rep.data())) return refused(rc);
-    d.audit.on = on != 0;
-    if (int rc = audit_setup(&d, rep.data())) return rc;
-  }
-  return HDSM_OK;
-}
-
-// The device's flight back into the mirror (hdsm_dswarm_download; the device is idle): the agent states, the path step's phase,
-// pending agents and goals, the audit's setting and record.
-int hand_back(DSwarm& d, void* swarm) {
-  const size_t n = (size_t)d.n_local;
-  std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
-  if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
-  int rc = hipMemcpy(tmp.get(), d.d_agents.get(), n * sizeof(AgentS), hipMemcpyDeviceToHost) == hipSuccess
-               ? hdsm_swarm_import_state(swarm, tmp.get(), d.n_local)
-               : HDSM_ERR_DEVICE;
-  if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d.path.period, d.path.round, d.path.due.data(), d.path.goals.data());
-  if (rc == HDSM_OK && d.audit.ever) {
-    std::vector<hdsm_flight_report> rep(n);
-    if (hipMemcpy(rep.data(), d.audit.d_report.get(), n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
-    else rc = hdsm_swarm_import_audit(swarm, d.audit.on ? 1 : 0, d.audit.sep_warn, rep.data());
-  }
-  return rc ? fail(rc, "state download failed") : HDSM_OK;
 }
 
 // ---- the phases of hdsm_dswarm_round, in the order of the header comment; every one issues on st and returns at its first error ----
@@ -1020,7 +619,7 @@ int path_step(DSwarm& d, hipStream_t st) {
 
 // k_corridor, k_vel_cap, the reference, k_keep_free and the solve (marks 0 to 4)
 int corridor_to_solve(DSwarm& d, hipStream_t st) {
-  const int n = d.n_fly(), G = d.per * d.world;
+  const int n = d.n_fly(), G = d.slots();
   PHASE_MARK(0);
   if (n == 0) {
     for (int k = 1; k <= 4; ++k) PHASE_MARK(k);
@@ -1081,7 +680,7 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
     if (int rc = hdsm_internal_local_commit_gate(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());
   const int n_fly = d.n_fly();
   hipLaunchKernelGGL(k_commit, dim3((unsigned)(d.per > 0 ? d.per : 1)), dim3(64), 0, st, d.c, n_fly, d.per, d.d_agents.get(), d.d_traj.get(),
-                     d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), direct ? d.d_plans.get() : d.d_local.get(), d.d_fails.get(),
+                     d.d_ctrl.get(), d.d_used.get(), d.d_status.get(), d.publish_to(direct), d.d_fails.get(),
                      direct ? d.d_has.get() : nullptr, d.d_ref_full.get(), d.d_pv.get());
   HIP_TRY(hipGetLastError());
   if (Track& t = d.track; t.on) {  // the flown agents fly something else than they planned (inside phase [5]; the records above stay the plans)
@@ -1094,9 +693,8 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
     ++t.q;
   }
   if (Script& s = d.script; s.n > 0) {  // the scripted tail, over the slots k_commit has just padded (and inside its phase [5])
-    const size_t rec = (size_t)(d.c.N + 1) * 9;
     HIP_TRY(hdsm_script::launch(hdsm_script::Round{s.n, s.n_knots, d.c.N, d.c.step_plan, s.predict, s.round, d.prm.dt, s.d_knots.get(),
-                                                   (direct ? d.d_plans.get() : d.d_local.get()) + (size_t)n_fly * rec,
+                                                   d.publish_to(direct) + (size_t)n_fly * d.rec(),
                                                    direct ? d.d_has.get() + n_fly : nullptr, d.d_status.get() + n_fly, d.d_agents.get() + n_fly},
                                 st));
     ++s.round, ++s.launches;
@@ -1127,12 +725,12 @@ int exchange(DSwarm& d, void* comm, void* local, hipStream_t st) {
 // link faults: the records the exchange has just left in the plans buffer meet their fates (k_deliver; only while links are on)
 hdsm_link::Round link_round(const DSwarm& d) {
   const Links& l = d.links;
-  return hdsm_link::Round{d.per * d.world, d.n_rob, d.c.N, d.c.step_plan, l.n_rounds, l.D, l.time_aware, l.round, l.d_fate.get(), d.d_plans.get(),
+  return hdsm_link::Round{d.slots(), d.n_rob, d.c.N, d.c.step_plan, l.n_rounds, l.D, l.time_aware, l.round, l.d_fate.get(), d.d_plans.get(),
                           l.d_ring.get(), l.d_seen.get(), l.d_seen_has.get(), l.d_seen_round.get(), l.d_shift.get(), l.d_cnt.get()};
 }
 int deliver(DSwarm& d, hipStream_t st) {
   Links& l = d.links;
-  const int G = d.per * d.world;
+  const int G = d.slots();
   if (!l.on || G == 0) return HDSM_OK;
   hipLaunchKernelGGL(k_deliver, dim3((unsigned)((G + 3) / 4)), dim3(256), 0, st, link_round(d));
   HIP_TRY(hipGetLastError());
@@ -1209,32 +807,12 @@ extern "C" {
 
 const char* hdsm_dswarm_last_error(void) { return g_err.c_str(); }
 
-// The flight per group (one record for the whole swarm without a partition): k_group_report over the agents' states, the last
-// statuses and — once the audit has been on — the flight records. Launched here and nowhere else: a round never pays for it.
-int hdsm_dswarm_group_report(void* dswarm, hdsm_group_report* out) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  const int ng = (int)d->group_start.size() - 1;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (!d->d_gstart) {
-    HIP_TRY(d->d_gstart.alloc(d->group_start.size()));
-    HIP_TRY(hipMemcpy(d->d_gstart.get(), d->group_start.data(), d->group_start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(d->d_greport.alloc((size_t)ng));
-  }
-  hipLaunchKernelGGL(k_group_report, dim3((unsigned)ng), dim3(64), 0, nullptr, d->first, d->n_local, d->d_gstart.get(), d->d_agents.get(), d->d_status.get(),
-                     d->audit.ever ? d->audit.d_report.get() : nullptr, d->d_greport.get());
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(out, d->d_greport.get(), (size_t)ng * sizeof(hdsm_group_report), hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
 // Where a round of the device-resident loop goes, measured with HIP events on the round's own stream: the records sit between the
 // launches of hdsm_dswarm_round — [0] k_corridor, [1] k_vel_cap, [2] hdsm_reference_device (pack + reference), [3] k_keep_free,
 // [4] hdsm_replan_device (pre-pass, solver kernels, merge), [5] k_commit, [6] the exchange. hdsm_dswarm_last_phase_ms synchronises
 // with the last timed round and returns the seven durations in milliseconds (a phase the round did not launch: ~0).
 int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  DSwarm* d = as_dswarm(dswarm);
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   HIP_TRY(hipSetDevice(d->device));
   if (on)
@@ -1243,27 +821,8 @@ int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on) {
   return HDSM_OK;
 }
 
-// The polyhedron cache of the device corridor (k_corridor, PolyCache), summed over the shard's agents since hdsm_dswarm_create:
-// out[0] polyhedra asked for, out[1] formed from a cached structure recorded in the same local grid, out[2] formed from one recorded in
-// ANOTHER grid at the same height (the interior rule), out[3] = 1 if the cache is on (HDSM_POLY_CACHE, a world is set), else 0.
-int hdsm_dswarm_cache_stats(void* dswarm, int64_t out[4]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (!d->d_cache || d->n_local == 0) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  out[3] = 1;
-  // (only the four counters of every entry travel: one strided 2-D copy)
-  std::vector<int32_t> cnt((size_t)d->n_local * 4);
-  HIP_TRY(hipMemcpy2D(cnt.data(), 16, reinterpret_cast<const char*>(d->d_cache.get()) + offsetof(PolyCache, asked), sizeof(PolyCache), 16,
-                      (size_t)d->n_local, hipMemcpyDeviceToHost));
-  for (int k = 0; k < d->n_local; ++k) out[0] += cnt[4 * (size_t)k], out[1] += cnt[4 * (size_t)k + 1], out[2] += cnt[4 * (size_t)k + 2];
-  return HDSM_OK;
-}
-
 int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  DSwarm* d = as_dswarm(dswarm);
   if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
   if (!d->phase_valid) return fail(HDSM_ERR_BAD_ARG, "no round has run with hdsm_dswarm_set_phase_timing on");
   HIP_TRY(hipSetDevice(d->device));
@@ -1275,51 +834,13 @@ int hdsm_dswarm_last_phase_ms(void* dswarm, float ms[7]) {
 // The path step of the last timed round that launched k_path, in milliseconds (0 if it planned no agent): kept out of
 // hdsm_dswarm_last_phase_ms, whose [0] k_corridor starts after it.
 int hdsm_dswarm_last_path_ms(void* dswarm, float* ms) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  DSwarm* d = as_dswarm(dswarm);
   if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
   if (!d->phase_valid) return fail(HDSM_ERR_BAD_ARG, "no round has run with hdsm_dswarm_set_phase_timing on");
   *ms = 0.0f;
   if (!d->path.timed.valid) return HDSM_OK;
   HIP_TRY(hipSetDevice(d->device));
   HIP_TRY(d->path.timed.ms(ms));
-  return HDSM_OK;
-}
-
-// GoalCallback (AC:2380-2388) for the shard: goals [n_local][3]; the agents whose goal changed plan a new path at the start of
-// the next round (k_path). Synchronises the device.
-int hdsm_dswarm_set_goals(void* dswarm, const double* goals) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (!goals && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (d->n_local == 0) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  PathStep& p = d->path;
-  for (int k = 0; k < d->n_local; ++k) {
-    double* g = &p.goals[3 * (size_t)k];
-    const double* ng = goals + 3 * (size_t)k;
-    if (g[0] == ng[0] && g[1] == ng[1] && g[2] == ng[2]) continue;
-    g[0] = ng[0], g[1] = ng[1], g[2] = ng[2];
-    p.due[k] = 1;
-  }
-  std::vector<int32_t> idx;
-  for (int k = 0; k < d->n_local; ++k)
-    if (p.due[k]) idx.push_back(k);
-  p.n_due = (int)idx.size();
-  HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), p.goals.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  return HDSM_OK;
-}
-
-// out[0] agents planned by k_path since hdsm_dswarm_create, out[1] of them without a new path, out[2] launches of k_path.
-// Synchronises the device.
-int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  unsigned long long cnt[2] = {0, 0};
-  HIP_TRY(hipMemcpy(cnt, d->path.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
-  out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path.launches;
   return HDSM_OK;
 }
 
@@ -1365,15 +886,14 @@ int hdsm_dswarm_create(void* swarm, void* solver, int32_t device, int32_t world_
 }
 
 void hdsm_dswarm_destroy(void* dswarm) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  DSwarm* d = as_dswarm(dswarm);
   if (!d) return;
-  (void)hipSetDevice(d->device);
-  (void)hipDeviceSynchronize();
+  (void)device_idle(d);
   delete d;
 }
 
 int hdsm_dswarm_round(void* dswarm, void* comm, void* hip_stream) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
+  DSwarm* d = as_dswarm(dswarm);
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   if (d->world > 1 && !comm) return fail(HDSM_ERR_BAD_ARG, "a sharded swarm needs a communicator");
   if (comm) {
@@ -1391,11 +911,11 @@ int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* co
   if (world < 1 || !dswarms || !comms) return fail(HDSM_ERR_BAD_ARG, "bad hdsm_dswarm_round_ranks argument");
   for (int r = 0; r < world; ++r)
     if (!dswarms[r] || !comms[r]) return fail(HDSM_ERR_BAD_ARG, "null dswarm or communicator of rank " + std::to_string(r));
-  const DSwarm* d0 = static_cast<const DSwarm*>(dswarms[0]);
-  if (int rc = hdsm_internal_local_check(world, comms, (d0->c.N + 1) * 9)) return fail(rc, std::string("hdsm_dswarm_round_ranks: ") + hdsm_last_error());
+  const DSwarm* d0 = as_dswarm(dswarms[0]);
+  if (int rc = hdsm_internal_local_check(world, comms, d0->rec())) return fail(rc, std::string("hdsm_dswarm_round_ranks: ") + hdsm_last_error());
   std::vector<const double*> send((size_t)world);
   for (int r = 0; r < world; ++r) {
-    const DSwarm* d = static_cast<const DSwarm*>(dswarms[r]);
+    const DSwarm* d = as_dswarm(dswarms[r]);
     for (int q = 0; q < r; ++q)
       if (dswarms[q] == dswarms[r]) return fail(HDSM_ERR_BAD_ARG, "the dswarm of rank " + std::to_string(q) + " is given again for rank " + std::to_string(r));
     // (the gather of every rank copies per * rec doubles out of every send buffer: one n_rob, one n_hor)
@@ -1409,471 +929,17 @@ int hdsm_dswarm_round_ranks(int32_t world, void* const* dswarms, void* const* co
   if (int rc = hdsm_internal_local_bind(world, comms, send.data(), d0->per)) return fail(rc, std::string("hdsm_dswarm_round_ranks: ") + hdsm_last_error());
   // every "published" is recorded (front) before a gather waits for it (back); every "gathered" before the next round's k_commit does
   for (int r = 0; r < world; ++r) {
-    DSwarm* d = static_cast<DSwarm*>(dswarms[r]);
+    DSwarm* d = as_dswarm(dswarms[r]);
     HIP_TRY(hipSetDevice(d->device));
     hipStream_t st = static_cast<hipStream_t>(hip_streams ? hip_streams[r] : nullptr);
     DoneOnce done_once(d->solver, st);
     if (int rc = round_front(*d, comms[r], st)) return rc;
   }
   for (int r = 0; r < world; ++r) {
-    DSwarm* d = static_cast<DSwarm*>(dswarms[r]);
+    DSwarm* d = as_dswarm(dswarms[r]);
     HIP_TRY(hipSetDevice(d->device));
     if (int rc = round_back(*d, comms[r], comms[r], static_cast<hipStream_t>(hip_streams ? hip_streams[r] : nullptr))) return rc;
   }
-  return HDSM_OK;
-}
-
-// Link faults (include/hdsm_swarm.h). The call starts a new link history: the view is the plans buffer as it stands (every slot
-// delivered on time, held round -1, shift 0), the counters are zero, link round 0 is the next round.
-int hdsm_dswarm_set_links(void* dswarm, int32_t n_rounds, const int8_t* fate, int32_t time_aware) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  if (n_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: negative n_rounds");
-  Links& l = d->links;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (n_rounds == 0 || fate == nullptr) {
-    l.on = false;
-    return HDSM_OK;
-  }
-  const int D = hdsm_link::table_max_delay(n_rounds, d->n_rob, fate);
-  if (D < 0) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_links: a delay above HDSM_LINK_MAX_DELAY");
-  const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9, cells = (size_t)n_rounds * (size_t)d->n_rob;
-  l.on = false;
-  if (!l.ready()) {  // the first call: everything but the table, whose size is the caller's
-    hdsm_mem::FirstError ok;
-    ok(l.d_ring.alloc_zeroed((size_t)(hdsm_link::MAX_DELAY + 1) * G * rec)), ok(l.d_seen.alloc_zeroed(G * rec)), ok(l.d_seen_has.alloc_zeroed(G));
-    ok(l.d_seen_round.alloc(G)), ok(l.d_shift.alloc(G)), ok(l.d_cnt.alloc(G * hdsm_link::COUNTERS));
-    if (!ok.ok()) {
-      l.d_cnt.reset();
-      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_links: ") + hipGetErrorString(ok.e));
-    }
-  }
-  HIP_TRY(l.d_fate.ensure(cells, nullptr));
-  if (cells) HIP_TRY(hipMemcpy(l.d_fate.get(), fate, cells, hipMemcpyHostToDevice));
-  if (G) {
-    HIP_TRY(hipMemcpy(l.d_seen.get(), d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemcpy(l.d_seen_has.get(), d->d_has.get(), G, hipMemcpyDeviceToDevice));
-    HIP_TRY(hipMemset(l.d_seen_round.get(), 0xff, G * sizeof(int32_t)));  // -1
-    HIP_TRY(hipMemset(l.d_shift.get(), 0, G * sizeof(int32_t)));
-    HIP_TRY(hipMemset(l.d_cnt.get(), 0, G * hdsm_link::COUNTERS * sizeof(int32_t)));
-  }
-  l.n_rounds = n_rounds, l.D = D, l.time_aware = time_aware != 0, l.round = 0, l.on = true;
-  return HDSM_OK;
-}
-
-// Scripted agents (include/hdsm_swarm.h). Every refusal comes before anything is touched.
-int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, const double* knots, int32_t predict) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  Script& s = d->script;
-  if (n_script < s.n) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: n_script may stay or grow (a scripted agent has no planner state to resume from)");
-  if (n_script > d->n_local) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: more scripted agents than the shard has");
-  if (predict != 0 && predict != 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: predict is 0 or 1");
-  if (!hdsm_script::tracks_valid(n_script, n_knots, knots))
-    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: 1 .. 256 knots per track, every entry finite, times strictly increasing");
-  if (n_script == 0) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (!s.d_knots) HIP_TRY(s.d_knots.alloc((size_t)d->n_local * hdsm_script::MAX_KNOTS * 4));
-  HIP_TRY(hipMemcpy(s.d_knots.get(), knots, (size_t)n_script * n_knots * 4 * sizeof(double), hipMemcpyHostToDevice));
-  // a scripted agent's goal is its last knot, and it plans no path: the flown agents that are due stay due
-  PathStep& p = d->path;
-  const int n_fly = d->n_local - n_script;
-  std::vector<int32_t> idx;
-  for (int k = 0; k < d->n_local; ++k) {
-    if (k >= n_fly) {
-      const double* last = knots + ((size_t)(k - n_fly) * n_knots + (n_knots - 1)) * 4;
-      for (int q = 0; q < 3; ++q) p.goals[3 * (size_t)k + q] = last[1 + q];
-      p.due[(size_t)k] = 0;
-    }
-    if (p.due[(size_t)k]) idx.push_back(k);
-  }
-  p.n_due = (int)idx.size();
-  HIP_TRY(hipMemcpy(p.d_goals.get(), p.goals.data(), p.goals.size() * sizeof(double), hipMemcpyHostToDevice));
-  if (p.n_due) HIP_TRY(hipMemcpy(p.d_due.get(), idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  s.n = n_script, s.n_knots = n_knots, s.predict = predict, s.round = 0;
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_script_stats(void* dswarm, int64_t out[3]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = d->script.round, out[1] = d->script.n, out[2] = d->script.launches;
-  return HDSM_OK;
-}
-
-// Imperfect tracking (include/hdsm_swarm.h). Every refusal comes before anything is touched.
-namespace {
-// the records, allocated by the first call that needs them (the caller has set the device)
-int track_records_ready(DSwarm* d) {
-  if (!d->track.d_rec) {
-    HIP_TRY(d->track.d_rec.alloc_zeroed((size_t)d->n_local));
-    HIP_TRY(hipDeviceSynchronize());  // (the fill is done before a kernel of any stream books into them)
-  }
-  return HDSM_OK;
-}
-// a state from outside into the flown agents: k_track's external form over device arrays, on st
-int track_external(DSwarm* d, const double* d_states, const uint8_t* d_mask, hipStream_t st) {
-  Track& t = d->track;
-  const History& h = d->hist;
-  const int n_fly = d->n_fly();
-  if (n_fly > 0) {
-    // the state measured behind a round IS the state after that round: the row the round left in the history takes it too
-    double* const row = h.last && h.n > 0 ? h.d_rows.get() + (size_t)(h.n - 1) * d->n_local * 9 : nullptr;
-    HIP_TRY(hdsm_track::launch(hdsm_track::Launch{n_fly, d->c.step_plan, 0, 0.0, hdsm_tracking{}, d->d_agents.get(), t.d_rec.get(), d_states, d_mask, nullptr,
-                                                  nullptr, nullptr, nullptr, row},
-                               st));
-    ++t.external_launches;
-  }
-  return HDSM_OK;
-}
-}  // namespace
-
-int hdsm_dswarm_set_tracking(void* dswarm, const hdsm_tracking* m) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  if (m && !hdsm_track::model_valid(m))
-    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_tracking: every entry of the model finite, gust and jitter not negative");
-  Track& t = d->track;
-  if (!m && !t.on) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (m) {
-    if (int rc = track_records_ready(d)) return rc;
-    t.model = *m, t.q = 0;
-  }
-  t.on = m != nullptr;
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_set_states(void* dswarm, const double* states, const uint8_t* mask) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (!states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states: null argument");
-  if (d->n_local == 0) return HDSM_OK;
-  Track& t = d->track;
-  const size_t n = (size_t)d->n_local;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (int rc = track_records_ready(d)) return rc;
-  if (!t.d_stage) HIP_TRY(t.d_stage.alloc(n * 9));
-  if (mask && !t.d_stage_mask) HIP_TRY(t.d_stage_mask.alloc(n));
-  HIP_TRY(hipMemcpy(t.d_stage.get(), states, n * 9 * sizeof(double), hipMemcpyHostToDevice));
-  if (mask) HIP_TRY(hipMemcpy(t.d_stage_mask.get(), mask, n, hipMemcpyHostToDevice));
-  if (int rc = track_external(d, t.d_stage.get(), mask ? t.d_stage_mask.get() : nullptr, nullptr)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_set_states_device(void* dswarm, const double* d_states, const uint8_t* d_mask, void* hip_stream) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (!d_states && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_states_device: null argument");
-  if (d->n_local == 0) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  if (int rc = track_records_ready(d)) return rc;
-  return track_external(d, d_states, d_mask, static_cast<hipStream_t>(hip_stream));
-}
-
-int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (!out && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_track_records: null argument");
-  if (d->n_local == 0) return HDSM_OK;
-  if (!d->track.d_rec) {
-    for (int k = 0; k < d->n_local; ++k) out[k] = hdsm_track_record{};
-    return HDSM_OK;
-  }
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, d->track.d_rec.get(), (size_t)d->n_local * sizeof(hdsm_track_record), hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_track_stats(void* dswarm, int64_t out[3]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = d->track.q, out[1] = d->track.model_launches, out[2] = d->track.external_launches;
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_plans_device(void* dswarm, void** d_plans, void** d_has) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !d_plans || !d_has) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  *d_plans = d->d_plans.get(), *d_has = d->d_has.get();
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_link_stats(void* dswarm, int64_t out[4]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = out[1] = out[2] = out[3] = 0;
-  if (!d->links.ready()) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t G = (size_t)d->per * d->world, have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;  // (the padded tail publishes nothing)
-  std::vector<int32_t> cnt(have * hdsm_link::COUNTERS + 1);
-  if (have) HIP_TRY(hipMemcpy(cnt.data(), d->links.d_cnt.get(), have * hdsm_link::COUNTERS * sizeof(int32_t), hipMemcpyDeviceToHost));
-  for (size_t k = 0; k < have; ++k) {
-    const int32_t* c = &cnt[k * hdsm_link::COUNTERS];
-    out[1] += c[0], out[2] += c[1];
-    out[3] = c[2] > out[3] ? c[2] : out[3], out[0] = c[3] > out[0] ? c[3] : out[0];
-  }
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_download_seen(void* dswarm, double* seen_raw, uint8_t* seen_has, int32_t* seen_round, int32_t* shift) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  if (!d->links.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_download_seen: no hdsm_dswarm_set_links yet");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const Links& l = d->links;
-  const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
-  if (G == 0) return HDSM_OK;
-  if (seen_raw) HIP_TRY(hipMemcpy(seen_raw, l.d_seen.get(), G * rec * 8, hipMemcpyDeviceToHost));
-  if (seen_has) HIP_TRY(hipMemcpy(seen_has, l.d_seen_has.get(), G, hipMemcpyDeviceToHost));
-  if (seen_round) HIP_TRY(hipMemcpy(seen_round, l.d_seen_round.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (shift) HIP_TRY(hipMemcpy(shift, l.d_shift.get(), G * sizeof(int32_t), hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_download_raw(void* dswarm, double* plans_all_raw, double* send_raw) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t L = (size_t)d->per, G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
-  if (plans_all_raw && G) HIP_TRY(hipMemcpy(plans_all_raw, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
-  if (send_raw && L) HIP_TRY(hipMemcpy(send_raw, d->d_local.get(), L * rec * 8, hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_upload_plans(void* dswarm, const double* plans_all, const uint8_t* has_plan) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !plans_all || !has_plan) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9, have = (size_t)d->n_rob < G ? (size_t)d->n_rob : G;
-  HIP_TRY(hipMemset(d->d_has.get(), 0, G));
-  HIP_TRY(hipMemcpy(d->d_plans.get(), plans_all, have * rec * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d->d_has.get(), has_plan, have, hipMemcpyHostToDevice));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_download(void* dswarm, void* swarm, double* plans_all, uint8_t* has_plan, int32_t* status, int32_t* failed_total) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t n = (size_t)d->n_local, G = (size_t)d->per * d->world, rec = (size_t)(d->c.N + 1) * 9;
-  if (swarm && n)
-    if (int rc = hand_back(*d, swarm)) return rc;
-  if (plans_all) {
-    HIP_TRY(hipMemcpy(plans_all, d->d_plans.get(), G * rec * 8, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < G; ++k)
-      if (plans_all[k * rec] != plans_all[k * rec]) plans_all[k * rec] = 0.0;  // the sentinel is for the wire only
-  }
-  if (has_plan) HIP_TRY(hipMemcpy(has_plan, d->d_has.get(), G, hipMemcpyDeviceToHost));
-  if (status && n) HIP_TRY(hipMemcpy(status, d->d_status.get(), n * 4, hipMemcpyDeviceToHost));
-  if (failed_total) HIP_TRY(hipMemcpy(failed_total, d->d_fails.get(), 4, hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-// ---- the flight audit and the state history of the device loop (audit_kernels.hip) ----
-int hdsm_dswarm_set_audit(void* dswarm, int32_t on, double sep_warn) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
-  if (!(sep_warn > 0)) return fail(HDSM_ERR_BAD_ARG, "sep_warn must be positive");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  d->audit.on = on != 0, d->audit.sep_warn = sep_warn;
-  if (on) {
-    if (int rc = audit_setup(d, nullptr)) return rc;
-    if (d->phase_timing)
-      if (int rc = timing_events(d)) return rc;
-  }
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_flight_report(void* dswarm, hdsm_flight_report* report) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (d->n_local && !report)) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->audit.ever) return fail(HDSM_ERR_BAD_ARG, "the flight audit was never switched on");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (d->n_local) HIP_TRY(hipMemcpy(report, d->audit.d_report.get(), (size_t)d->n_local * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_last_audit_round(void* dswarm, hdsm_audit_round* out) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || (d->n_local && !out)) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->audit.on || d->audit.rounds == 0) return fail(HDSM_ERR_BAD_ARG, "no round has been audited (hdsm_dswarm_set_audit)");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (d->n_local) HIP_TRY(hipMemcpy(out, d->audit.buf.d_round.get(), (size_t)d->n_local * sizeof(hdsm_audit_round), hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-// The audit's launches of the last timed round (pack, sweep, track; or the history write alone), in milliseconds; 0 when that round
-// launched none or no round was timed. Kept out of hdsm_dswarm_last_phase_ms: the audit starts after its [6].
-int hdsm_dswarm_last_audit_ms(void* dswarm, float* ms) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !ms) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  *ms = 0.0f;
-  if (!d->audit.timed.valid) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(d->audit.timed.ms(ms));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_set_history(void* dswarm, int32_t capacity_rounds) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || capacity_rounds < 0) return fail(HDSM_ERR_BAD_ARG, "bad argument");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  History& h = d->hist;
-  h.d_rows.reset();
-  h.cap = 0, h.n = h.dropped = h.delivered = 0, h.last = false;
-  if (capacity_rounds > 0) {
-    if (int rc = audit_setup(d, nullptr)) return rc;
-    HIP_TRY(h.d_rows.alloc((size_t)capacity_rounds * d->n_local * 9 + 1));
-    h.cap = capacity_rounds;
-    if (d->phase_timing)
-      if (int rc = timing_events(d)) return rc;
-  }
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_download_history(void* dswarm, void* swarm, double* hist, int32_t max_rounds, int32_t* n_rounds, int32_t* dropped) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || max_rounds < 0 || (hist == nullptr && max_rounds > 0)) return fail(HDSM_ERR_BAD_ARG, "bad argument");
-  History& h = d->hist;
-  if (h.cap == 0) return fail(HDSM_ERR_BAD_ARG, "the history is off (hdsm_dswarm_set_history)");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t row = (size_t)d->n_local * 9;
-  const int n_copy = h.n < max_rounds ? h.n : max_rounds;
-  if (n_copy > 0 && row) HIP_TRY(hipMemcpy(hist, h.d_rows.get(), (size_t)n_copy * row * sizeof(double), hipMemcpyDeviceToHost));
-  if (swarm && h.n > h.delivered) {  // every recorded round reaches the mirror's planner records once
-    const int m = h.n - h.delivered;
-    std::vector<double> rows((size_t)m * row);
-    if (row) HIP_TRY(hipMemcpy(rows.data(), h.d_rows.get() + (size_t)h.delivered * row, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const int rc = hdsm_swarm_append_history(swarm, m, rows.data());
-    if (rc) return fail(rc, "hdsm_swarm_append_history");
-    h.delivered = h.n;
-  }
-  if (n_rounds) *n_rounds = h.n;
-  if (dropped) *dropped = h.dropped;
-  return HDSM_OK;
-}
-
-// ---- map updates in flight (ABI 1.7; semantics in hdsm_swarm.h) ----
-int hdsm_dswarm_update_world(void* dswarm, const int8_t* values, const int32_t lo[3], const int32_t bdim[3]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  const int k = world_box(d, lo, bdim);
-  if (k <= 0) return k;
-  if (!values) return fail(HDSM_ERR_BAD_ARG, "null values");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (int rc = stage_box(d, values, bdim)) return rc;
-  if (int rc = put_box(d, d->edits.d_edit.get(), d->d_world.get(), lo, bdim, nullptr)) return rc;
-  if (int rc = invalidate(d, lo, bdim, nullptr)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  ++d->edits.updates, d->edits.voxels += (long long)bdim[0] * bdim[1] * bdim[2];
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_set_raw_world(void* dswarm, const hdsm_map_config* map_cfg, const int8_t* raw_full) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !map_cfg || !raw_full) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world (hdsm_swarm_set_world before hdsm_dswarm_create)");
-  const size_t vox = (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2];
-  for (size_t i = 0; i < vox; ++i)
-    if (raw_full[i] != -1 && raw_full[i] != 0 && raw_full[i] != 100) return fail(HDSM_ERR_BAD_ARG, "a raw grid holds -1, 0 and 100 only");
-  if (vox < 4 || vox >= ((size_t)1 << 30)) return fail(HDSM_ERR_BAD_ARG, "a raw world needs 4 .. 2^30 - 1 voxels");
-  const int32_t zero[3] = {0, 0, 0};
-  const size_t scr = hdsm_map_region_scratch_bytes(map_cfg, d->c.wdim, zero, d->c.wdim);  // the largest box; >= the full form's 2 vox
-  if (scr == 0) return fail(HDSM_ERR_BAD_ARG, std::string("map configuration: ") + hdsm_map_last_error());
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  WorldEdits& w = d->edits;
-  {  // out of the dswarm until the new grid is in it: an allocation or a copy that fails leaves no raw world resident
-    DevBuf<int8_t> raw = std::move(w.d_raw);
-    DevBuf<uint8_t> map_scr = std::move(w.d_map_scr);
-    if (!raw) HIP_TRY(raw.alloc(vox));
-    if (!map_scr) HIP_TRY(map_scr.alloc(scr));
-    HIP_TRY(hipMemcpy(raw.get(), raw_full, vox, hipMemcpyHostToDevice));
-    w.d_raw = std::move(raw), w.d_map_scr = std::move(map_scr);
-  }
-  // (the arguments were checked above: what can still fail is a launch, and then the device world is no longer the old one —
-  // the cache is emptied on that way out too)
-  const int rc = hdsm_map_preprocess_device(d->device, map_cfg, 1, d->c.wdim, w.d_raw.get(), d->d_world.get(), w.d_map_scr.get(), nullptr);
-  if (rc == HDSM_OK) w.mcfg = *map_cfg;
-  const int rc2 = invalidate(d, nullptr, nullptr, nullptr);
-  if (rc) {
-    w.d_raw.reset();  // (no raw world is resident: the raw update calls keep refusing)
-    return fail(rc, std::string("hdsm_map_preprocess_device: ") + hdsm_map_last_error());
-  }
-  if (rc2) return rc2;
-  HIP_TRY(hipDeviceSynchronize());
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_update_world_raw_device(void* dswarm, const int8_t* d_raw_values, const int32_t lo[3], const int32_t bdim[3], void* hip_stream) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  const int k = world_box(d, lo, bdim);
-  if (k < 0) return k;
-  WorldEdits& w = d->edits;
-  if (!w.d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
-  if (k == 0) return HDSM_OK;
-  if (!d_raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
-  HIP_TRY(hipSetDevice(d->device));
-  hipStream_t st = static_cast<hipStream_t>(hip_stream);
-  int32_t wlo[3], wdim[3];
-  if (int rc = hdsm_map_region_extent(&w.mcfg, d->c.wdim, lo, bdim, wlo, wdim, nullptr, nullptr)) return fail(rc, hdsm_map_last_error());
-  if (int rc = put_box(d, d_raw_values, w.d_raw.get(), lo, bdim, st)) return rc;
-  if (int rc = hdsm_map_preprocess_region_device(d->device, &w.mcfg, d->c.wdim, w.d_raw.get(), d->d_world.get(), lo, bdim, w.d_map_scr.get(), st))
-    return fail(rc, std::string("hdsm_map_preprocess_region_device: ") + hdsm_map_last_error());
-  if (int rc = invalidate(d, wlo, wdim, st)) return rc;
-  ++w.updates, w.voxels += (long long)wdim[0] * wdim[1] * wdim[2];
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_update_world_raw(void* dswarm, const int8_t* raw_values, const int32_t lo[3], const int32_t bdim[3]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  const int k = world_box(d, lo, bdim);
-  if (k < 0) return k;
-  if (!d->edits.d_raw) return fail(HDSM_ERR_BAD_ARG, "no raw world is resident (hdsm_dswarm_set_raw_world)");
-  if (k == 0) return HDSM_OK;
-  if (!raw_values) return fail(HDSM_ERR_BAD_ARG, "null values");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (int rc = stage_box(d, raw_values, bdim)) return rc;
-  if (int rc = hdsm_dswarm_update_world_raw_device(dswarm, d->edits.d_edit.get(), lo, bdim, nullptr)) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_download_world(void* dswarm, int8_t* world) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !world) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  if (!d->c.has_world) return fail(HDSM_ERR_BAD_ARG, "the dswarm has no world");
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(world, d->d_world.get(), (size_t)d->c.wdim[0] * d->c.wdim[1] * d->c.wdim[2], hipMemcpyDeviceToHost));
-  return HDSM_OK;
-}
-
-int hdsm_dswarm_world_stats(void* dswarm, int64_t out[4]) {
-  DSwarm* d = static_cast<DSwarm*>(dswarm);
-  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
-  out[0] = d->edits.updates, out[1] = d->edits.voxels, out[2] = 0, out[3] = d->edits.d_raw ? 1 : 0;
-  if (!d->edits.d_dropped) return HDSM_OK;
-  HIP_TRY(hipSetDevice(d->device));
-  HIP_TRY(hipDeviceSynchronize());
-  unsigned long long n = 0;
-  HIP_TRY(hipMemcpy(&n, d->edits.d_dropped.get(), sizeof n, hipMemcpyDeviceToHost));
-  out[2] = (int64_t)n;
   return HDSM_OK;
 }
 

@@ -1,5 +1,5 @@
 // track_device.h — the launch interface of k_track (track_kernels.hip), used by hdsm_track_states_batch and by the device-resident
-// loop (swarm_kernels.hip).
+// loop (the model form: swarm_kernels.hip; the external form: dswarm_models.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
