@@ -243,7 +243,7 @@ const char* hdsm_dswarm_last_error(void);
  * with timing on, hdsm_dswarm_round records HIP events on its stream between its launches; hdsm_dswarm_last_phase_ms waits for the
  * last timed round and returns milliseconds of [0] k_corridor (GenerateSafeCorridor, AC:1236-1447), [1] k_vel_cap (ComputePathVelocity's
  * voxel term, AC:1709-1766), [2] hdsm_reference_device (AC:1449-1553), [3] k_keep_free (AC:1665-1693), [4] hdsm_replan_device
- * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238; with a tracking model k_track, with scripted agents k_script behind it, both below), [6] the exchange
+ * (AC:1086-1215 + 858-1023), [5] k_commit (AC:955-1019, 569-585, 233-238; with a tracking model k_track, with scripted agents k_script, with commands k_command behind it, all below), [6] the exchange
  * (AC:610-677; one rank: nothing).
  * Every record is a barrier packet in front of the next launch: a timed round is a few microseconds longer than a plain one. */
 int hdsm_dswarm_set_phase_timing(void* dswarm, int32_t on);
@@ -577,6 +577,85 @@ int hdsm_dswarm_set_states_device(void* dswarm, const double* d_states, const ui
 int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out);
 int hdsm_dswarm_track_stats(void* dswarm, int64_t out[3]);
 int hdsm_dswarm_plans_device(void* dswarm, void** d_plans, void** d_has);
+
+/* ---- commands for the vehicle: yaw, attitude, full-state setpoints (no new ABI minor; discover by symbol) ------------------------------
+ * The last step of Agent::TrajPlanningIteration: ComputeYawAngle after the solve (AC:177, 1025-1050), the yaw in the trajectory
+ * message (Trajectory.msg field 11, AC:653), the attitude broadcast (ComputeAttitude, AC:1052-1069, through AC:797), and what the
+ * reference's only consumer of a plan, planner_crazyswarm_bridge, makes of states[1]: a full-state command. Opt-in; one source
+ * (csrc/command_core.h) for the host form, the host mirror and k_command, which agree bit for bit: atan2 and sincos are built there
+ * from + - * / alone (host libm and the device's math library differ in the last bit; their error against the true functions is in
+ * DESIGN §8, sincos pinned for |x| <= 1e4, NaN for |x| >= 2^20).
+ *   yaw step  v = traj_ref[yaw_idx][0:3] - state_curr[0:3] with state_curr of BEFORE the commit and this round's reference. Only if
+ *             n_ref > yaw_idx, v is finite and (vx vx + vy vy) + vz vz > 0.1: yaw_ref = atan2(vy, vx); err = yaw_ref - yaw, wrapped once
+ *             (err > pi: err - 2 pi; err < -pi: err + 2 pi, pi = M_PI); yaw = yaw + (k_p_yaw err) dt — dt, not step_plan dt, as the
+ *             reference. Otherwise the yaw stays.
+ *   attitude  t = a - g, g = (0, 0, -9.81) (the mass cancels); z_b = t / sqrt(t.t) if t.t > 0, else t; x_i = (cos yaw, sin yaw, 0);
+ *             y_b = z_b x x_i; x_b = y_b x z_b, neither normalised (as the reference); the matrix of the columns x_b, y_b, z_b goes
+ *             through Eigen's matrix-to-quaternion rule: T = m00 + m11 + m22 > 0: s = sqrt(T + 1), w = s / 2, s = 0.5 / s, x = (m21 -
+ *             m12) s, y = (m02 - m20) s, z = (m10 - m01) s; else i the largest diagonal entry (i = 0; m11 > m00: 1; m22 > m_ii: 2),
+ *             j = (i + 1) % 3, k = (j + 1) % 3, s = sqrt(m_ii - m_jj - m_kk + 1), q_i = s / 2, s = 0.5 / s, w = (m_kj - m_jk) s,
+ *             q_j = (m_ji + m_ij) s, q_k = (m_ki + m_ik) s. quat = (x, y, z, w), the order of geometry_msgs.
+ *   records   per round and flown agent, hdsm_command each:
+ *             setpoint [n_local][step_plan]: entry j is knot j + 1 of the record the agent published this round — the interval about
+ *               to be flown; entry 0 is the bridge's states[1]. Its quaternion is that knot's acceleration and the yaw AFTER this
+ *               round's step.
+ *             pose [n_local]: the state the round ends in — state_curr after the commit, after the tracking model when one is on
+ *               — with the attitude of that state. (The reference's transform carries traj_curr_[0] as translation, AC:779, one
+ *               round behind its own rotation; here both are state_curr.)
+ *             valid: 1 solved this round; 2 the shifted fallback of a failed solve; 0 no plan yet — pos = state_curr, vel = acc = 0 in
+ *               the setpoints and the pose, like the bridge's position command before the first trajectory — or a state, yaw or
+ *               quaternion that is not finite: every other field is then zero. The scripted tail's slots are zeros.
+ *   hdsm_command_host         n agents on plain arrays: yaw [n] in and out; n_ref [n] and ref_point [n][3] = traj_ref[yaw_idx][0:3];
+ *                             state_before [n][9]; records [n][n_hor + 1][9]; valid_in [n] (0, 1, 2); state_after [n][9] -> setpoint
+ *                             [n][step_plan], pose [n] (either may be NULL), stats[2] (may be NULL) += steps taken, steps skipped.
+ *                             Pure. hdsm_command_batch: the same through k_command on `device` (host pointers), bit for bit.
+ *                             HDSM_ERR_BAD_ARG before anything is touched: a NULL where a pointer is needed, n < 0, n_hor outside
+ *                             1..HDSM_MAX_HOR, step_plan outside 1..n_hor, yaw_idx outside 0..n_hor, dt not positive and finite, k_p_yaw
+ *                             or a yaw not finite, a valid_in outside 0..2.
+ *   hdsm_swarm_set_commands   the host mirror: hdsm_swarm_commit applies the round (behind the tracking model) to a yaw state of its
+ *                             own — hdsm_swarm_yaw and its state stay what they are. on = 0: off, the yaw kept. yaw0 [n_local] or NULL:
+ *                             zeros; given with on = 0 it is ignored. HDSM_ERR_BAD_ARG: yaw_idx outside 0..n_hor, k_p_yaw or a yaw0
+ *                             not finite. hdsm_swarm_commands: the last commit's setpoint [n_local][step_plan], pose [n_local], yaw
+ *                             [n_local] (any may be NULL); an error before the first hdsm_swarm_set_commands.
+ *   hdsm_dswarm_set_commands  the device loop: k_command, one lane per local agent, behind k_commit, k_track and k_script, inside entry
+ *                             [5] of the phase timing — ONE launch: it reads state_curr of before the commit from the solver's x_0 input
+ *                             and this round's reference from the reference buffer, both still standing behind k_commit, and the
+ *                             committed agent for the rest. Synchronises, like hdsm_dswarm_set_tracking. Device memory (the yaw, the
+ *                             two record arrays, two counters) is allocated by the first call with on != 0; a flight that never
+ *                             calls it allocates and launches nothing new, and commands never steer: plans and history are the same
+ *                             with them on. Local ranks: every rank writes its own shard's commands.
+ *   hdsm_dswarm_commands      synchronises and copies setpoint [n_local][step_plan], pose [n_local] (either may be NULL).
+ *   hdsm_dswarm_commands_device  the device addresses of the two arrays, valid until hdsm_dswarm_destroy, written on the rounds'
+ *                             stream: a simulator on the same GPU reads them there (or after synchronising with it) and answers with
+ *                             hdsm_dswarm_set_states_device — planner -> command -> vehicle model -> measured state without the host.
+ *                             An error before the first hdsm_dswarm_set_commands.
+ *   hdsm_dswarm_command_stats out[0] launches of k_command, out[1] agent-rounds with a yaw step taken, out[2] agent-rounds skipped (the
+ *                             0.1 rule, a missing reference), since hdsm_dswarm_create. Synchronises once commands were on.
+ * hdsm_dswarm_create takes the mirror's command setting and yaw over, hdsm_dswarm_download(swarm) hands them back. */
+typedef struct hdsm_command {
+  double  pos[3], vel[3], acc[3];
+  double  quat[4];                     /* x, y, z, w */
+  double  yaw;
+  int32_t valid, pad;
+  double  reserved0;                   /* 0; the record is 128 bytes */
+} hdsm_command;
+
+int hdsm_command_host(int32_t n, int32_t n_hor, int32_t step_plan, double dt, int32_t yaw_idx, double k_p_yaw, const int32_t* n_ref,
+                      const double* ref_point, const double* state_before, const double* records, const int32_t* valid_in,
+                      const double* state_after, double* yaw, hdsm_command* setpoint, hdsm_command* pose, int64_t stats[2]);
+int hdsm_command_batch(int32_t device, int32_t n, int32_t n_hor, int32_t step_plan, double dt, int32_t yaw_idx, double k_p_yaw,
+                       const int32_t* n_ref, const double* ref_point, const double* state_before, const double* records,
+                       const int32_t* valid_in, const double* state_after, double* yaw, hdsm_command* setpoint, hdsm_command* pose,
+                       int64_t stats[2]);
+int hdsm_swarm_set_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw0);
+int hdsm_swarm_commands(void* swarm, hdsm_command* setpoint, hdsm_command* pose, double* yaw);
+int hdsm_dswarm_set_commands(void* dswarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw0);
+int hdsm_dswarm_commands(void* dswarm, hdsm_command* setpoint, hdsm_command* pose);
+int hdsm_dswarm_commands_device(void* dswarm, void** d_setpoint, void** d_pose);
+int hdsm_dswarm_command_stats(void* dswarm, int64_t out[3]);
+/* the own atan2 and sincos of csrc/command_core.h on n values each (s, c: sin and cos), for whoever wants to measure them */
+int hdsm_command_atan2(int32_t n, const double* y, const double* x, double* out);
+int hdsm_command_sincos(int32_t n, const double* x, double* s, double* c);
 
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between

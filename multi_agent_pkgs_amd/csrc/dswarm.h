@@ -138,6 +138,20 @@ struct Track {
   DevBuf<uint8_t> d_stage_mask;
 };
 
+// commands for the vehicle (hdsm_dswarm_set_commands; nothing is allocated or launched before the first call that switches them on):
+// the setting, the yaw per agent ([n_local], a buffer of its own: AgentS is shared with the mirror and stays as it is), the records
+// k_command writes ([n_local][step_plan] and [n_local]), the counters [steps taken, skipped] and the launches
+struct Commands {
+  bool on = false;
+  int yaw_idx = 0;
+  double k_p_yaw = 0;
+  long long launches = 0;
+  DevBuf<double> d_yaw;
+  DevBuf<hdsm_command> d_setpoint, d_pose;
+  DevBuf<unsigned long long> d_cnt;
+  bool ready() const { return (bool)d_cnt; }
+};
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -163,6 +177,7 @@ struct DSwarm {
   Links links;
   Script script;
   Track track;
+  Commands cmd;
   int n_fly() const { return n_local - script.n; }  // the agents this shard plans for: all but its scripted tail
   int slots() const { return per * world; }         // the records of the plans buffer (and of everything shaped like it)
   int rec() const { return (c.N + 1) * 9; }         // the doubles of a record
@@ -192,6 +207,9 @@ int upload_goals_and_due(DSwarm* d);
 // (dswarm_flight.cpp) the mirror's flight becomes the device's, and the way back
 int take_over(DSwarm& d, void* swarm, const int8_t* hworld);
 int hand_back(DSwarm& d, void* swarm);
+// (dswarm_models.cpp) the command buffers, allocated by the first call that needs them (the caller has set the device); the setting
+// and the yaw [n_local] (NULL: zeros) onto the device (the device is idle)
+int commands_setup(DSwarm* d, bool on, int yaw_idx, double k_p_yaw, const double* yaw0);
 // (swarm_kernels.hip) every event a timed round records
 int timing_events(DSwarm* d);
 // (dswarm_audit.hip) the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports

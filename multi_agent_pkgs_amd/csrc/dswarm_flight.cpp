@@ -91,6 +91,14 @@ int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
     d.audit.on = on != 0;
     if (int rc = audit_setup(&d, rep.data())) return rc;
   }
+  int32_t cmd_ever = 0, cmd_on = 0, yaw_idx = 0;  // the command setting and yaw of the mirror (a flight taken over keeps its yaw)
+  double k_p_yaw = 0;
+  if (int rc = hdsm_swarm_export_commands(swarm, &cmd_ever, &cmd_on, &yaw_idx, &k_p_yaw, nullptr)) return refused(rc);
+  if (cmd_on) {
+    std::vector<double> yaw(n + 1, 0.0);
+    if (int rc = hdsm_swarm_export_commands(swarm, &cmd_ever, &cmd_on, &yaw_idx, &k_p_yaw, yaw.data())) return refused(rc);
+    if (int rc = commands_setup(&d, true, yaw_idx, k_p_yaw, yaw.data())) return rc;
+  }
   return HDSM_OK;
 }
 
@@ -108,6 +116,11 @@ int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
     std::vector<hdsm_flight_report> rep(n);
     if (hipMemcpy(rep.data(), d.audit.d_report.get(), n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
     else rc = hdsm_swarm_import_audit(swarm, d.audit.on ? 1 : 0, d.audit.sep_warn, rep.data());
+  }
+  if (rc == HDSM_OK && d.cmd.ready()) {
+    std::vector<double> yaw(n);
+    if (hipMemcpy(yaw.data(), d.cmd.d_yaw.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
+    else rc = hdsm_swarm_import_commands(swarm, d.cmd.on ? 1 : 0, d.cmd.yaw_idx, d.cmd.k_p_yaw, yaw.data());
   }
   return rc ? fail(rc, "state download failed") : HDSM_OK;
 }

@@ -1,12 +1,13 @@
 // dswarm_models.cpp — what a caller puts between the plans and the flight of the device-resident loop, set between rounds: link faults
-// (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip) and imperfect tracking (k_track, track_kernels.hip),
-// each with its counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
+// (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip), imperfect tracking (k_track, track_kernels.hip) and
+// the commands for the vehicle (k_command, command_kernels.hip), each with its counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
 // (hdsm_dswarm_set_states*), through track_device.h.
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
+#include "command_core.h"
 #include "dswarm.h"
 #include "link_core.h"
 #include "script_device.h"
@@ -41,6 +42,27 @@ int track_external(DSwarm* d, const double* d_states, const uint8_t* d_mask, hip
 }
 
 }  // namespace
+
+int hdsm_dswarm::commands_setup(DSwarm* d, bool on, int yaw_idx, double k_p_yaw, const double* yaw0) {
+  Commands& m = d->cmd;
+  const size_t n = (size_t)d->n_local;
+  if (on && !m.ready()) {
+    hdsm_mem::FirstError ok;
+    ok(m.d_yaw.alloc_zeroed(n)), ok(m.d_setpoint.alloc_zeroed(n * (size_t)d->c.step_plan)), ok(m.d_pose.alloc_zeroed(n)), ok(m.d_cnt.alloc_zeroed(2));
+    if (!ok.ok()) {
+      m.d_cnt.reset();
+      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_commands: ") + hipGetErrorString(ok.e));
+    }
+  }
+  if (on) {
+    if (yaw0 && n) HIP_TRY(hipMemcpy(m.d_yaw.get(), yaw0, n * sizeof(double), hipMemcpyHostToDevice));
+    else HIP_TRY(hipMemset(m.d_yaw.get(), 0, (n ? n : 1) * sizeof(double)));
+    HIP_TRY(hipDeviceSynchronize());  // (the fills are done before a kernel of any stream writes into the buffers)
+    m.yaw_idx = yaw_idx, m.k_p_yaw = k_p_yaw;
+  }
+  m.on = on;
+  return HDSM_OK;
+}
 
 extern "C" {
 
@@ -201,6 +223,48 @@ int hdsm_dswarm_track_records(void* dswarm, hdsm_track_record* out) {
   }
   if (int rc = device_idle(d)) return rc;
   HIP_TRY(hipMemcpy(out, d->track.d_rec.get(), (size_t)d->n_local * sizeof(hdsm_track_record), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+// Commands for the vehicle (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_commands(void* dswarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw0) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (on && !hdsm_cmd::settings_valid(yaw_idx, d->c.N, k_p_yaw, yaw0, d->n_local))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_commands: yaw_idx in 0 .. n_hor, k_p_yaw and every yaw0 finite");
+  if (!on && !d->cmd.on) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  return commands_setup(d, on != 0, yaw_idx, k_p_yaw, yaw0);
+}
+
+int hdsm_dswarm_commands(void* dswarm, hdsm_command* setpoint, hdsm_command* pose) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (!d->cmd.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_commands: no hdsm_dswarm_set_commands yet");
+  if (int rc = device_idle(d)) return rc;
+  const size_t n = (size_t)d->n_local;
+  if (setpoint && n) HIP_TRY(hipMemcpy(setpoint, d->cmd.d_setpoint.get(), n * (size_t)d->c.step_plan * sizeof(hdsm_command), hipMemcpyDeviceToHost));
+  if (pose && n) HIP_TRY(hipMemcpy(pose, d->cmd.d_pose.get(), n * sizeof(hdsm_command), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_commands_device(void* dswarm, void** d_setpoint, void** d_pose) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !d_setpoint || !d_pose) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->cmd.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_commands_device: no hdsm_dswarm_set_commands yet");
+  *d_setpoint = d->cmd.d_setpoint.get(), *d_pose = d->cmd.d_pose.get();
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_command_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->cmd.launches, out[1] = out[2] = 0;
+  if (!d->cmd.ready()) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  unsigned long long cnt[2] = {0, 0};
+  HIP_TRY(hipMemcpy(cnt, d->cmd.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
+  out[1] = (int64_t)cnt[0], out[2] = (int64_t)cnt[1];
   return HDSM_OK;
 }
 

@@ -63,6 +63,13 @@ int hdsm_internal_script_args(int32_t n_script, int32_t n_knots, const double* k
 // (track_host.cpp) the argument checks shared by hdsm_track_states_host / _batch
 int hdsm_internal_track_args(const hdsm_tracking* m, int32_t n, const int32_t* agent_id, const double* planned, double T, int64_t round,
                              const double* flown);
+// (command_host.cpp) the argument checks shared by hdsm_command_host / _batch
+int hdsm_internal_command_args(int32_t n, int32_t n_hor, int32_t step_plan, double dt, int32_t yaw_idx, double k_p_yaw, const int32_t* n_ref,
+                               const double* ref_point, const double* state_before, const double* records, const int32_t* valid_in,
+                               const double* state_after, const double* yaw);
+// (swarm_host.cpp) the command setting and yaw of the mirror (yaw [n_local], may be NULL on export; ever: set_commands was called)
+int hdsm_swarm_export_commands(void* swarm, int32_t* ever, int32_t* on, int32_t* yaw_idx, double* k_p_yaw, double* yaw);
+int hdsm_swarm_import_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

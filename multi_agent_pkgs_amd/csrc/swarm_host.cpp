@@ -19,6 +19,7 @@
 #include "../../include/hdsm_stats.h"
 #include "../../include/hdsm_swarm.h"
 #include "audit_core.h"
+#include "command_core.h"
 #include "hdsm_internal.h"
 #include "link_core.h"
 #include "path_core.h"
@@ -98,6 +99,14 @@ struct Swarm {
   void track_ready() {
     if (track_rec.size() != (size_t)n_local) track_rec.assign((size_t)n_local, hdsm_track_record{});
   }
+  // commands for the vehicle (command_core.h; hdsm_swarm_set_commands): the setting, a yaw state of its own (AgentX::yaw stays
+  // hdsm_swarm_yaw's), the last commit's records and the counters [steps taken, skipped]
+  bool cmd_on = false, cmd_ever = false;
+  int cmd_yaw_idx = 0;
+  double cmd_k_p_yaw = 0;
+  std::vector<double> cmd_yaw;
+  std::vector<hdsm_command> cmd_setpoint, cmd_pose;
+  int64_t cmd_stats[2] = {0, 0};
   void neighbour_range(int id, int* lo, int* hi) const {
     *lo = range.empty() ? 0 : range[2 * (size_t)id], *hi = range.empty() ? n_rob : range[2 * (size_t)id + 1];
   }
@@ -501,6 +510,9 @@ int hdsm_swarm_commit(void* swarm, const double* traj_out, const double* ctrl_ou
     return HDSM_ERR_BAD_ARG;
   const int N = sw->prm.n_hor, P = sw->prm.poly_hor;
   const hdsm_sw::Cfg cc = sw->core_cfg();
+  std::vector<double> cmd_before;  // state_curr of before the commit: what the yaw step looks from (AC:177 comes before AC:233)
+  if (sw->cmd_on)
+    for (int k = 0; k < sw->n_local; ++k) cmd_before.insert(cmd_before.end(), sw->agents[k].state_curr, sw->agents[k].state_curr + 9);
   for (int k = 0; k < sw->n_local; ++k) {
     AgentS& ag = sw->agents[k];
     const int have_plan = hdsm_sw::commit_one(cc, ag, traj_out + (size_t)k * (N + 1) * 9, ctrl_out + (size_t)k * N * 3,
@@ -522,6 +534,19 @@ int hdsm_swarm_commit(void* swarm, const double* traj_out, const double* ctrl_ou
       hdsm_track::book(sw->track_rec[(size_t)k], hdsm_track::pos_dist(from, to), hdsm_track::vel_dist(from, to), false);
     }
     ++sw->track_q;
+  }
+  if (sw->cmd_on) {  // the yaw step, the setpoints of the interval about to be flown and the pose the round ends in (command_core.h)
+    const int step = sw->cfg.step_plan;
+    for (int k = 0; k < sw->n_local; ++k) {
+      const AgentS& ag = sw->agents[k];
+      const int valid = !ag.has_traj ? 0 : (status[k] != HDSM_NO_SOLUTION ? 1 : 2);
+      const bool has_ref = ag.n_ref > sw->cmd_yaw_idx;
+      double& yaw = sw->cmd_yaw[(size_t)k];
+      int stepped = 0;
+      yaw = hdsm_cmd::agent_round(yaw, has_ref, ag.traj_ref[has_ref ? sw->cmd_yaw_idx : 0], &cmd_before[(size_t)k * 9], &ag.traj_curr[0][0], ag.state_curr,
+                                  valid, step, sw->cmd_k_p_yaw, sw->prm.dt, &sw->cmd_setpoint[(size_t)k * step], &sw->cmd_pose[(size_t)k], &stepped);
+      sw->cmd_stats[stepped ? 0 : 1] += 1;
+    }
   }
   // f3: the records Agent::TrajPlanningIteration keeps (AC:193-245). The separating planes are generated inside the fused
   // launch: its duration (hdsm_swarm_record_solve_ms) is booked as comp_time_opt_, comp_time_tasc_ is 0.
@@ -568,6 +593,53 @@ int hdsm_swarm_track_records(void* swarm, hdsm_track_record* out) {
   Swarm* sw = static_cast<Swarm*>(swarm);
   if (!sw || (!out && sw->n_local)) return HDSM_ERR_BAD_ARG;
   for (int k = 0; k < sw->n_local; ++k) out[k] = (size_t)k < sw->track_rec.size() ? sw->track_rec[(size_t)k] : hdsm_track_record{};
+  return HDSM_OK;
+}
+
+// Commands for the vehicle on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_swarm_set_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw0) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  if (on && !hdsm_cmd::settings_valid(yaw_idx, sw->prm.n_hor, k_p_yaw, yaw0, sw->n_local)) return HDSM_ERR_BAD_ARG;
+  const size_t n = (size_t)sw->n_local;
+  if (!sw->cmd_ever) {
+    sw->cmd_yaw.assign(n, 0.0);
+    sw->cmd_setpoint.assign(n * (size_t)sw->cfg.step_plan, hdsm_command{}), sw->cmd_pose.assign(n, hdsm_command{});
+    sw->cmd_ever = true;
+  }
+  sw->cmd_on = on != 0;
+  if (on) {
+    sw->cmd_yaw_idx = yaw_idx, sw->cmd_k_p_yaw = k_p_yaw;
+    for (size_t k = 0; k < n; ++k) sw->cmd_yaw[k] = yaw0 ? yaw0[k] : 0.0;
+  }
+  return HDSM_OK;
+}
+
+int hdsm_swarm_commands(void* swarm, hdsm_command* setpoint, hdsm_command* pose, double* yaw) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !sw->cmd_ever) return HDSM_ERR_BAD_ARG;
+  if (setpoint) std::copy(sw->cmd_setpoint.begin(), sw->cmd_setpoint.end(), setpoint);
+  if (pose) std::copy(sw->cmd_pose.begin(), sw->cmd_pose.end(), pose);
+  if (yaw) std::copy(sw->cmd_yaw.begin(), sw->cmd_yaw.end(), yaw);
+  return HDSM_OK;
+}
+
+// (hdsm_internal.h) the flight in and out of the device-resident loop
+int hdsm_swarm_export_commands(void* swarm, int32_t* ever, int32_t* on, int32_t* yaw_idx, double* k_p_yaw, double* yaw) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !ever || !on || !yaw_idx || !k_p_yaw) return HDSM_ERR_BAD_ARG;
+  *ever = sw->cmd_ever, *on = sw->cmd_on, *yaw_idx = sw->cmd_yaw_idx, *k_p_yaw = sw->cmd_k_p_yaw;
+  if (yaw && sw->cmd_ever) std::copy(sw->cmd_yaw.begin(), sw->cmd_yaw.end(), yaw);
+  return HDSM_OK;
+}
+
+int hdsm_swarm_import_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw) {
+  Swarm* sw = static_cast<Swarm*>(swarm);
+  if (!sw || !yaw) return HDSM_ERR_BAD_ARG;
+  // (the setting as the device loop was left with it; switched on there and off again, k_p_yaw and yaw_idx are the last ones given)
+  if (int rc = hdsm_swarm_set_commands(swarm, 0, 0, 0.0, nullptr)) return rc;
+  sw->cmd_on = on != 0, sw->cmd_yaw_idx = yaw_idx, sw->cmd_k_p_yaw = k_p_yaw;
+  std::copy(yaw, yaw + sw->n_local, sw->cmd_yaw.begin());
   return HDSM_OK;
 }
 

@@ -11,6 +11,8 @@
 //                of the difference (track_kernels.hip); also launched between rounds by hdsm_dswarm_set_states*   one lane per flown agent
 //   k_script     (only with scripted agents, hdsm_dswarm_set_script) the records of the shard's scripted tail, over the slots
 //                k_commit has just padded (script_kernels.hip)                                   one wavefront per scripted agent
+//   k_command    (only with commands on, hdsm_dswarm_set_commands) the yaw step, the setpoints of the interval about to be flown and the
+//                pose the round ends in (command_kernels.hip)                                    one lane per agent
 //   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
 //                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
@@ -28,6 +30,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "command_device.h"
 #include "dswarm.h"
 #include "hdsm_internal.h"
 #include "link_core.h"
@@ -698,6 +701,15 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
                                                    direct ? d.d_has.get() + n_fly : nullptr, d.d_status.get() + n_fly, d.d_agents.get() + n_fly},
                                 st));
     ++s.round, ++s.launches;
+  }
+  if (Commands& m = d.cmd; m.on && d.n_local > 0) {  // what the vehicles are told (inside phase [5]). ONE launch behind the commit: state_curr
+    // of before it still stands in the solver's x_0 input, this round's reference in the reference buffer
+    hdsm_cmd::Launch a{};
+    a.n = d.n_local, a.n_fly = n_fly, a.N = d.c.N, a.step_plan = d.c.step_plan, a.yaw_idx = m.yaw_idx, a.dt = d.prm.dt, a.k_p_yaw = m.k_p_yaw;
+    a.agents = d.d_agents.get(), a.status = d.d_status.get(), a.before = d.d_state.get(), a.ref_full = d.d_ref_full.get();
+    a.yaw = m.d_yaw.get(), a.setpoint = m.d_setpoint.get(), a.pose = m.d_pose.get(), a.cnt = m.d_cnt.get();
+    HIP_TRY(hdsm_cmd::launch(a, st));
+    ++m.launches;
   }
   if (local) {
     if (int rc = hdsm_internal_local_published(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());

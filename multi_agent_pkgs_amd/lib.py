@@ -16,7 +16,7 @@ import re
 
 import numpy as np
 
-from .params import HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord
+from .params import Command, HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("HDSM_LIBRARY") or os.path.join(_HERE, "libhdsm.so")  # (HDSM_LIBRARY: a development build, e.g. -DCD_PROFILE)
@@ -40,6 +40,9 @@ GROUP_REPORT = np.dtype([("first", "<i4"), ("count", "<i4"), ("n_local", "<i4"),
                          ("speed_max", "<f8")])                                                            # hdsm_group_report
 TRACK_RECORD = np.dtype([("rounds", "<i8"), ("external", "<i8"), ("dist_sum", "<f8"), ("dist_sq_sum", "<f8"), ("dist_max", "<f8"),
                          ("dvel_max", "<f8")])                                                             # hdsm_track_record
+COMMAND = np.dtype([("pos", "<f8", 3), ("vel", "<f8", 3), ("acc", "<f8", 3), ("quat", "<f8", 4), ("yaw", "<f8"), ("valid", "<i4"), ("pad", "<i4"),
+                    ("reserved0", "<f8")])                                                                 # hdsm_command
+assert COMMAND.itemsize == 128 == C.sizeof(Command)
 assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104 and GROUP_REPORT.itemsize == 128
 assert TRACK_RECORD.itemsize == 48 == C.sizeof(TrackRecord) and C.sizeof(Tracking) == 80
 
@@ -76,7 +79,7 @@ CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": 
 CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32_t", np.int32), ("int8_t", np.int8), ("uint8_t", np.uint8),
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
                                                   ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
-                                                  ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD))})
+                                                  ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD), ("hdsm_command", COMMAND))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
                                                   ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking))})
 
@@ -119,6 +122,7 @@ EXPORTS = tuple(SIGNATURES)
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
               ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_track_", None),
+              ("hdsm_command_", None),
               ("hdsm_", "hdsm_last_error"))
 
 _lib = None
@@ -536,6 +540,43 @@ def track_states(model, ids, planned, T, round=0, device=None):
     lead, fn = ((), "hdsm_track_states_host") if device is None else ((int(device),), "hdsm_track_states_batch")
     call(fn, *lead, model, ids.size, ids, planned, float(T), int(round), flown, dist)
     return flown, dist
+
+
+def command(yaw, n_ref, ref_point, state_before, records, valid, state_after, step_plan=1, dt=0.1, yaw_idx=3, k_p_yaw=1.0, device=None):
+    """hdsm_command_host: one round of commands for n agents on plain arrays (csrc/command_core.h) — yaw [n] the yaw before the round,
+    n_ref [n] and ref_point [n][3] = traj_ref[yaw_idx][0:3], state_before [n][9] = state_curr before the commit, records [n][n_hor+1][9],
+    valid [n] (1 solved, 2 shifted fallback, 0 no plan), state_after [n][9] the state the round ends in. Returns (yaw after the step
+    [n], setpoint [n][step_plan] and pose [n] of lib.COMMAND, (steps taken, steps skipped)). device given: hdsm_command_batch, the same
+    through k_command on that device, bit for bit."""
+    yaw = np.array(yaw, dtype=np.float64, order="C", copy=True).reshape(-1)
+    n = yaw.size
+    records = _f64(records)
+    if records.ndim != 3 or records.shape[0] != n or records.shape[2] != 9:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "command: records [n][n_hor+1][9] for yaw [n] expected")
+    n_ref, valid = _i32(n_ref).reshape(n), _i32(valid).reshape(n)
+    ref_point, state_before, state_after = _f64(ref_point).reshape(n, 3), _f64(state_before).reshape(n, 9), _f64(state_after).reshape(n, 9)
+    setpoint, pose, stats = np.zeros((n, int(step_plan)), COMMAND), np.zeros(n, COMMAND), np.zeros(2, np.int64)
+    lead, fn = ((), "hdsm_command_host") if device is None else ((int(device),), "hdsm_command_batch")
+    call(fn, *lead, n, records.shape[1] - 1, int(step_plan), float(dt), int(yaw_idx), float(k_p_yaw), n_ref, ref_point, state_before, records,
+         valid, state_after, yaw, setpoint, pose, stats)
+    return yaw, setpoint, pose, (int(stats[0]), int(stats[1]))
+
+
+def command_atan2(y, x):
+    """hdsm_command_atan2: the own atan2 of csrc/command_core.h, elementwise."""
+    y, x = np.broadcast_arrays(_f64(y), _f64(x))
+    y, x = _f64(y).reshape(-1), _f64(x).reshape(-1)
+    out = np.zeros(y.size)
+    call("hdsm_command_atan2", y.size, y, x, out)
+    return out
+
+
+def command_sincos(x):
+    """hdsm_command_sincos: the own (sin, cos) of csrc/command_core.h, elementwise (NaN for |x| >= 2^20)."""
+    x = _f64(x).reshape(-1)
+    s, c = np.zeros(x.size), np.zeros(x.size)
+    call("hdsm_command_sincos", x.size, x, s, c)
+    return s, c
 
 
 def _flight_audit(fn, lead, plans_all, has_plan, step_plan, first, n_local, drone_radius, drone_z_offset, world, worigin, voxel_size):

@@ -142,6 +142,19 @@ class Tracking(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("wind", C.c_double * 3), ("gust", C.c_double * 3), ("jitter", C.c_double * 3)]
 
 
+# Agent::ComputeYawAngle's two parameters as the reference ships them (multi_agent_planner/config/*.yaml): yaw_idx 3 in
+# agent_agile_config.yaml — the declared default (agent_class.cpp:2237) the two other files leave alone — and k_p_yaw 1.0 in all three.
+YAW_IDX, K_P_YAW = 3, 1.0
+
+
+class Command(C.Structure):
+    """hdsm_command (include/hdsm_swarm.h): one full-state command — position, velocity, acceleration, the attitude quaternion
+    (x, y, z, w), the yaw it was formed with, and valid (1 solved this round, 2 the shifted fallback, 0 no plan yet or not finite).
+    lib.COMMAND is the numpy dtype of the same layout."""
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("acc", C.c_double * 3), ("quat", C.c_double * 4), ("yaw", C.c_double),
+                ("valid", C.c_int32), ("pad", C.c_int32), ("reserved0", C.c_double)]
+
+
 class TrackRecord(C.Structure):
     """hdsm_track_record: per agent the model rounds and the states taken from outside that were counted, over those samples the sum,
     the sum of squares and the maximum of the distance between the planned and the flown position, and the largest velocity

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import _f64, _i8, _i32, _stream, _u8, call
-from .params import HdsmParams, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
+from .params import K_P_YAW, YAW_IDX, HdsmParams, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
 from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario, repeat_scenario  # noqa: F401  (scenario geometry lives in scenarios.py)
 
 
@@ -210,6 +210,20 @@ class SwarmShard:
         rec = np.zeros(self.n_local, _lib.TRACK_RECORD)
         call("hdsm_swarm_track_records", self.h, rec)
         return rec
+
+    # ---- commands for the vehicle (include/hdsm_swarm.h) ----
+    def set_commands(self, on=True, yaw_idx=YAW_IDX, k_p_yaw=K_P_YAW, yaw0=None):
+        """hdsm_swarm_set_commands: from the next commit on every agent's yaw follows reference point yaw_idx (ComputeYawAngle) and the
+        commit leaves the setpoints of the interval about to be flown and the pose the round ends in (commands()). yaw0 [n_local]: the
+        yaw to start from (None: zeros). on=False: off, the yaw kept. A DeviceSwarm made from this shard takes setting and yaw over."""
+        call("hdsm_swarm_set_commands", self.h, 1 if on else 0, int(yaw_idx), float(k_p_yaw), None if yaw0 is None else _f64(yaw0).reshape(self.n_local))
+
+    def commands(self):
+        """hdsm_swarm_commands: (setpoint [n_local][step_plan], pose [n_local] of lib.COMMAND, yaw [n_local]) of the last commit."""
+        sp, pose = np.zeros((self.n_local, self.cfg.step_plan), _lib.COMMAND), np.zeros(self.n_local, _lib.COMMAND)
+        yaw = np.zeros(self.n_local)
+        call("hdsm_swarm_commands", self.h, sp, pose, yaw)
+        return sp, pose, yaw
 
     def state(self):
         pos = np.zeros((self.n_local, 3))
@@ -507,6 +521,35 @@ class DeviceSwarm:
         plans, has = C.c_void_p(), C.c_void_p()
         call("hdsm_dswarm_plans_device", self.h, C.byref(plans), C.byref(has))
         return plans.value, has.value
+
+    # ---- commands for the vehicle (include/hdsm_swarm.h) ----
+    def set_commands(self, on=True, yaw_idx=YAW_IDX, k_p_yaw=K_P_YAW, yaw0=None):
+        """hdsm_dswarm_set_commands: from the next round on k_command, the last launch behind k_commit, steps every flown agent's yaw
+        towards reference point yaw_idx and writes the setpoints of the interval about to be flown and the pose the round ends in.
+        yaw0 [n_local]: the yaw to start from (None: zeros). on=False: off, yaw and records kept. Commands never steer: the plans
+        are what they are without them. Synchronises."""
+        n = self.shard.n_local
+        call("hdsm_dswarm_set_commands", self.h, 1 if on else 0, int(yaw_idx), float(k_p_yaw), None if yaw0 is None else _f64(yaw0).reshape(n))
+
+    def commands(self):
+        """hdsm_dswarm_commands: (setpoint [n_local][step_plan], pose [n_local]) of lib.COMMAND as the last round left them; setpoint[k][0]
+        is what planner_crazyswarm_bridge sends as FullState, its yaw field 11 of Trajectory.msg. Synchronises."""
+        n = self.shard.n_local
+        sp, pose = np.zeros((n, self.shard.cfg.step_plan), _lib.COMMAND), np.zeros(n, _lib.COMMAND)
+        call("hdsm_dswarm_commands", self.h, sp, pose)
+        return sp, pose
+
+    def commands_device(self):
+        """hdsm_dswarm_commands_device: the device addresses of (setpoint [n_local][step_plan], pose [n_local]), 128-byte hdsm_command
+        records, valid for the dswarm's life and written on the rounds' stream — what a vehicle model on the same GPU reads."""
+        sp, pose = C.c_void_p(), C.c_void_p()
+        call("hdsm_dswarm_commands_device", self.h, C.byref(sp), C.byref(pose))
+        return sp.value, pose.value
+
+    def command_stats(self):
+        """hdsm_dswarm_command_stats: launches of k_command, agent-rounds with a yaw step taken, agent-rounds skipped (the reference point
+        closer than sqrt(0.1) m, or missing). Synchronises once commands were on."""
+        return dict(zip(("launches", "steps", "skipped"), self._counters("hdsm_dswarm_command_stats", 3)))
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
