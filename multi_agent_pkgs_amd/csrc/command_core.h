@@ -1,6 +1,6 @@
 // command_core.h — what a vehicle is told after a round: the yaw step of Agent::ComputeYawAngle (AC:1025-1050), the attitude of
 // Agent::ComputeAttitude (AC:1052-1069) and the full-state setpoints planner_crazyswarm_bridge takes from a plan, as plain functions
-// that compile for the host forms (command_host.cpp, swarm_host.cpp) AND for the device kernel (command_kernels.hip). One source, the
+// that compile for the host forms (command_host.cpp, swarm_models.cpp) AND for the device kernel (command_kernels.hip). One source, the
 // same IEEE operations in the same order (floating-point contraction off, products first, sums left to right, sqrt and division
 // correctly rounded on both sides), so the forms agree bit for bit. No libm call sits in this path: host libm and the device's math
 // library differ in the last bit, so atan2 and sincos are built here from +, -, *, / alone. Their constants were derived with mpmath

@@ -6,11 +6,12 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dswarm.h"
 #include "hdsm_internal.h"
-#include "path_core.h"
+#include "swarm_host.h"
 
 using namespace hdsm_dswarm;
 
@@ -26,34 +27,25 @@ int hdsm_dswarm::upload_goals_and_due(DSwarm* d) {
 }
 
 // The mirror's flight becomes the device's (hdsm_dswarm_create, after alloc_round_buffers): the path step's phase and pending agents,
-// the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the audit's setting and record.
+// the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the partition, the audit's
+// setting and record, the command setting and yaw. Each is read from the mirror's member struct (swarm_host.h).
 int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
+  const hdsm_mirror::Swarm& sw = *hdsm_mirror::as_swarm(swarm);
   const size_t n = (size_t)d.n_local;
   PathStep& p = d.path;
-  const auto refused = [](int rc) { return fail(rc, "hdsm_dswarm_create: export failed"); };
-  p.due.assign(n, 0), p.goals.assign(n * 3, 0.0);
-  int32_t period = 0;
-  int64_t round = 0;
-  if (int rc = hdsm_swarm_export_path_state(swarm, &period, &round, p.due.data())) return refused(rc);
-  p.period = period, p.round = round;
-  double rad = 0;
-  if (int rc = hdsm_swarm_export_path_clearance(swarm, &rad)) return refused(rc);
-  if (rad != 0) {
-    hdsm_path::DmpMask mask{};
-    if (!hdsm_path::dmp_build_mask(rad, d.cfg.voxel_size, &mask)) return refused(HDSM_ERR_BAD_ARG);
-    p.dmp = true, p.dmp_rn = mask.rn;
-    HIP_TRY(p.d_dmp_rows.alloc_zeroed(sizeof mask.rows / sizeof mask.rows[0]));
-    HIP_TRY(hipMemcpy(p.d_dmp_rows.get(), mask.rows, sizeof mask.rows, hipMemcpyHostToDevice));
+  p.period = sw.path.period, p.round = sw.path.round, p.due = sw.path.due;
+  p.goals.assign(n * 3, 0.0);
+  if (const hdsm_path::DmpMask* mask = sw.path.dmp()) {
+    p.dmp = true, p.dmp_rn = mask->rn;
+    HIP_TRY(p.d_dmp_rows.alloc_zeroed(sizeof mask->rows / sizeof mask->rows[0]));
+    HIP_TRY(hipMemcpy(p.d_dmp_rows.get(), mask->rows, sizeof mask->rows, hipMemcpyHostToDevice));
   }
   if (n) {
-    std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
-    if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
-    if (int rc = hdsm_swarm_export_state(swarm, tmp.get(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) return refused(rc);
-    HIP_TRY(hipMemcpy(d.d_agents.get(), tmp.get(), n * sizeof(AgentS), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.d_agents.get(), sw.agents.data(), n * sizeof(AgentS), hipMemcpyHostToDevice));
     // the agent ids of the shard (a contiguous block), the goals, and the agents the mirror had marked due (hdsm_swarm_set_goals before the dswarm)
     std::vector<int32_t> ids(n, 0);
     for (size_t k = 0; k < n; ++k) {
-      for (int q = 0; q < 3; ++q) p.goals[3 * k + q] = tmp[k].goal[q];
+      for (int q = 0; q < 3; ++q) p.goals[3 * k + q] = sw.agents[k].goal[q];
       ids[k] = d.first + (int)k;
     }
     HIP_TRY(hipMemcpy(d.d_id.get(), ids.data(), n * 4, hipMemcpyHostToDevice));
@@ -62,16 +54,10 @@ int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
   if (hworld) HIP_TRY(hipMemcpy(d.d_world.get(), hworld, d.voxels(), hipMemcpyHostToDevice));
   d.c.world = d.d_world.get();
   {  // the mirror's partition goes onto the solver handle (none: the handle's is cleared) and, for the audit, into a range table
-    int32_t ng = 0;
-    if (int rc = hdsm_swarm_export_groups(swarm, &ng, nullptr)) return refused(rc);
+    const int ng = sw.groups.n();
     d.grouped = ng > 0;
-    d.group_start.assign((size_t)(d.grouped ? ng + 1 : 2), 0);
-    if (d.grouped) {
-      if (int rc = hdsm_swarm_export_groups(swarm, &ng, d.group_start.data())) return refused(rc);
-    } else {
-      d.group_start[1] = d.n_rob;
-    }
-    if (int rc = hdsm_set_groups(d.solver, d.grouped ? ng : 0, d.grouped ? d.group_start.data() : nullptr))
+    d.group_start = d.grouped ? sw.groups.start : std::vector<int32_t>{0, d.n_rob};
+    if (int rc = hdsm_set_groups(d.solver, ng, d.grouped ? d.group_start.data() : nullptr))
       return fail(rc, std::string("hdsm_set_groups: ") + hdsm_last_error());
     HIP_TRY(hipSetDevice(d.device));  // (the handle may live on another device)
     if (d.grouped) {
@@ -83,44 +69,38 @@ int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
       HIP_TRY(hipMemcpy(d.d_range.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
   }
-  int32_t on = 0, ever = 0;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
-  if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, nullptr)) return refused(rc);
-  if (ever) {
-    std::vector<hdsm_flight_report> rep(n);
-    if (int rc = hdsm_swarm_export_audit(swarm, &on, &ever, &d.audit.sep_warn, rep.data())) return refused(rc);
-    d.audit.on = on != 0;
-    if (int rc = audit_setup(&d, rep.data())) return rc;
+  d.audit.sep_warn = sw.audit.sep_warn;  // the audit's setting and record of the mirror (a flight taken over keeps its record)
+  if (sw.audit.ever) {
+    d.audit.on = sw.audit.on;
+    if (int rc = audit_setup(&d, sw.audit.flight.data())) return rc;
   }
-  int32_t cmd_ever = 0, cmd_on = 0, yaw_idx = 0;  // the command setting and yaw of the mirror (a flight taken over keeps its yaw)
-  double k_p_yaw = 0;
-  if (int rc = hdsm_swarm_export_commands(swarm, &cmd_ever, &cmd_on, &yaw_idx, &k_p_yaw, nullptr)) return refused(rc);
-  if (cmd_on) {
-    std::vector<double> yaw(n + 1, 0.0);
-    if (int rc = hdsm_swarm_export_commands(swarm, &cmd_ever, &cmd_on, &yaw_idx, &k_p_yaw, yaw.data())) return refused(rc);
-    if (int rc = commands_setup(&d, true, yaw_idx, k_p_yaw, yaw.data())) return rc;
-  }
+  if (sw.cmd.on)  // the command setting and yaw of the mirror (a flight taken over keeps its yaw)
+    if (int rc = commands_setup(&d, true, sw.cmd.yaw_idx, sw.cmd.k_p_yaw, sw.cmd.yaw.data())) return rc;
   return HDSM_OK;
 }
 
 // The device's flight back into the mirror (hdsm_dswarm_download; the device is idle): the agent states, the path step's phase,
-// pending agents and goals, the audit's setting and record.
+// pending agents and goals, the audit's setting and record, the command setting and yaw. Each piece goes through the adopt of the
+// mirror's member struct, which keeps that struct's invariants.
 int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
+  hdsm_mirror::Swarm& sw = *hdsm_mirror::as_swarm(swarm);
   const size_t n = (size_t)d.n_local;
   std::unique_ptr<AgentS[]> tmp(new (std::nothrow) AgentS[n]);
   if (!tmp) return fail(HDSM_ERR_DEVICE, "out of host memory");
   int rc = hipMemcpy(tmp.get(), d.d_agents.get(), n * sizeof(AgentS), hipMemcpyDeviceToHost) == hipSuccess
                ? hdsm_swarm_import_state(swarm, tmp.get(), d.n_local)
                : HDSM_ERR_DEVICE;
-  if (rc == HDSM_OK) rc = hdsm_swarm_import_path_state(swarm, d.path.period, d.path.round, d.path.due.data(), d.path.goals.data());
+  if (rc == HDSM_OK) rc = sw.path.adopt(d.path.period, d.path.round, d.path.due);
+  if (rc == HDSM_OK) sw.adopt_goals(d.path.goals);
   if (rc == HDSM_OK && d.audit.ever) {
     std::vector<hdsm_flight_report> rep(n);
     if (hipMemcpy(rep.data(), d.audit.d_report.get(), n * sizeof(hdsm_flight_report), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
-    else rc = hdsm_swarm_import_audit(swarm, d.audit.on ? 1 : 0, d.audit.sep_warn, rep.data());
+    else rc = sw.audit.adopt(d.audit.on, d.audit.sep_warn, std::move(rep));
   }
   if (rc == HDSM_OK && d.cmd.ready()) {
     std::vector<double> yaw(n);
     if (hipMemcpy(yaw.data(), d.cmd.d_yaw.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
-    else rc = hdsm_swarm_import_commands(swarm, d.cmd.on ? 1 : 0, d.cmd.yaw_idx, d.cmd.k_p_yaw, yaw.data());
+    else sw.cmd.adopt(d.cfg.step_plan, d.cmd.on, d.cmd.yaw_idx, d.cmd.k_p_yaw, yaw);
   }
   return rc ? fail(rc, "state download failed") : HDSM_OK;
 }

@@ -29,22 +29,11 @@ int hdsm_internal_local_gather(void* comm, double* plans_all, uint8_t* has_plan_
 int hdsm_internal_gather_local_launch(int32_t world, int32_t per, int32_t rec, const double* const* d_send, double* plans_all,
                                       uint8_t* has_plan_all, void* hip_stream);
 
-// (swarm_host.cpp) the host mirror's flight in and out of the device-resident loop:
-// the plain agent states (hdsm_sw::AgentS [n_local]) and the configuration of a shard; every out argument may be NULL
+// (swarm_flight.cpp) the hooks of the host mirror that stay C (the rest of the flight in and out of the device-resident loop is typed:
+// swarm_host.h). The plain agent states (hdsm_sw::AgentS [n_local]) and the configuration of a shard; every out argument may be NULL
 int hdsm_swarm_export_state(void* swarm, void* agents_out, int32_t* n_local, int32_t* n_rob, int32_t* first_id, hdsm_params* prm,
                             hdsm_swarm_config* cfg, const int8_t** world, int32_t wdim[3], double worigin[3]);
 int hdsm_swarm_import_state(void* swarm, const void* agents_in, int32_t n_local);
-// the path step's round phase and pending agents (and the goals a device loop set between its rounds); due / goals may be NULL
-int hdsm_swarm_export_path_state(void* swarm, int32_t* period, int64_t* round, uint8_t* due);
-int hdsm_swarm_import_path_state(void* swarm, int32_t period, int64_t round, const uint8_t* due, const double* goals);
-// the clearance radius of the path step (0: off)
-int hdsm_swarm_export_path_clearance(void* swarm, double* search_rad);
-// the audit's setting and record (report [n_local], may be NULL on export)
-int hdsm_swarm_export_audit(void* swarm, int32_t* on, int32_t* ever, double* sep_warn, hdsm_flight_report* report);
-int hdsm_swarm_import_audit(void* swarm, int32_t on, double sep_warn, const hdsm_flight_report* report);
-// the partition of hdsm_swarm_set_groups: n_groups (0: none) and, when group_start is given, its n_groups + 1 entries
-// (at most n_rob + 1); hdsm_dswarm_create sets it on the solver handle it is given
-int hdsm_swarm_export_groups(void* swarm, int32_t* n_groups, int32_t* group_start);
 // rounds flown on the device into the planner records: rows [n_rounds][n_local][9]
 int hdsm_swarm_append_history(void* swarm, int32_t n_rounds, const double* rows);
 
@@ -67,9 +56,6 @@ int hdsm_internal_track_args(const hdsm_tracking* m, int32_t n, const int32_t* a
 int hdsm_internal_command_args(int32_t n, int32_t n_hor, int32_t step_plan, double dt, int32_t yaw_idx, double k_p_yaw, const int32_t* n_ref,
                                const double* ref_point, const double* state_before, const double* records, const int32_t* valid_in,
                                const double* state_after, const double* yaw);
-// (swarm_host.cpp) the command setting and yaw of the mirror (yaw [n_local], may be NULL on export; ever: set_commands was called)
-int hdsm_swarm_export_commands(void* swarm, int32_t* ever, int32_t* on, int32_t* yaw_idx, double* k_p_yaw, double* yaw);
-int hdsm_swarm_import_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p_yaw, const double* yaw);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

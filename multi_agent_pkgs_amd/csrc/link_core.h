@@ -1,5 +1,5 @@
 // link_core.h — stale plans: the step shift of a neighbour's record and the per-sender link model of the device loop, as plain
-// functions that compile for the host form (hdsm_link_deliver_host, swarm_host.cpp) AND for the device (k_plan_prepass, k_ref_pack,
+// functions that compile for the host form (hdsm_link_deliver_host, link_host.cpp) AND for the device (k_plan_prepass, k_ref_pack,
 // k_reference, k_tasc_planes, k_deliver). One source: integers and copies only, so the two forms agree bit for bit.
 //
 // Shift. With shift s >= 0 every instance but k's own reads record k as R'[i] = R[min(i + s, N)], i = 0..N: the plan advanced by s

@@ -1,5 +1,5 @@
 // track_core.h — imperfect tracking: the state an agent has flown instead of the state it planned, and the record of the difference,
-// as plain functions that compile for the host forms (track_host.cpp, swarm_host.cpp) AND for the device kernel (track_kernels.hip).
+// as plain functions that compile for the host forms (track_host.cpp, swarm_models.cpp) AND for the device kernel (track_kernels.hip).
 // One source, the same IEEE operations in the same order (floating-point contraction off, products first, sums left to right, sqrt
 // correctly rounded on both sides), so the forms agree bit for bit.
 //
