@@ -657,6 +657,104 @@ int hdsm_dswarm_command_stats(void* dswarm, int64_t out[3]);
 int hdsm_command_atan2(int32_t n, const double* y, const double* x, double* out);
 int hdsm_command_sincos(int32_t n, const double* x, double* s, double* c);
 
+/* ---- a vehicle in the loop: a quadrotor and its controller behind the commit (no new ABI minor; discover by symbol) ----------------------
+ * The fourth box of planner -> command -> vehicle model -> measured state: a rigid body with thrust along its z axis, first-order
+ * lags on body rates and thrust, and the position / attitude controller that sits on it. It flies the setpoints of "commands for the
+ * vehicle" sub-step by sub-step and its state becomes state_curr: the next round's corridor, reference and x_0 see what was flown.
+ * Opt-in; one source (csrc/vehicle_core.h: the stage order and the sum order written there ARE the definition) for the host form, the
+ * host mirror and k_vehicle, which agree bit for bit: only + - * / and sqrt, contraction off, sincos from csrc/command_core.h, draws
+ * from csrc/track_core.h. g = (0, 0, -9.81), command_core.h's constant.
+ *   settings   hdsm_vehicle, one for all agents. n_sub 1..1000 sub-steps per plan interval, h = dt / (double)n_sub. feed 0 HOLD:
+ *              setpoint j is held over interval j (the bridge: states[1], once per iteration); 1 ALONG: the knot interval j starts
+ *              from, advanced at constant acceleration: t = (double)s * h for sub-step s, p_r = (p_j + v_j t) + 0.5 (a_j (t t)),
+ *              v_r = v_j + a_j t, a_r = a_j; knot 0 is traj_curr[0] (`start`), knot j > 0 is setpoint j - 1. acc_from 0: the
+ *              acceleration written to state_curr stays the plan's (as k_track); 1: the model's acceleration at the end state.
+ *              kp, kv >= 0 position and velocity gains; k_att >= 0 attitude error to body rate, 1/s; tau_rate, tau_thrust > 0 s;
+ *              0 <= thrust_min <= thrust_max specific thrust, m/s^2; rate_max > 0 rad/s; drag >= 0, 1/s, world axes; seed, wind,
+ *              gust (>= 0) as hdsm_tracking: w = wind + gust * s_ax with draws 0..2 under key(seed, global id, q), q the vehicle
+ *              round (0 = the first round after hdsm_*_set_vehicle), drawn once per agent and round and held over it. Every entry
+ *              finite; a setting that violates a bound is refused before anything is touched.
+ *   state      hdsm_vehicle_state, 128 bytes: pos, vel, quat (x, y, z, w), omega (body rates), thrust, yaw_cmd (the last yaw
+ *              commanded), one reserved double (0).
+ *   seat       a vehicle on a 9-state (p, v, a) and a yaw: pos = p, vel = v, quat = the attitude of "commands for the vehicle" for
+ *              (a, sin yaw, cos yaw) divided by its norm, omega = 0, thrust = clamp(sqrt(t.t), thrust_min, thrust_max), t = a - g,
+ *              yaw_cmd = yaw.
+ *   controller once per sub-step, held over it. x_b, y_b, z_b the columns of R(q); (p_r, v_r, a_r) the reference:
+ *              a_c = ((a_r + kp (p_r - p)) + kv (v_r - v)) - g;  z_d = a_c / sqrt(a_c.a_c) if a_c.a_c > 0, else z_b;
+ *              f_c = clamp(a_c . z_b, thrust_min, thrust_max);  x_i = (cos yaw, sin yaw, 0);  y_d = z_d x x_i divided by its norm
+ *              (norm 0: y_b);  x_d = y_d x z_d;  e_R = 1/2 vee(R_d^T R - R^T R_d);  omega_c = clamp(-(k_att e_R), +-rate_max).
+ *   plant      one classical RK4 step of length h over (p, v, q, omega, f) with omega_c, f_c and w held: p' = v;
+ *              v' = ((f z_b(q) + g) - drag v) + w;  q' = 1/2 q (x) (0, omega);  omega' = (omega_c - omega) / tau_rate;
+ *              f' = (f_c - f) / tau_thrust (evaluated as a product with 1.0 / tau, rounded once);  then q = q / sqrt(q.q).
+ *   a round    step_plan * n_sub sub-steps against the step_plan setpoints of k_command. valid != 0 (2, the shifted fallback,
+ *              included): flown as given, under `feed`. valid = 0 with a quaternion that is not all zero ("no plan yet"): the
+ *              position held (the hold form whatever `feed` says). valid = 0 and the quaternion all zero (something upstream was not
+ *              finite): the vehicle hovers where it stood at the start of the interval: p_r = p, v_r = a_r = 0, yaw = yaw_cmd.
+ *              Afterwards flown[0:6] = the vehicle's position and velocity, flown[6:9] by acc_from; d and the velocity norm against
+ *              planned_end (in the loop: state_curr as the commit left it, traj_curr[step_plan] for an agent with a plan) are booked
+ *              as a model round of the agent's hdsm_track_record; the pose record is rewritten from the vehicle: its position,
+ *              velocity, flown[6:9], ITS OWN quaternion, the commanded yaw, the last setpoint's valid. An end state that is not
+ *              finite is not stored: the vehicle is re-seated on planned_end and the last yaw commanded (0 if that is not finite), the
+ *              agent is counted in `reseated`, flown = planned_end, nothing is booked, dist = 0.
+ *   hdsm_vehicle_default      a Crazyflie-class setting, wind and gust 0. PROPOSALS: no flight was measured with them.
+ *   hdsm_vehicle_seat_host    out [n] from states [n][9] and yaw [n]; pure.
+ *   hdsm_vehicle_fly_host     one round of n agents agent_id (global ids) in vehicle round `round` (0 .. 2^40): start [n][9],
+ *                             setpoint [n][step_plan], planned_end [n][9], vstate [n] in and out -> flown [n][9], dist [n] and pose
+ *                             [n] (either may be NULL), stats[4] (may be NULL) += agent-rounds flown, reseated, sub-steps with the
+ *                             thrust clamped, sub-steps with a rate clamped. Pure. hdsm_vehicle_fly_batch: the same through
+ *                             k_vehicle on `device` (host pointers), bit for bit. HDSM_ERR_BAD_ARG before anything is touched: a
+ *                             NULL where a pointer is needed, a setting out of bounds, n < 0, step_plan outside 1..HDSM_MAX_HOR, dt
+ *                             not positive and finite, round outside 0..2^40.
+ *   hdsm_swarm_set_vehicle    the host mirror: hdsm_swarm_commit flies every agent behind the command step; the samples go into the
+ *                             mirror's track records. At a switch-on (the first, and any after the vehicle was off: the agents
+ *                             moved on without it) every vehicle is seated on state_curr and the command yaw; a call while it is on
+ *                             changes the setting, restarts the vehicle round and keeps the vehicles. NULL: off, records kept. HDSM_ERR_BAD_ARG: a setting
+ *                             out of bounds, commands off (the vehicle needs the setpoints and the yaw), a tracking model on. While a
+ *                             vehicle is on, hdsm_*_set_tracking(non-NULL) and hdsm_*_set_commands(on = 0) are refused.
+ *                             hdsm_*_set_states* keeps working and re-seats the masked vehicles on the given state and the agent's yaw.
+ *   hdsm_dswarm_set_vehicle   the device loop: k_vehicle, one lane per flown agent, right behind k_command inside entry [5] of the
+ *                             phase timing and before the history row and the audit are taken; the scripted tail is never touched.
+ *                             Synchronises. Device memory (the states, four counters, the track records) is allocated by the first
+ *                             call with a setting; a flight that never calls it allocates and launches nothing new.
+ *   hdsm_*_vehicle_states     out [n_local]; an error before the first hdsm_*_set_vehicle. hdsm_dswarm_vehicle_states_device: the
+ *                             device address, valid until hdsm_dswarm_destroy, written on the rounds' stream.
+ *   hdsm_dswarm_vehicle_stats out[0] launches of k_vehicle, out[1] agent-rounds flown, out[2] reseated, out[3] sub-steps with the
+ *                             thrust clamped, out[4] sub-steps with a rate clamped, since hdsm_dswarm_create. Synchronises once a
+ *                             vehicle was on.
+ * hdsm_dswarm_create takes the mirror's setting, vehicle round and vehicle states over, hdsm_dswarm_download(swarm) hands them back:
+ * a vehicle has memory, and a flight that is taken over does not jump. */
+typedef struct hdsm_vehicle {
+  int32_t  n_sub, feed, acc_from, pad;
+  double   kp[3], kv[3], k_att[3];
+  double   tau_rate, tau_thrust, thrust_min, thrust_max;
+  double   rate_max[3], drag[3];
+  uint64_t seed;
+  double   wind[3], gust[3];
+} hdsm_vehicle;                        /* 224 bytes */
+
+typedef struct hdsm_vehicle_state {
+  double pos[3], vel[3];
+  double quat[4];                      /* x, y, z, w */
+  double omega[3];
+  double thrust, yaw_cmd;
+  double reserved0;                    /* 0; the record is 128 bytes */
+} hdsm_vehicle_state;
+
+int hdsm_vehicle_default(hdsm_vehicle* m);
+int hdsm_vehicle_seat_host(const hdsm_vehicle* m, int32_t n, const double* states, const double* yaw, hdsm_vehicle_state* out);
+int hdsm_vehicle_fly_host(const hdsm_vehicle* m, int32_t n, const int32_t* agent_id, int32_t step_plan, double dt, int64_t round,
+                          const double* start, const hdsm_command* setpoint, const double* planned_end, hdsm_vehicle_state* vstate,
+                          double* flown, double* dist, hdsm_command* pose, int64_t stats[4]);
+int hdsm_vehicle_fly_batch(int32_t device, const hdsm_vehicle* m, int32_t n, const int32_t* agent_id, int32_t step_plan, double dt,
+                           int64_t round, const double* start, const hdsm_command* setpoint, const double* planned_end,
+                           hdsm_vehicle_state* vstate, double* flown, double* dist, hdsm_command* pose, int64_t stats[4]);
+int hdsm_swarm_set_vehicle(void* swarm, const hdsm_vehicle* m);
+int hdsm_swarm_vehicle_states(void* swarm, hdsm_vehicle_state* out);
+int hdsm_dswarm_set_vehicle(void* dswarm, const hdsm_vehicle* m);
+int hdsm_dswarm_vehicle_states(void* dswarm, hdsm_vehicle_state* out);
+int hdsm_dswarm_vehicle_states_device(void* dswarm, void** d_states);
+int hdsm_dswarm_vehicle_stats(void* dswarm, int64_t out[5]);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

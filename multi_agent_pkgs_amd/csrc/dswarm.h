@@ -1,7 +1,7 @@
 // dswarm.h — private host header of the hdsm_dswarm_ entry points: the state of a device-resident shard (DSwarm) and what the files
 // of the loop share and nothing else — swarm_kernels.hip (the round), dswarm_world.hip (map updates in flight), dswarm_audit.hip (audit,
 // history, groups), dswarm_flight.cpp (the flight in and out, goals) and dswarm_models.cpp (link faults, scripted agents, imperfect
-// tracking). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
+// tracking, commands, the vehicle). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -152,6 +152,18 @@ struct Commands {
   bool ready() const { return (bool)d_cnt; }
 };
 
+// a vehicle in the loop (hdsm_dswarm_set_vehicle; nothing is allocated or launched before the first call with a setting): the setting
+// while it is on, the vehicle round the next k_vehicle flies, the launches, the state per agent ([n_local]; the scripted tail's are never
+// touched) and the counters [agent-rounds flown, reseated, sub-steps with the thrust clamped, with a rate clamped]
+struct Vehicle {
+  bool on = false;
+  hdsm_vehicle m{};
+  long long q = 0, launches = 0;
+  DevBuf<hdsm_vehicle_state> d_state;
+  DevBuf<unsigned long long> d_cnt;
+  bool ready() const { return (bool)d_cnt; }
+};
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -191,6 +203,7 @@ struct DSwarm {
   bool grouped = false;
   DevBuf<int32_t> d_gstart, d_range;
   DevBuf<hdsm_group_report> d_greport;
+  Vehicle veh;
 };
 
 inline DSwarm* as_dswarm(void* dswarm) { return static_cast<DSwarm*>(dswarm); }
@@ -210,6 +223,10 @@ int hand_back(DSwarm& d, void* swarm);
 // (dswarm_models.cpp) the command buffers, allocated by the first call that needs them (the caller has set the device); the setting
 // and the yaw [n_local] (NULL: zeros) onto the device (the device is idle)
 int commands_setup(DSwarm* d, bool on, int yaw_idx, double k_p_yaw, const double* yaw0);
+// (dswarm_models.cpp) the vehicle buffers, allocated by the first call that needs them, and the setting switched on (the caller has set
+// the device, which is idle). vs [n_local]: the states to start from; NULL: every flown agent is seated on its state_curr and yaw,
+// unless the vehicle is on already.
+int vehicle_setup(DSwarm* d, const hdsm_vehicle& m, long long q, const hdsm_vehicle_state* vs);
 // (swarm_kernels.hip) every event a timed round records
 int timing_events(DSwarm* d);
 // (dswarm_audit.hip) the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports

@@ -28,7 +28,7 @@ int hdsm_dswarm::upload_goals_and_due(DSwarm* d) {
 
 // The mirror's flight becomes the device's (hdsm_dswarm_create, after alloc_round_buffers): the path step's phase and pending agents,
 // the clearance mode, the agent states, ids and goals, the world (hworld: the mirror's grid or NULL), the partition, the audit's
-// setting and record, the command setting and yaw. Each is read from the mirror's member struct (swarm_host.h).
+// setting and record, the command setting and yaw, the vehicle setting, round and states. Each is read from the mirror's member struct (swarm_host.h).
 int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
   const hdsm_mirror::Swarm& sw = *hdsm_mirror::as_swarm(swarm);
   const size_t n = (size_t)d.n_local;
@@ -76,11 +76,13 @@ int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
   }
   if (sw.cmd.on)  // the command setting and yaw of the mirror (a flight taken over keeps its yaw)
     if (int rc = commands_setup(&d, true, sw.cmd.yaw_idx, sw.cmd.k_p_yaw, sw.cmd.yaw.data())) return rc;
+  if (sw.veh.on)  // the vehicle setting, round and states of the mirror (a vehicle has memory: a flight taken over does not jump)
+    if (int rc = vehicle_setup(&d, sw.veh.m, sw.veh.q, sw.veh.state.data())) return rc;
   return HDSM_OK;
 }
 
 // The device's flight back into the mirror (hdsm_dswarm_download; the device is idle): the agent states, the path step's phase,
-// pending agents and goals, the audit's setting and record, the command setting and yaw. Each piece goes through the adopt of the
+// pending agents and goals, the audit's setting and record, the command setting and yaw, the vehicle setting, round and states. Each piece goes through the adopt of the
 // mirror's member struct, which keeps that struct's invariants.
 int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
   hdsm_mirror::Swarm& sw = *hdsm_mirror::as_swarm(swarm);
@@ -101,6 +103,11 @@ int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
     std::vector<double> yaw(n);
     if (hipMemcpy(yaw.data(), d.cmd.d_yaw.get(), n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
     else sw.cmd.adopt(d.cfg.step_plan, d.cmd.on, d.cmd.yaw_idx, d.cmd.k_p_yaw, yaw);
+  }
+  if (rc == HDSM_OK && d.veh.ready()) {
+    std::vector<hdsm_vehicle_state> vs(n);
+    if (hipMemcpy(vs.data(), d.veh.d_state.get(), n * sizeof(hdsm_vehicle_state), hipMemcpyDeviceToHost) != hipSuccess) rc = HDSM_ERR_DEVICE;
+    else sw.veh.adopt(d.veh.on, d.veh.m, d.veh.q, std::move(vs)), sw.track.ready(d.n_local);
   }
   return rc ? fail(rc, "state download failed") : HDSM_OK;
 }

@@ -1,7 +1,9 @@
 // dswarm_models.cpp — what a caller puts between the plans and the flight of the device-resident loop, set between rounds: link faults
-// (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip), imperfect tracking (k_track, track_kernels.hip) and
-// the commands for the vehicle (k_command, command_kernels.hip), each with its counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
-// (hdsm_dswarm_set_states*), through track_device.h.
+// (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip), imperfect tracking (k_track, track_kernels.hip), the
+// commands for the vehicle (k_command, command_kernels.hip) and the vehicle itself (k_vehicle, vehicle_kernels.hip), each with its
+// counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
+// (hdsm_dswarm_set_states*, through track_device.h) and k_seat (a vehicle seated at a switch-on or on a state from outside, through
+// vehicle_device.h).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -12,6 +14,7 @@
 #include "link_core.h"
 #include "script_device.h"
 #include "track_device.h"
+#include "vehicle_device.h"
 
 using namespace hdsm_dswarm;
 
@@ -37,6 +40,9 @@ int track_external(DSwarm* d, const double* d_states, const uint8_t* d_mask, hip
                                                   nullptr, nullptr, nullptr, row},
                                st));
     ++t.external_launches;
+    // a vehicle that sits on the agent is re-seated on what was measured (the same rows: masked and finite), with the agent's yaw
+    if (d->veh.ready())
+      HIP_TRY(hdsm_veh::launch_seat(hdsm_veh::Seat{n_fly, d->veh.m, d_states, 9, d->cmd.d_yaw.get(), d_mask, d->veh.d_state.get()}, st));
   }
   return HDSM_OK;
 }
@@ -61,6 +67,33 @@ int hdsm_dswarm::commands_setup(DSwarm* d, bool on, int yaw_idx, double k_p_yaw,
     m.yaw_idx = yaw_idx, m.k_p_yaw = k_p_yaw;
   }
   m.on = on;
+  return HDSM_OK;
+}
+
+int hdsm_dswarm::vehicle_setup(DSwarm* d, const hdsm_vehicle& m, long long q, const hdsm_vehicle_state* vs) {
+  Vehicle& v = d->veh;
+  const size_t n = (size_t)d->n_local;
+  if (int rc = track_records_ready(d)) return rc;
+  const bool first = !v.ready();
+  if (first) {
+    hdsm_mem::FirstError ok;
+    ok(v.d_state.alloc_zeroed(n)), ok(v.d_cnt.alloc_zeroed(4));
+    if (!ok.ok()) {
+      v.d_cnt.reset();
+      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_vehicle: ") + hipGetErrorString(ok.e));
+    }
+    HIP_TRY(hipDeviceSynchronize());  // (the fills are done before a kernel of any stream writes into the buffers)
+  }
+  v.m = m, v.q = q;
+  if (vs != nullptr) {
+    if (n) HIP_TRY(hipMemcpy(v.d_state.get(), vs, n * sizeof(hdsm_vehicle_state), hipMemcpyHostToDevice));
+  } else if (!v.on && d->n_fly() > 0) {  // a switch-on: the vehicle was off (or never there) while the agents moved
+    HIP_TRY(hdsm_veh::launch_seat(hdsm_veh::Seat{d->n_fly(), m, &d->d_agents.get()[0].state_curr[0], sizeof(AgentS) / sizeof(double), d->cmd.d_yaw.get(),
+                                                 nullptr, v.d_state.get()},
+                                  nullptr));
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  v.on = true;
   return HDSM_OK;
 }
 
@@ -176,6 +209,7 @@ int hdsm_dswarm_set_tracking(void* dswarm, const hdsm_tracking* m) {
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   if (m && !hdsm_track::model_valid(m))
     return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_tracking: every entry of the model finite, gust and jitter not negative");
+  if (m && d->veh.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_tracking: a vehicle is on (hdsm_dswarm_set_vehicle): it is what deviates from the plan");
   Track& t = d->track;
   if (!m && !t.on) return HDSM_OK;
   if (int rc = device_idle(d)) return rc;
@@ -232,6 +266,7 @@ int hdsm_dswarm_set_commands(void* dswarm, int32_t on, int32_t yaw_idx, double k
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   if (on && !hdsm_cmd::settings_valid(yaw_idx, d->c.N, k_p_yaw, yaw0, d->n_local))
     return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_commands: yaw_idx in 0 .. n_hor, k_p_yaw and every yaw0 finite");
+  if (!on && d->veh.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_commands: a vehicle is on (hdsm_dswarm_set_vehicle): it needs the setpoints and the yaw");
   if (!on && !d->cmd.on) return HDSM_OK;
   if (int rc = device_idle(d)) return rc;
   return commands_setup(d, on != 0, yaw_idx, k_p_yaw, yaw0);
@@ -265,6 +300,53 @@ int hdsm_dswarm_command_stats(void* dswarm, int64_t out[3]) {
   unsigned long long cnt[2] = {0, 0};
   HIP_TRY(hipMemcpy(cnt, d->cmd.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
   out[1] = (int64_t)cnt[0], out[2] = (int64_t)cnt[1];
+  return HDSM_OK;
+}
+
+// A vehicle in the loop (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_vehicle(void* dswarm, const hdsm_vehicle* m) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  Vehicle& v = d->veh;
+  if (!m) {
+    if (!v.on) return HDSM_OK;
+    if (int rc = device_idle(d)) return rc;
+    v.on = false;
+    return HDSM_OK;
+  }
+  if (!hdsm_veh::settings_valid(m)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_vehicle: a setting out of its bounds (include/hdsm_swarm.h), or not finite");
+  if (!d->cmd.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_vehicle: commands are off (hdsm_dswarm_set_commands): the vehicle needs the setpoints and the yaw");
+  if (d->track.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_vehicle: a tracking model is on (hdsm_dswarm_set_tracking)");
+  if (int rc = device_idle(d)) return rc;
+  return vehicle_setup(d, *m, 0, nullptr);
+}
+
+int hdsm_dswarm_vehicle_states(void* dswarm, hdsm_vehicle_state* out) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!out && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_vehicle_states: null argument");
+  if (!d->veh.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_vehicle_states: no hdsm_dswarm_set_vehicle yet");
+  if (int rc = device_idle(d)) return rc;
+  if (d->n_local) HIP_TRY(hipMemcpy(out, d->veh.d_state.get(), (size_t)d->n_local * sizeof(hdsm_vehicle_state), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_vehicle_states_device(void* dswarm, void** d_states) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !d_states) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (!d->veh.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_vehicle_states_device: no hdsm_dswarm_set_vehicle yet");
+  *d_states = d->veh.d_state.get();
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_vehicle_stats(void* dswarm, int64_t out[5]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->veh.launches, out[1] = out[2] = out[3] = out[4] = 0;
+  if (!d->veh.ready()) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(cnt, d->veh.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
+  for (int c = 0; c < 4; ++c) out[1 + c] = (int64_t)cnt[c];
   return HDSM_OK;
 }
 

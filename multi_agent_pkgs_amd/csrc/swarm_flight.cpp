@@ -32,6 +32,11 @@ void Commands::adopt(int step_plan, bool on_, int yaw_idx_, double k_p_yaw_, con
   std::copy(yaw_.begin(), yaw_.end(), yaw.begin());
 }
 
+void Vehicle::adopt(bool on_, const hdsm_vehicle& m_, long long q_, std::vector<hdsm_vehicle_state> state_) {
+  on = on_, ever = true, m = m_, q = q_;
+  state = std::move(state_);
+}
+
 extern "C" {
 
 // the plain agent states and the configuration of a shard (hdsm_dswarm_create reads the configuration; the tests read the agents)

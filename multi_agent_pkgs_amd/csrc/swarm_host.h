@@ -1,6 +1,6 @@
 // swarm_host.h — private header of the host mirror (include/hdsm_swarm.h, the hdsm_swarm_ entry points): the state of a shard on the
 // host (Swarm) and what the files of the mirror share and nothing else — swarm_host.cpp (the round), swarm_router.cpp (hdsm_swarm_route),
-// swarm_world.cpp (world and paths between rounds), swarm_models.cpp (audit, groups, tracking, commands) and swarm_flight.cpp (the
+// swarm_world.cpp (world and paths between rounds), swarm_models.cpp (audit, groups, tracking, commands, the vehicle) and swarm_flight.cpp (the
 // flight in and out of the device-resident loop). dswarm_flight.cpp includes it too: take_over reads the member structs, hand_back
 // gives each its piece back through that struct's adopt.
 #pragma once
@@ -101,6 +101,19 @@ struct Commands {
   void adopt(int step_plan, bool on_, int yaw_idx_, double k_p_yaw_, const std::vector<double>& yaw_);
 };
 
+// a vehicle in the loop (vehicle_core.h; hdsm_swarm_set_vehicle): the setting while it is on, the vehicle round the next commit flies,
+// the state per agent (empty until the first setting; then seated) and the counters [agent-rounds flown, reseated, sub-steps with the
+// thrust clamped, with a rate clamped]
+struct Vehicle {
+  bool on = false, ever = false;
+  hdsm_vehicle m{};
+  long long q = 0;
+  std::vector<hdsm_vehicle_state> state;
+  int64_t stats[4] = {0, 0, 0, 0};
+  // (swarm_flight.cpp) the setting, the vehicle round and the states [n_local] a device loop was left with
+  void adopt(bool on_, const hdsm_vehicle& m_, long long q_, std::vector<hdsm_vehicle_state> state_);
+};
+
 // timing of the round in flight (f3): the duration of the fused launch as reported by the caller, wall clock at prepare
 struct Round {
   double solve_ms = 0;
@@ -124,6 +137,7 @@ struct Swarm {
   Groups groups;
   Track track;
   Commands cmd;
+  Vehicle veh;
   // the core configuration of an entry point: built once per call and passed down (the test hook is read at every call)
   hdsm_sw::Cfg core_cfg() const {
     hdsm_sw::Cfg c{};
@@ -158,5 +172,7 @@ void path_round(Swarm& sw, const hdsm_sw::Cfg& cc);
 void track_commit(Swarm& sw);
 std::vector<double> commands_before(const Swarm& sw);
 void commands_commit(Swarm& sw, const std::vector<double>& before, const int32_t* status);
+// ... and, behind the commands, the vehicles flying this round's setpoints: state_curr, the track records and the poses take what they flew
+void vehicle_commit(Swarm& sw);
 
 }  // namespace hdsm_mirror

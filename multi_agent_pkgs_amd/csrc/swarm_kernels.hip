@@ -13,6 +13,9 @@
 //                k_commit has just padded (script_kernels.hip)                                   one wavefront per scripted agent
 //   k_command    (only with commands on, hdsm_dswarm_set_commands) the yaw step, the setpoints of the interval about to be flown and the
 //                pose the round ends in (command_kernels.hip)                                    one lane per agent
+//   k_vehicle    (only with a vehicle on, hdsm_dswarm_set_vehicle) every flown agent's quadrotor and controller fly those setpoints,
+//                step_plan * n_sub sub-steps; state_curr, the track record and the pose take what it flew (vehicle_kernels.hip)
+//                                                                                                one lane per flown agent
 //   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
 //                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
@@ -37,6 +40,7 @@
 #include "path_core.h"
 #include "script_device.h"
 #include "track_device.h"
+#include "vehicle_device.h"
 
 #ifdef CD_PROFILE
 // development builds only: the phase counters of the corridor kernel's decompositions (read and cleared); [12] cycles of the whole
@@ -710,6 +714,17 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
     a.yaw = m.d_yaw.get(), a.setpoint = m.d_setpoint.get(), a.pose = m.d_pose.get(), a.cnt = m.d_cnt.get();
     HIP_TRY(hdsm_cmd::launch(a, st));
     ++m.launches;
+  }
+  if (Vehicle& v = d.veh; v.on) {  // the flown agents' vehicles fly the setpoints just written (inside phase [5]); state_curr takes what they flew
+    if (n_fly > 0) {
+      hdsm_veh::Launch a{};
+      a.n = n_fly, a.step_plan = d.c.step_plan, a.q = v.q, a.dt = d.prm.dt, a.m = v.m;
+      a.agents = d.d_agents.get(), a.records = d.track.d_rec.get(), a.setpoint = d.cmd.d_setpoint.get(), a.vstate = v.d_state.get();
+      a.pose = d.cmd.d_pose.get(), a.cnt = v.d_cnt.get();
+      HIP_TRY(hdsm_veh::launch(a, st));
+      ++v.launches;
+    }
+    ++v.q;
   }
   if (local) {
     if (int rc = hdsm_internal_local_published(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());

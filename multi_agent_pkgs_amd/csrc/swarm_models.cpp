@@ -1,5 +1,6 @@
 // swarm_models.cpp — the models the host mirror flies beside the round (include/hdsm_swarm.h): the flight audit, neighbour groups,
-// imperfect tracking and commands for the vehicle, each with its entry points and its step of hdsm_swarm_commit. Pure host C++.
+// imperfect tracking, commands for the vehicle and the vehicle in the loop, each with its entry points and its step of
+// hdsm_swarm_commit. Pure host C++.
 #include <algorithm>
 
 #include "audit_core.h"
@@ -7,6 +8,7 @@
 #include "hdsm_internal.h"
 #include "swarm_host.h"
 #include "track_core.h"
+#include "vehicle_core.h"
 
 using namespace hdsm_mirror;
 
@@ -52,12 +54,60 @@ void hdsm_mirror::commands_commit(Swarm& sw, const std::vector<double>& before, 
   }
 }
 
+// the vehicles fly the setpoints commands_commit has just written (vehicle_core.h): state_curr takes the flown state, the track record
+// the sample, the pose the vehicle's own attitude
+void hdsm_mirror::vehicle_commit(Swarm& sw) {
+  Vehicle& v = sw.veh;
+  if (!v.on) return;
+  const int step = sw.cfg.step_plan;
+  for (int k = 0; k < sw.n_local; ++k) {
+    AgentS& ag = sw.agents[k];
+    double start[9], planned[9], flown[9], d, dvel;
+    for (int c = 0; c < 9; ++c) start[c] = ag.traj_curr[0][c], planned[c] = ag.state_curr[c];
+    int n_thrust = 0, n_rate = 0;
+    const int ok = hdsm_veh::agent_round(v.m, ag.id, v.q, step, sw.prm.dt, start, &sw.cmd.setpoint[(size_t)k * step], planned, v.state[(size_t)k], flown,
+                                         &d, &dvel, &sw.cmd.pose[(size_t)k], &n_thrust, &n_rate);
+    for (int c = 0; c < 9; ++c) ag.state_curr[c] = flown[c];
+    if (ok) hdsm_track::book(sw.track.rec[(size_t)k], d, dvel, false);
+    v.stats[0] += ok, v.stats[1] += 1 - ok, v.stats[2] += n_thrust, v.stats[3] += n_rate;
+  }
+  ++v.q;
+}
+
 extern "C" {
+
+// A vehicle in the loop on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_swarm_set_vehicle(void* swarm, const hdsm_vehicle* m) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  Vehicle& v = sw->veh;
+  if (!m) {
+    v.on = false;
+    return HDSM_OK;
+  }
+  if (!hdsm_veh::settings_valid(m) || !sw->cmd.on || sw->track.on) return HDSM_ERR_BAD_ARG;
+  sw->track.ready(sw->n_local);
+  if (!v.on) {  // a switch-on (the vehicle was off, or never there, while the agents moved): every vehicle seated on its agent's state and yaw
+    v.state.assign((size_t)sw->n_local, hdsm_vehicle_state{});
+    for (int k = 0; k < sw->n_local; ++k) hdsm_veh::seat(*m, sw->agents[k].state_curr, sw->cmd.yaw[(size_t)k], v.state[(size_t)k]);
+    v.ever = true;
+  }
+  v.m = *m, v.q = 0, v.on = true;
+  return HDSM_OK;
+}
+
+int hdsm_swarm_vehicle_states(void* swarm, hdsm_vehicle_state* out) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw || !sw->veh.ever || (!out && sw->n_local)) return HDSM_ERR_BAD_ARG;
+  std::copy(sw->veh.state.begin(), sw->veh.state.end(), out);
+  return HDSM_OK;
+}
 
 // Imperfect tracking on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
 int hdsm_swarm_set_tracking(void* swarm, const hdsm_tracking* m) {
   Swarm* sw = as_swarm(swarm);
   if (!sw || (m && !hdsm_track::model_valid(m))) return HDSM_ERR_BAD_ARG;
+  if (m && sw->veh.on) return HDSM_ERR_BAD_ARG;  // (a vehicle is what deviates from the plan)
   sw->track.on = m != nullptr;
   if (m) sw->track.model = *m, sw->track.q = 0, sw->track.ready(sw->n_local);
   return HDSM_OK;
@@ -74,6 +124,7 @@ int hdsm_swarm_set_states(void* swarm, const double* states, const uint8_t* mask
     double from[9];
     for (int c = 0; c < 9; ++c) from[c] = ag.state_curr[c], ag.state_curr[c] = to[c];
     hdsm_track::book(sw->track.rec[(size_t)k], hdsm_track::pos_dist(from, to), hdsm_track::vel_dist(from, to), true);
+    if (sw->veh.ever) hdsm_veh::seat(sw->veh.m, to, sw->cmd.yaw[(size_t)k], sw->veh.state[(size_t)k]);  // the vehicle is where it was measured
   }
   return HDSM_OK;
 }
@@ -90,6 +141,7 @@ int hdsm_swarm_set_commands(void* swarm, int32_t on, int32_t yaw_idx, double k_p
   Swarm* sw = as_swarm(swarm);
   if (!sw) return HDSM_ERR_BAD_ARG;
   if (on && !hdsm_cmd::settings_valid(yaw_idx, sw->prm.n_hor, k_p_yaw, yaw0, sw->n_local)) return HDSM_ERR_BAD_ARG;
+  if (!on && sw->veh.on) return HDSM_ERR_BAD_ARG;  // (the vehicle needs the setpoints and the yaw)
   Commands& m = sw->cmd;
   const size_t n = (size_t)sw->n_local;
   m.ready(n, sw->cfg.step_plan);

@@ -16,7 +16,7 @@ import re
 
 import numpy as np
 
-from .params import Command, HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord
+from .params import Command, HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord, Vehicle, VehicleState
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("HDSM_LIBRARY") or os.path.join(_HERE, "libhdsm.so")  # (HDSM_LIBRARY: a development build, e.g. -DCD_PROFILE)
@@ -42,7 +42,13 @@ TRACK_RECORD = np.dtype([("rounds", "<i8"), ("external", "<i8"), ("dist_sum", "<
                          ("dvel_max", "<f8")])                                                             # hdsm_track_record
 COMMAND = np.dtype([("pos", "<f8", 3), ("vel", "<f8", 3), ("acc", "<f8", 3), ("quat", "<f8", 4), ("yaw", "<f8"), ("valid", "<i4"), ("pad", "<i4"),
                     ("reserved0", "<f8")])                                                                 # hdsm_command
+VEHICLE_STATE = np.dtype([("pos", "<f8", 3), ("vel", "<f8", 3), ("quat", "<f8", 4), ("omega", "<f8", 3), ("thrust", "<f8"), ("yaw_cmd", "<f8"),
+                          ("reserved0", "<f8")])                                                           # hdsm_vehicle_state
+VEHICLE = np.dtype([("n_sub", "<i4"), ("feed", "<i4"), ("acc_from", "<i4"), ("pad", "<i4"), ("kp", "<f8", 3), ("kv", "<f8", 3), ("k_att", "<f8", 3),
+                    ("tau_rate", "<f8"), ("tau_thrust", "<f8"), ("thrust_min", "<f8"), ("thrust_max", "<f8"), ("rate_max", "<f8", 3),
+                    ("drag", "<f8", 3), ("seed", "<u8"), ("wind", "<f8", 3), ("gust", "<f8", 3)])            # hdsm_vehicle
 assert COMMAND.itemsize == 128 == C.sizeof(Command)
+assert VEHICLE_STATE.itemsize == 128 == C.sizeof(VehicleState) and VEHICLE.itemsize == 224 == C.sizeof(Vehicle)
 assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104 and GROUP_REPORT.itemsize == 128
 assert TRACK_RECORD.itemsize == 48 == C.sizeof(TrackRecord) and C.sizeof(Tracking) == 80
 
@@ -79,9 +85,10 @@ CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": 
 CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32_t", np.int32), ("int8_t", np.int8), ("uint8_t", np.uint8),
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
                                                   ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
-                                                  ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD), ("hdsm_command", COMMAND))})
+                                                  ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD), ("hdsm_command", COMMAND),
+                                                  ("hdsm_vehicle_state", VEHICLE_STATE))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
-                                                  ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking))})
+                                                  ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking), ("hdsm_vehicle", Vehicle))})
 
 
 def parse_declarations(text):
@@ -122,7 +129,7 @@ EXPORTS = tuple(SIGNATURES)
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
               ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_track_", None),
-              ("hdsm_command_", None),
+              ("hdsm_command_", None), ("hdsm_vehicle_", None),
               ("hdsm_", "hdsm_last_error"))
 
 _lib = None
@@ -560,6 +567,40 @@ def command(yaw, n_ref, ref_point, state_before, records, valid, state_after, st
     call(fn, *lead, n, records.shape[1] - 1, int(step_plan), float(dt), int(yaw_idx), float(k_p_yaw), n_ref, ref_point, state_before, records,
          valid, state_after, yaw, setpoint, pose, stats)
     return yaw, setpoint, pose, (int(stats[0]), int(stats[1]))
+
+
+def vehicle_default():
+    """hdsm_vehicle_default: a Crazyflie-class setting (params.Vehicle), wind and gust 0. Proposals: no flight was measured with them."""
+    m = Vehicle()
+    call("hdsm_vehicle_default", C.byref(m))
+    return m
+
+
+def vehicle_seat(model, states, yaw):
+    """hdsm_vehicle_seat_host: vehicles (lib.VEHICLE_STATE [n]) seated on states [n][9] = (p, v, a) and yaw [n]: at rest in attitude, the
+    quaternion of that acceleration and yaw, the thrust that acceleration asks for (clamped)."""
+    yaw = _f64(yaw).reshape(-1)
+    states = _f64(states).reshape(yaw.size, 9)
+    out = np.zeros(yaw.size, VEHICLE_STATE)
+    call("hdsm_vehicle_seat_host", model, yaw.size, states, yaw, out)
+    return out
+
+
+def vehicle_fly(model, ids, start, setpoint, planned_end, vstate, step_plan=1, dt=0.1, round=0, device=None):
+    """hdsm_vehicle_fly_host: one round of n vehicles (csrc/vehicle_core.h) — ids [n] global ids, start [n][9] knot 0 of the along feed
+    (traj_curr[0]), setpoint [n][step_plan] of lib.COMMAND, planned_end [n][9] the state the commit left, vstate [n] of
+    lib.VEHICLE_STATE (not modified). Returns (vstate after the round, flown [n][9], dist [n], pose [n] of lib.COMMAND, (agent-rounds
+    flown, reseated, sub-steps with the thrust clamped, with a rate clamped)). device given: hdsm_vehicle_fly_batch, the same through
+    k_vehicle on that device, bit for bit."""
+    ids = _i32(ids).reshape(-1)
+    n = ids.size
+    start, planned_end = _f64(start).reshape(n, 9), _f64(planned_end).reshape(n, 9)
+    setpoint = np.ascontiguousarray(setpoint, dtype=COMMAND).reshape(n, int(step_plan))
+    vs = np.array(vstate, dtype=VEHICLE_STATE, order="C", copy=True).reshape(n)
+    flown, dist, pose, stats = np.zeros((n, 9)), np.zeros(n), np.zeros(n, COMMAND), np.zeros(4, np.int64)
+    lead, fn = ((), "hdsm_vehicle_fly_host") if device is None else ((int(device),), "hdsm_vehicle_fly_batch")
+    call(fn, *lead, model, n, ids, int(step_plan), float(dt), int(round), start, setpoint, planned_end, vs, flown, dist, pose, stats)
+    return vs, flown, dist, pose, tuple(int(x) for x in stats)
 
 
 def command_atan2(y, x):

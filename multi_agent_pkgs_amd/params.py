@@ -161,3 +161,20 @@ class TrackRecord(C.Structure):
     difference. lib.TRACK_RECORD is the numpy dtype of the same layout."""
     _fields_ = [("rounds", C.c_int64), ("external", C.c_int64), ("dist_sum", C.c_double), ("dist_sq_sum", C.c_double),
                 ("dist_max", C.c_double), ("dvel_max", C.c_double)]
+
+
+class Vehicle(C.Structure):
+    """hdsm_vehicle (include/hdsm_swarm.h, "a vehicle in the loop"): sub-steps per plan interval, the feed (0 hold, 1 along), where the
+    acceleration of state_curr comes from (0 the plan, 1 the model), position / velocity / attitude gains, the lags on body rates and
+    thrust, the thrust and rate limits, a linear drag, and seed / wind / gust as params.Tracking. scenarios.crazyflie_vehicle() fills it."""
+    _fields_ = [("n_sub", C.c_int32), ("feed", C.c_int32), ("acc_from", C.c_int32), ("pad", C.c_int32),
+                ("kp", C.c_double * 3), ("kv", C.c_double * 3), ("k_att", C.c_double * 3),
+                ("tau_rate", C.c_double), ("tau_thrust", C.c_double), ("thrust_min", C.c_double), ("thrust_max", C.c_double),
+                ("rate_max", C.c_double * 3), ("drag", C.c_double * 3), ("seed", C.c_uint64), ("wind", C.c_double * 3), ("gust", C.c_double * 3)]
+
+
+class VehicleState(C.Structure):
+    """hdsm_vehicle_state: position, velocity, the attitude quaternion (x, y, z, w), body rates, specific thrust, the last yaw
+    commanded. lib.VEHICLE_STATE is the numpy dtype of the same layout."""
+    _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("quat", C.c_double * 4), ("omega", C.c_double * 3), ("thrust", C.c_double),
+                ("yaw_cmd", C.c_double), ("reserved0", C.c_double)]

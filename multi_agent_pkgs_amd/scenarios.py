@@ -112,6 +112,26 @@ def gust_model(seed=0, wind=(0.0, 0.0, 0.0), gust=(0.0, 0.0, 0.0), jitter=(0.0, 
     return m
 
 
+def crazyflie_vehicle(n_sub=10, feed=0, acc_from=0, seed=0, wind=(0.0, 0.0, 0.0), gust=(0.0, 0.0, 0.0), **over):
+    """A vehicle for SwarmShard.set_vehicle / DeviceSwarm.set_vehicle (params.Vehicle): the library's Crazyflie-class defaults
+    (hdsm_vehicle_default — proposals, no flight was measured with them) with n_sub sub-steps per plan interval, the feed (0 hold: a
+    setpoint is held over its interval, as planner_crazyswarm_bridge does; 1 along: the knot advanced at constant acceleration),
+    acc_from (0: state_curr keeps the plan's acceleration, 1: the model's), a wind and a gust amplitude per axis in m/s^2 drawn once per
+    agent and round, and any other field by name (kp=(..), tau_rate=.., thrust_max=..)."""
+    from .lib import vehicle_default
+    m = vehicle_default()
+    m.n_sub, m.feed, m.acc_from, m.seed = int(n_sub), int(feed), int(acc_from), int(seed) & 0xFFFFFFFFFFFFFFFF
+    over.update(wind=wind, gust=gust)
+    for name, v in over.items():
+        if isinstance(getattr(m, name), float):
+            setattr(m, name, float(v))
+        else:
+            v = np.asarray(v, dtype=np.float64).reshape(3)
+            for ax in range(3):
+                getattr(m, name)[ax] = v[ax]
+    return m
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

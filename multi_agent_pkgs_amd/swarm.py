@@ -225,6 +225,20 @@ class SwarmShard:
         call("hdsm_swarm_commands", self.h, sp, pose, yaw)
         return sp, pose, yaw
 
+    # ---- a vehicle in the loop (include/hdsm_swarm.h) ----
+    def set_vehicle(self, model=None):
+        """hdsm_swarm_set_vehicle: from the next commit on every agent's vehicle (params.Vehicle, scenarios.crazyflie_vehicle) flies the
+        round's setpoints sub-step by sub-step behind the command step, and state_curr, the track records and the poses take what it
+        flew. Needs set_commands on and no tracking model. A switch-on seats every vehicle on state_curr and the command yaw. None:
+        off. A DeviceSwarm made from this shard takes setting and vehicles over."""
+        call("hdsm_swarm_set_vehicle", self.h, model)
+
+    def vehicle_states(self):
+        """hdsm_swarm_vehicle_states: the vehicle per local agent (lib.VEHICLE_STATE)."""
+        vs = np.zeros(self.n_local, _lib.VEHICLE_STATE)
+        call("hdsm_swarm_vehicle_states", self.h, vs)
+        return vs
+
     def state(self):
         pos = np.zeros((self.n_local, 3))
         dist = np.zeros(self.n_local)
@@ -550,6 +564,32 @@ class DeviceSwarm:
         """hdsm_dswarm_command_stats: launches of k_command, agent-rounds with a yaw step taken, agent-rounds skipped (the reference point
         closer than sqrt(0.1) m, or missing). Synchronises once commands were on."""
         return dict(zip(("launches", "steps", "skipped"), self._counters("hdsm_dswarm_command_stats", 3)))
+
+    # ---- a vehicle in the loop (include/hdsm_swarm.h) ----
+    def set_vehicle(self, model=None):
+        """hdsm_dswarm_set_vehicle: from the next round on k_vehicle, right behind k_command, flies every flown agent's vehicle
+        (params.Vehicle, scenarios.crazyflie_vehicle) against the round's setpoints — step_plan * n_sub controller evaluations and RK4
+        steps — and state_curr, the history, the track records and the poses take what it flew. Needs set_commands on and no tracking
+        model. A switch-on seats every vehicle on state_curr and the yaw. None: off. Synchronises."""
+        call("hdsm_dswarm_set_vehicle", self.h, model)
+
+    def vehicle_states(self):
+        """hdsm_dswarm_vehicle_states: the vehicle per local agent (lib.VEHICLE_STATE). Synchronises."""
+        vs = np.zeros(self.shard.n_local, _lib.VEHICLE_STATE)
+        call("hdsm_dswarm_vehicle_states", self.h, vs)
+        return vs
+
+    def vehicle_states_device(self):
+        """hdsm_dswarm_vehicle_states_device: the device address of the vehicle states [n_local], 128-byte hdsm_vehicle_state records,
+        valid for the dswarm's life and written on the rounds' stream."""
+        p = C.c_void_p()
+        call("hdsm_dswarm_vehicle_states_device", self.h, C.byref(p))
+        return p.value
+
+    def vehicle_stats(self):
+        """hdsm_dswarm_vehicle_stats: launches of k_vehicle, agent-rounds flown, vehicles re-seated (an end state that was not finite),
+        sub-steps with the thrust clamped, sub-steps with a body rate clamped. Synchronises once a vehicle was on."""
+        return dict(zip(("launches", "flown", "reseated", "thrust_clamped", "rate_clamped"), self._counters("hdsm_dswarm_vehicle_stats", 5)))
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
