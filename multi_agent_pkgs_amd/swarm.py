@@ -381,7 +381,15 @@ class DeviceSwarm:
         call("hdsm_dswarm_download", self.h, self.shard.h if states else None, plans, has, status, C.byref(failed))
         return plans, has, status, failed.value
 
-    PHASES = ("k_corridor", "k_vel_cap", "hdsm_reference_device", "k_keep_free", "hdsm_replan_device", "k_commit", "exchange")
+    def download_raw(self):
+        """hdsm_dswarm_download_raw: (plans buffer [per * world_size][N+1][9] as it is, sentinels included; send buffer
+        [per][N+1][9]). Synchronises the device."""
+        N = self.shard.prm.n_hor
+        plans, send = np.zeros((self.per * self.world_size, N + 1, 9)), np.zeros((self.per, N + 1, 9))
+        call("hdsm_dswarm_download_raw", self.h, plans, send)
+        return plans, send
+
+    PHASES =("k_corridor", "k_vel_cap", "hdsm_reference_device", "k_keep_free", "hdsm_replan_device", "k_commit", "exchange")
 
     def set_phase_timing(self, on=True):
         """hdsm_dswarm_set_phase_timing: HIP events between the launches of the following rounds (see phase_ms)."""
@@ -686,12 +694,8 @@ class LocalRanks:
         call("hdsm_dswarm_round_ranks", self.world, self._dsw, self._comms, st)
 
     def download_raw(self, rank):
-        """hdsm_dswarm_download_raw of one rank: (plans buffer [world * per][N+1][9] as it is, sentinels included; send buffer
-        [per][N+1][9]). Synchronises that rank's device."""
-        N = self.shards[rank].prm.n_hor
-        plans, send = np.zeros((self.world * self.per, N + 1, 9)), np.zeros((self.per, N + 1, 9))
-        call("hdsm_dswarm_download_raw", self.dswarms[rank].h, plans, send)
-        return plans, send
+        """DeviceSwarm.download_raw of one rank: (plans buffer [world * per][N+1][9], send buffer [per][N+1][9])."""
+        return self.dswarms[rank].download_raw()
 
     def close(self):
         for d in self.dswarms:

@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from multi_agent_pkgs_amd import lib as hdsm, scenarios as sc, swarm  # noqa: E402
 from multi_agent_pkgs_amd.params import agile_params  # noqa: E402
-import test_gpu_configs as T  # noqa: E402
+import flight_harness as T  # noqa: E402
 from oracle import pyoracle as orc  # noqa: E402
 
 rnd = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -18,7 +18,7 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 n_rob, N = 48, 10
 prm = agile_params(N, max_rows_static=18)
 os.environ["HDSM_SCANNER"] = "0"
-sol, loop = T._device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+sol, loop = T.device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
 raw, origin = sc.forest_for_circle(n_rob, seed=21)
 assert loop.set_world(sc.inflate(raw), origin) == 0
 recs = []

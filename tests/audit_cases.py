@@ -9,6 +9,8 @@ import math
 
 import numpy as np
 
+from refmath import py_raycast as _py_raycast
+
 N_HOR = 4          # horizon of the generated records (>= every step_plan used)
 BIG = np.finfo(np.float64).max
 
@@ -224,3 +226,34 @@ def tracks_in_world(rng, world, worigin, n, vs=0.3, S=2):
             p0[t, ax] = lo[ax] + vs * int(rng.integers(1, world.shape[2 - ax] - 1))
             steps[t, :, ax] = 0.0
     return records(p0, steps, vel=rng.uniform(-9, 9, (n, N_HOR + 1, 3))), np.ones(n, np.uint8), S
+
+
+DBL_MAX = BIG
+SEP_RTOL = 1e-12      # sep2 against numpy: the two evaluate the same closed form in a different order of operations
+CLEAR = 1e-9          # a partner is compared exactly when numpy's runner-up is more than this (relative) behind
+
+
+def check_separation(got, plans, has, S, first, n_local, r, z):
+    """One batch of the library (host or device form) against the numpy restatement. Returns the number of rows whose runner-up is
+    within CLEAR (their partner / sub-step may be the runner-up's). The runner-up of a partner is the best OTHER partner; the
+    sub-step is compared where, in addition, the same partner's next best sub-step is either more than CLEAR behind or an exact tie
+    (the end of one sub-step and the start of the next are the same positions: both sides then take the smaller sub-step)."""
+    sep2, partner, substep, second, second_sub = np_separation(plans, has, S, first, n_local, r, z)
+    lone = partner < 0
+    assert (got["partner"][lone] == -1).all() and (got["sep2"][lone] == DBL_MAX).all() and (got["substep"][lone] == 0).all()
+    assert ((got["partner"] < 0) == lone).all()
+    ok = ~lone
+    assert (np.abs(got["sep2"][ok] - sep2[ok]) <= SEP_RTOL * sep2[ok]).all(), float(np.abs(got["sep2"][ok] / sep2[ok] - 1).max())
+    clear = ok & (second - sep2 > CLEAR * sep2)
+    assert (got["partner"][clear] == partner[clear]).all()
+    clear_sub = clear & ((second_sub == sep2) | (second_sub - sep2 > CLEAR * sep2))
+    assert (got["substep"][clear_sub] == substep[clear_sub]).all()
+    return int((ok & ~clear_sub).sum())
+
+
+def check_track(got, plans, has, S, first, n_local, world, origin, vs=0.3):
+    want = np_track(plans, has, S, first, n_local, world, origin, vs, _py_raycast)
+    for f in ("occupied", "unknown", "crossed", "pot"):
+        assert np.array_equal(got[f], want[f]), (f, np.nonzero(got[f] != want[f])[0][:8])
+    assert np.array_equal(got["dist"], want["dist"]) and np.array_equal(got["speed"], want["speed"])
+    return want

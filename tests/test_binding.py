@@ -9,7 +9,7 @@ import pytest
 
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd.params import HdsmParams, agile_params, default_map_config
-from test_host import ROOT, declared_functions  # a regular expression of its own, independent of the binding's parser
+from abi_headers import ROOT, declared_functions  # a regular expression of its own, independent of the binding's parser
 
 HEADERS = ("hdsm.h", "hdsm_swarm.h", "hdsm_stats.h")
 

@@ -9,33 +9,13 @@ import pytest
 
 import audit_cases as ac
 import dmp_cases as dc
+from audit_cases import CLEAR, DBL_MAX, check_separation, check_track
+from kernel_elf import LIB, _group_segments, _kernel_descriptors
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import agile_params
-from refmath import py_raycast as _py_raycast
 
-DBL_MAX = np.finfo(np.float64).max
-SEP_RTOL = 1e-12      # sep2 against numpy: the two evaluate the same closed form in a different order of operations
-CLEAR = 1e-9          # a partner is compared exactly when numpy's runner-up is more than this (relative) behind
 TIE_RATE = 0.02       # rows of a batch that may be closer than CLEAR
-
-
-def check_separation(got, plans, has, S, first, n_local, r, z):
-    """One batch of the library (host or device form) against the numpy restatement. Returns the number of rows whose runner-up is
-    within CLEAR (their partner / sub-step may be the runner-up's). The runner-up of a partner is the best OTHER partner; the
-    sub-step is compared where, in addition, the same partner's next best sub-step is either more than CLEAR behind or an exact tie
-    (the end of one sub-step and the start of the next are the same positions: both sides then take the smaller sub-step)."""
-    sep2, partner, substep, second, second_sub = ac.np_separation(plans, has, S, first, n_local, r, z)
-    lone = partner < 0
-    assert (got["partner"][lone] == -1).all() and (got["sep2"][lone] == DBL_MAX).all() and (got["substep"][lone] == 0).all()
-    assert ((got["partner"] < 0) == lone).all()
-    ok = ~lone
-    assert (np.abs(got["sep2"][ok] - sep2[ok]) <= SEP_RTOL * sep2[ok]).all(), float(np.abs(got["sep2"][ok] / sep2[ok] - 1).max())
-    clear = ok & (second - sep2 > CLEAR * sep2)
-    assert (got["partner"][clear] == partner[clear]).all()
-    clear_sub = clear & ((second_sub == sep2) | (second_sub - sep2 > CLEAR * sep2))
-    assert (got["substep"][clear_sub] == substep[clear_sub]).all()
-    return int((ok & ~clear_sub).sum())
 
 
 def check_sampling(rng, plans, has, S, r, z):
@@ -131,14 +111,6 @@ def own_track_worlds(map_preprocess):
     raw, origin = sc.forest_for_circle(48, seed=21)
     yield "forest", sc.inflate(raw), origin
     yield "preprocessed", dc.preprocessed(raw, map_preprocess), origin
-
-
-def check_track(got, plans, has, S, first, n_local, world, origin, vs=0.3):
-    want = ac.np_track(plans, has, S, first, n_local, world, origin, vs, _py_raycast)
-    for f in ("occupied", "unknown", "crossed", "pot"):
-        assert np.array_equal(got[f], want[f]), (f, np.nonzero(got[f] != want[f])[0][:8])
-    assert np.array_equal(got["dist"], want["dist"]) and np.array_equal(got["speed"], want["speed"])
-    return want
 
 
 def test_own_track_rule_follows_the_python_raycast_and_plain_look_ups(oracle):
@@ -269,36 +241,10 @@ def test_planner_records_are_unchanged_by_the_audit_and_arguments_are_checked(or
     assert (sh.flight_report()["rounds"] == 1).all()                            # the record is kept when the audit is switched off
 
 
-def _group_segments(tmp_path):
-    """{kernel name: group_segment_fixed_size} read from the code objects _kernel_descriptors unbundled into tmp_path. In a kernel's
-    note the group segment stands a few lines IN FRONT of its name (the keys are in alphabetical order), so the figure is searched
-    backwards from the name, up to the end of the kernel before it."""
-    import glob
-    import re
-    import subprocess
-
-    from test_kernel_resources import LLVM
-    out = {}
-    for co in sorted(glob.glob(str(tmp_path / "dev*.co"))):
-        lines = subprocess.check_output([LLVM + "/llvm-readelf", "--notes", co], text=True).splitlines()
-        for i, ln in enumerate(lines):
-            m = re.match(r"\s*\.name:\s+(_Z\S+)\s*$", ln)
-            if not m:
-                continue
-            for back in lines[i - 1::-1]:
-                g = re.match(r"\s*\.group_segment_fixed_size:\s+(\d+)\s*$", back)
-                if g:
-                    out[m.group(1)] = int(g.group(1))
-                    break
-                assert not re.match(r"\s*(- )?\.(symbol|vgpr_count|private_segment_fixed_size):", back), (m.group(1), back)
-    return out
-
-
 def test_audit_kernels_use_no_scratch_and_little_lds(tmp_path):
     """Every k_audit* kernel of the built library: no private segment, no spill, its own LDS within the 160 KB of a CU."""
     import os
 
-    from test_kernel_resources import LIB, _kernel_descriptors
     assert os.path.exists(LIB), "libhdsm.so is not built"
     desc = _kernel_descriptors(tmp_path)
     mine = {k: v for k, v in desc.items() if "k_audit" in k}

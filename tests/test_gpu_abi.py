@@ -437,7 +437,7 @@ def test_staging_overflow_in_a_shared_cu_kernel_is_rescued(hdsm, oracle, monkeyp
     import torch
     import problems
     from multi_agent_pkgs_amd.params import make_params
-    from test_gpu_fuzz import K
+    from fuzz_cases import K
     prm = make_params(n_hor=10, max_rows_static=18, poly_hor=4)
     n_rob = 64
     sn = problems.swarm_snapshot(prm, n_rob, seed=4242, spacing=1.0, narrow=False, turn=False, chamfer=False, absent_frac=0, speed=(0.0, 3.0))
@@ -501,7 +501,7 @@ def test_staging_overflow_at_each_shared_cu_capacity_is_rescued(hdsm, oracle, mo
     on the handle carries the rescue pass — no flags, the oracle's answers."""
     import torch
     import staging_cases as sc
-    from test_gpu_fuzz import K
+    from fuzz_cases import K
     prm, args = sc.batch(sc.CASES[shape]["over"])
     n_inst, n_rob = args[1].shape[0], args[7].shape[0]
     o = sc.verdict(oracle, prm, args, n_threads=32)

@@ -12,28 +12,23 @@ How the mirror follows bit for bit: before a round the device's agent states go 
 round's reference, solver output and status — read back from the device's committed agents through a second shard — are handed to
 hdsm_swarm_set_reference / hdsm_swarm_commit of the mirror, which then looks from the same state_curr at the same reference point, commits
 the same record and flies the same tracking model. The plans it publishes must be the device's, byte for byte, before anything is compared."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import command_cases as cc
 import corridor_oracle as co
 import loop_cases as lc
+from flight_harness import MirroredRank, hdsm, model, raw  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import assert_no_scratch_no_lds
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
-from multi_agent_pkgs_amd.lib import COMMAND, call, command
+from multi_agent_pkgs_amd.lib import COMMAND, command
 from multi_agent_pkgs_amd.params import K_P_YAW, YAW_IDX, agile_params
-from test_gpu_configs import hdsm  # noqa: F401  (the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
 N_ROB, ROUNDS = cc.N_FLIGHT, 12
 ZERO = np.zeros(1, COMMAND)[0].tobytes()
-
-
-def model():
-    return sc.gust_model(7, (0.5, 0.0, 0.0), (2.0, 2.0, 1.0), (0.01, 0.01, 0.005))
 
 
 @pytest.mark.parametrize("step_plan", [1, 3])
@@ -62,49 +57,19 @@ def test_the_batch_equals_the_host_form_bit_for_bit(hdsm, n, step_plan):  # noqa
         assert not pose["valid"].any()
 
 
-class Rank:
-    """One shard of a device flight with the host mirror that follows it (the module docstring)."""
+class Rank(MirroredRank):
+    """tests/flight_harness.py's MirroredRank with what the commands add: setpoints, poses, yaw, the host form, the counters."""
 
-    def __init__(self, dsw, prm, cfg, starts, goals, n_fly=None):
-        self.dsw, self.mirror, self.prm = dsw, dsw.shard, prm
-        self.n = self.mirror.n_local
-        self.n_fly = self.n if n_fly is None else n_fly
-        self.post = swarm.SwarmShard(prm, cfg, self.mirror.n_rob, self.mirror.first_id, starts, goals)
-        self.on = False
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
         self.rounds_on = self.steps = self.skipped = 0
 
-    def set_commands(self, on=True, yaw0=None):
-        self.dsw.set_commands(on, yaw0=yaw0)
-        self.mirror.set_commands(on, yaw0=yaw0)
-        self.on = on
+    def empty_round(self, tag):
+        if self.on:
+            assert self.dsw.commands()[1].size == 0
 
-    def before_round(self):
-        if self.n:
-            self.dsw.download(states=True)
-        self.pre = co.export_agents(self.mirror)[0]
-        self.yaw = self.mirror.commands()[2] if self.on else None
-
-    def after_round(self, tag):
-        n, N, P = self.n, self.prm.n_hor, self.prm.poly_hor
-        G = self.dsw.per * self.dsw.world_size
-        plans, has, status, failed = np.zeros((G, N + 1, 9)), np.zeros(G, np.uint8), np.zeros(n, np.int32), C.c_int32(0)
-        call("hdsm_dswarm_download", self.dsw.h, self.post.h if n else None, plans, has, status, C.byref(failed))
-        if n == 0:
-            if self.on:
-                assert self.dsw.commands()[1].size == 0
-            return
-        ag = co.export_agents(self.post)[0]
-        ref_full = np.array([lc.arr(ag[k].traj_ref, co.MAXH + 1, 6)[:N + 1] for k in range(n)])
-        self.mirror.set_reference(ref_full, np.array([ag[k].path_vel for k in range(n)]))
-        out = dict(traj=np.array([lc.arr(ag[k].traj_curr, co.MAXH + 1, 9)[:N + 1] for k in range(n)]),
-                   ctrl=np.array([lc.arr(ag[k].ctrl_curr, co.MAXH, 3)[:N] for k in range(n)]),
-                   used=np.array([[ag[k].poly_used[j] for j in range(P)] for k in range(n)], np.uint8), status=status)
-        mine, mine_has = self.mirror.commit(out)
-        first, fly = self.mirror.first_id, self.n_fly
-        assert mine[:fly].tobytes() == plans[first:first + fly].tobytes() and (mine_has[:fly] == has[first:first + fly]).all(), tag
-        after = co.export_agents(self.mirror)[0]
-        state = np.array([lc.arr(after[k].state_curr, 9) for k in range(n)])
-        assert state[:fly].tobytes() == np.array([lc.arr(ag[k].state_curr, 9) for k in range(fly)]).tobytes(), tag     # (also the flown one)
+    def feature_round(self, tag, ref_full, out, after, state):
+        n, N, fly, status = self.n, self.prm.n_hor, self.n_fly, out["status"]
         if not self.on:
             return
         self.rounds_on += 1
@@ -228,13 +193,6 @@ def test_local_ranks_write_their_own_commands(hdsm, n_rob, world):  # noqa: F811
     flock.close()
 
 
-def _raw(dsw):
-    N, G = dsw.shard.prm.n_hor, dsw.per * dsw.world_size
-    raw = np.zeros((G, N + 1, 9))
-    call("hdsm_dswarm_download_raw", dsw.h, raw, None)
-    return raw.tobytes()
-
-
 def test_commands_do_not_steer(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
     (sol0, off), (sol1, on) = _one_rank(hdsm, prm), _one_rank(hdsm, prm)
@@ -242,7 +200,7 @@ def test_commands_do_not_steer(hdsm):  # noqa: F811
     on.dsw.set_commands(True, yaw0=np.linspace(-3.0, 3.0, N_ROB))
     for r in range(ROUNDS):
         off.dsw.round(), on.dsw.round()
-        assert _raw(off.dsw) == _raw(on.dsw), r
+        assert raw(off.dsw).tobytes() == raw(on.dsw).tobytes(), r
     assert off.dsw.history(mirror=False)[0].tobytes() == on.dsw.history(mirror=False)[0].tobytes()
     assert off.dsw.command_stats() == dict(launches=0, steps=0, skipped=0) and on.dsw.command_stats()["launches"] == ROUNDS
     with pytest.raises(hdsm.HdsmError) as e:
@@ -287,16 +245,4 @@ def test_the_device_pointers(hdsm):  # noqa: F811
 
 
 def test_k_command_uses_no_scratch_and_no_lds(tmp_path):
-    import os
-
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
-    assert os.path.exists(LIB), "libhdsm.so is not built"
-    desc = _kernel_descriptors(tmp_path)
-    mine = {k: v for k, v in desc.items() if "k_command" in k}
-    assert len(mine) == 1, sorted(mine)
-    lds = _group_segments(tmp_path)
-    for k, v in mine.items():
-        assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
-        assert lds[k] == 0, (k, lds[k])
-    print({k: dict(v, group_segment_fixed_size=lds[k]) for k, v in mine.items()})
+    assert_no_scratch_no_lds(tmp_path, "k_command")

@@ -16,35 +16,14 @@ through the host mirror's fallback: the published plan is the shifted previous o
 import numpy as np
 import pytest
 
+from flight_harness import device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 from multi_agent_pkgs_amd import scenarios as sc
-from multi_agent_pkgs_amd.params import agile_params, agile_ref_config
+from multi_agent_pkgs_amd.params import agile_params
 
 pytestmark = pytest.mark.gpu
 
 TRAJ_TOL = 1e-7
 OBJ_RTOL = 1e-6
-
-
-@pytest.fixture(scope="module")
-def hdsm():
-    from multi_agent_pkgs_amd import lib
-    return lib
-
-
-def _device_loop(hdsm, prm, cfg, n_rob, starts=None, goals=None, radius=None):
-    from multi_agent_pkgs_amd import swarm
-    sol = hdsm.Solver(prm, n_rob, n_rob)
-    rcfg = agile_ref_config()
-
-    def solve(inp, plans, has):
-        return sol.replan(inp["agent_id"], inp["state"], inp["ref"], inp["n_poly"], inp["n_rows"], inp["A"], inp["b"], plans, has)
-
-    def ref_dev(ids, path, n_path, plans, has, vel_cap=None):
-        full, _, pv = sol.reference(rcfg, ids, path, n_path, plans, has, vel_cap=vel_cap)
-        return full, pv
-
-    loop = swarm.SwarmLoop(prm, cfg, n_rob, solve=solve, radius=radius, reference=ref_dev, starts=starts, goals=goals)
-    return sol, loop
 
 
 def _check_round(sol, oracle, prm, rec, out, n_parity, rng, plane_chunk=32, traj_tol=TRAJ_TOL):
@@ -152,7 +131,7 @@ def _check_limit_instances(sol, oracle, prm, rec, out, max_check=3):
     return res
 
 
-def test_config_2_64_agents_circle_shipped_geometry(hdsm, oracle):
+def test_config_2_64_agents_circle_shipped_geometry(hdsm, oracle):  # noqa: F811
     """BASELINE configs[1]: 64 agents, circular exchange, empty environment, H = 10 — the geometry of the reference's own
     launch file (R = 22 m, centre (18, 15), z = 1.5: chord 2.16 m), flown until the swarm has crossed; EVERY instance of
     every tenth round is compared with the oracle."""
@@ -161,7 +140,7 @@ def test_config_2_64_agents_circle_shipped_geometry(hdsm, oracle):
     prm = agile_params(N, max_rows_static=18)
     starts, goals = sc.circle_scenario(n_rob, radius=22.0, cx=18.0, cy=15.0, z=1.5)
     assert np.allclose(starts[0], [40.0, 15.0, 1.5]) and np.allclose(goals[0], [-4.0, 15.0, 1.5])   # SURVEY 8d known answers
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob, starts=starts, goals=goals)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob, starts=starts, goals=goals)
     rng = np.random.default_rng(2)
     solved = failed = multi = 0
     dmin = 1e9
@@ -198,14 +177,14 @@ def _pillar_hits(pos, raw, origin, vox=0.3):
     return int((raw[v[:, 2], v[:, 1], v[:, 0]] >= 100).sum())
 
 
-def test_config_3_256_agents_through_a_forest(hdsm, oracle):
+def test_config_3_256_agents_through_a_forest(hdsm, oracle):  # noqa: F811
     """BASELINE configs[2]: 256 agents, forest environment, corridors by voxel decomposition (<= 4 polyhedra), H = 10."""
     from multi_agent_pkgs_amd import swarm
     n_rob, N = 256, 10
     prm = agile_params(N, max_rows_static=18)
     raw, origin = sc.forest_for_circle(n_rob, seed=13)
     occ = sc.inflate(raw)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
     assert loop.set_world(occ, origin) == 0                       # every agent has a route
     rng = np.random.default_rng(3)
     checked, rows_max, chamfered, hits = 0, 0, 0, 0
@@ -227,13 +206,13 @@ def test_config_3_256_agents_through_a_forest(hdsm, oracle):
     print("cfg3: instances checked", checked, "max static rows", rows_max, "agent-rounds inside an obstacle voxel", hits)
 
 
-def test_config_4_1024_agents_circle_through_the_squeeze(hdsm, oracle):
+def test_config_4_1024_agents_circle_through_the_squeeze(hdsm, oracle):  # noqa: F811
     """BASELINE configs[3] on one GPU: 1024 agents, circular exchange, H = 10, through the rounds in which the contracting
     ring reaches the separation limit (the hard rounds of the flight: root relaxations become infeasible by the hundred)."""
     from multi_agent_pkgs_amd import swarm
     n_rob, N = 1024, 10
     prm = agile_params(N, max_rows_static=18)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
     rng = np.random.default_rng(4)
     bad_total, prev_plans = 0, None
     for r in range(186):
@@ -254,7 +233,7 @@ def test_config_4_1024_agents_circle_through_the_squeeze(hdsm, oracle):
     assert d.min() > 0.45                                           # nobody closer than the drone diameter (0.5 m) - tolerance
 
 
-def test_config_5_4096_agents_forest_wall_forest(hdsm, oracle):
+def test_config_5_4096_agents_forest_wall_forest(hdsm, oracle):  # noqa: F811
     """BASELINE configs[4] on one GPU: 4096 agents (64 x 64 lattice, 2.01 m pitch), forest + wall + forest, H = 15."""
     from multi_agent_pkgs_amd import swarm
     n_y = n_z = 64
@@ -267,7 +246,7 @@ def test_config_5_4096_agents_forest_wall_forest(hdsm, oracle):
     starts, goals = sc.lattice_scenario(n_y, n_z)
     cfg = swarm.default_swarm_config()
     cfg.grid_range[2], cfg.grid_z_min = 12.0, -6.0                 # voxel_grid_range of multi_agent_planner_long.launch.py:29
-    sol, loop = _device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
+    sol, loop = device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
     assert loop.set_world(occ, origin) == 0
     rng = np.random.default_rng(5)
     rows_max, limited = 0, []
@@ -288,7 +267,7 @@ def test_config_5_4096_agents_forest_wall_forest(hdsm, oracle):
     print("cfg5: instances that ended on a budget (instance, flags, relative gap to the proven optimum):", limited)
 
 
-def test_voxel_decomposition_on_the_device_matches_the_host_bit_for_bit(hdsm):
+def test_voxel_decomposition_on_the_device_matches_the_host_bit_for_bit(hdsm):  # noqa: F811
     """Row f2 on the device (hdsm_poly_octa3d_batch, one thread per seed) against the host functions hdsm_poly_octa3d /
     hdsm_poly_octa3d_new on the same local grids: rows, row counts and the number of voxels taken must be IDENTICAL — for
     windows cut out of an inflated pillar forest and of forest + wall + forest (ground below, world border inside the
@@ -332,7 +311,7 @@ def test_voxel_decomposition_on_the_device_matches_the_host_bit_for_bit(hdsm):
 
 
 @pytest.mark.parametrize("scene", ["circle", "forest"])
-def test_device_resident_loop_follows_the_host_mirror(hdsm, scene):
+def test_device_resident_loop_follows_the_host_mirror(hdsm, scene):  # noqa: F811
     """hdsm_dswarm_round (corridor -> reference -> replan -> commit -> publish, all on the device, one stream) against the
     host-mirror loop that drives the same device kernels for the reference and the solve: same published plans round after
     round. The per-agent code is one source (csrc/swarm_core.h); the solver's staging order is not deterministic (atomics),
@@ -345,7 +324,7 @@ def test_device_resident_loop_follows_the_host_mirror(hdsm, scene):
     prm = agile_params(N, max_rows_static=18)
 
     def make():
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+        sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
         if scene == "forest":
             raw, origin = sc.forest_for_circle(n_rob, seed=21)
             assert loop.set_world(sc.inflate(raw), origin) == 0
@@ -378,7 +357,7 @@ def test_device_resident_loop_follows_the_host_mirror(hdsm, scene):
 
 
 @pytest.mark.parametrize("scene", ["forest", "fwf"])
-def test_device_corridor_kernel_matches_the_reference_restatement(hdsm, oracle, scene):
+def test_device_corridor_kernel_matches_the_reference_restatement(hdsm, oracle, scene):  # noqa: F811
     """Row f2 on the device: k_corridor (one wavefront per agent, rows of the kept polyhedra in registers, cooperative voxel
     decomposition out of LDS) against oracle/hdsm_oracle.c: orc_safe_corridor — GenerateSafeCorridor (agent_class.cpp:1236-1447)
     restated from the reference text — on every agent of >= 50 rounds of the device-resident loop, in the world of BASELINE
@@ -391,7 +370,7 @@ def test_device_corridor_kernel_matches_the_reference_restatement(hdsm, oracle, 
     if scene == "forest":
         n_rob, N = 64, 10
         prm = agile_params(N, max_rows_static=18)
-        sol, loop = _device_loop(hdsm, prm, cfg, n_rob)
+        sol, loop = device_loop(hdsm, prm, cfg, n_rob)
         raw, origin = sc.forest_for_circle(n_rob, seed=13)
     else:
         n_y, N = 8, 15
@@ -399,7 +378,7 @@ def test_device_corridor_kernel_matches_the_reference_restatement(hdsm, oracle, 
         prm = agile_params(N, max_rows_static=18)
         starts, goals = sc.lattice_scenario(n_y, n_y)
         cfg.grid_range[2], cfg.grid_z_min = 12.0, -6.0
-        sol, loop = _device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
+        sol, loop = device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
         raw, origin = sc.forest_wall_forest(int(np.ceil((10 + 2.01 * n_y) / 30)), int(np.ceil((9 + 2.01 * n_y) / 15)), seed=0)
     assert loop.set_world(sc.inflate(raw), origin) == 0
     dsw = swarm.DeviceSwarm(loop.shard, sol)

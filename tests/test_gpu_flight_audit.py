@@ -8,10 +8,10 @@ import pytest
 
 import audit_cases as ac
 import dmp_cases as dc
+from audit_cases import CLEAR, check_separation, check_track
+from flight_harness import device_loop, hdsm  # noqa: F401  (hdsm: the module's fixture)
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import agile_params
-from test_flight_audit import CLEAR, check_separation, check_track
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 
 pytestmark = pytest.mark.gpu
 
@@ -87,7 +87,7 @@ def _forest_loop(hdsm, n_rob):  # noqa: F811
     raw, origin = sc.forest_for_circle(n_rob, seed=21)
     world = dc.preprocessed(raw, hdsm.map_preprocess)
     from multi_agent_pkgs_amd import swarm
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
     assert loop.set_world(world, origin) == 0
     return prm, sol, loop, world, origin
 
@@ -152,7 +152,7 @@ def test_device_loop_audit_equals_the_restatement_round_by_round(hdsm, tmp_path)
             dsw = swarm.DeviceSwarm(loop.shard, sol)
         else:
             prm = agile_params(10, max_rows_static=18)
-            sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n)
+            sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n)
             world, origin = None, None
             dsw = swarm.DeviceSwarm(loop.shard, sol)
             with pytest.raises(hdsm.HdsmError):
@@ -196,7 +196,7 @@ def test_device_loop_audit_equals_the_restatement_round_by_round(hdsm, tmp_path)
 def test_history_stops_when_full_and_counts_the_rounds_lost(hdsm):  # noqa: F811
     from multi_agent_pkgs_amd import swarm
     prm = agile_params(10, max_rows_static=18)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), 16)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), 16)
     dsw = swarm.DeviceSwarm(loop.shard, sol)
     with pytest.raises(hdsm.HdsmError):
         dsw.history()                                                              # the history is off
@@ -221,7 +221,7 @@ def test_flight_taken_over_in_mid_air_keeps_its_record_and_the_off_switch(hdsm):
     from multi_agent_pkgs_amd import swarm
     n = 32
     prm = agile_params(10, max_rows_static=18)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n)
     loop.shard.set_audit(True)
     r, z = prm.drone_radius, prm.drone_z_offset
     mine = ac.Flight(n, 1)
@@ -249,7 +249,7 @@ def test_flight_taken_over_in_mid_air_keeps_its_record_and_the_off_switch(hdsm):
     assert mine.same_as(rep2) is None, mine.same_as(rep2)
     dsw.close()
     # the off switch
-    sol2, loop2 = _device_loop(hdsm, prm, swarm.default_swarm_config(), n)
+    sol2, loop2 = device_loop(hdsm, prm, swarm.default_swarm_config(), n)
     dsw = swarm.DeviceSwarm(loop2.shard, sol2)
     dsw.set_phase_timing(True)
     for _ in range(3):

@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 
 import problems
+from flight_harness import circle_flight, device_loop, hdsm  # noqa: F401  (hdsm: the module's fixture)
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import agile_params, agile_ref_config
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
-from test_gpu_parity import ARG_KEYS, compare
+from parity_cases import ARG_KEYS, compare
 
 pytestmark = pytest.mark.gpu
 
@@ -230,7 +230,7 @@ def forest_flight(hdsm):  # noqa: F811
     world = sc.inflate(raw)
 
     def make():
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n)
+        sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n)
         assert loop.set_world(world, origin) == 0
         loop.pmax = 49
         loop.shard.set_path_period(1)
@@ -308,16 +308,6 @@ def test_group_report_is_the_fold_of_the_agent_records(forest_flight):
     assert got["rounds"].tolist() == [ROUNDS] * 3 and got["sep_agent"][1] == -1 and (got["sep_agent"][[0, 2]] >= 0).all()
 
 
-def _circle_dswarm(hdsm, prm, starts, goals, groups=None, audit=False):  # noqa: F811
-    from multi_agent_pkgs_amd import swarm
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), starts.shape[0], starts=starts, goals=goals)
-    if groups is not None:
-        loop.shard.set_groups(groups)
-    if audit:
-        loop.shard.set_audit(True, 1.0)
-    return sol, loop, swarm.DeviceSwarm(loop.shard, sol)
-
-
 def test_copies_of_one_swarm_fly_the_same_flight(hdsm):  # noqa: F811
     """Four copies of one 6-agent circle exchange at IDENTICAL coordinates as the groups [0,6,12,18,24], free space, 8 rounds:
     every group flies group 0's flight and the flight of a plain 6-agent dswarm (1e-7, statuses equal). Before the audit was
@@ -330,9 +320,9 @@ def test_copies_of_one_swarm_fly_the_same_flight(hdsm):  # noqa: F811
     starts6, goals6 = sc.circle_scenario(6, radius=5.0)
     starts, goals, groups = sc.repeat_scenario(starts6, goals6, 4)
     assert groups.tolist() == [0, 6, 12, 18, 24]
-    sol1, loop1, one = _circle_dswarm(hdsm, prm, starts6, goals6)
-    sol4, loop4, four = _circle_dswarm(hdsm, prm, starts, goals, groups)
-    solu, loopu, ungrouped = _circle_dswarm(hdsm, prm, starts, goals)
+    sol1, loop1, one = circle_flight(hdsm, prm, starts6, goals6)
+    sol4, loop4, four = circle_flight(hdsm, prm, starts, goals, groups=groups)
+    solu, loopu, ungrouped = circle_flight(hdsm, prm, starts, goals)
     unsolved = 0
     for r in range(8):
         one.round(), four.round(), ungrouped.round()

@@ -14,7 +14,7 @@ import corridor_oracle as co
 import loop_cases as lc
 from multi_agent_pkgs_amd import swarm
 from multi_agent_pkgs_amd.lib import call
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
+from flight_harness import device_loop, hdsm  # noqa: F401  (hdsm: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +27,7 @@ def _mirror(hdsm):  # noqa: F811
     s16, _ = lc.open_scene()
     starts = s16[[0, 1, 2, 8, 9, 10]]
     goals = starts[[4, 5, 3, 1, 2, 0]] + [0.0, 0.3, 0.0]
-    sol, loop = _device_loop(hdsm, prm, cfg, 6, starts=starts, goals=goals)
+    sol, loop = device_loop(hdsm, prm, cfg, 6, starts=starts, goals=goals)
     grid, origin = lc.make_world()
     assert loop.set_world(grid, origin, route=False) == 0
     loop.pmax = 32

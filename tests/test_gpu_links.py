@@ -16,30 +16,18 @@ import pytest
 
 import link_cases as lc
 import shift_cases as shc
+from flight_harness import circle_flight, hdsm, raw  # noqa: F401  (hdsm: the module's fixture)
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
 from multi_agent_pkgs_amd.params import agile_params, agile_ref_config
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 
 pytestmark = pytest.mark.gpu
 
 N_ROB, RADIUS, PLAN_TOL = 8, 4.0, 1e-7
 
 
-def _dswarm(hdsm, prm, audit=False):  # noqa: F811
-    starts, goals = sc.circle_scenario(N_ROB, radius=RADIUS)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=starts, goals=goals)
-    if audit:
-        loop.shard.set_audit(True, 1.0)
-    return sol, loop, swarm.DeviceSwarm(loop.shard, sol)
-
-
-def _raw(dsw):
-    """the plans buffer as it is (sentinels included)"""
-    N, G = dsw.shard.prm.n_hor, dsw.per * dsw.world_size
-    raw = np.zeros((G, N + 1, 9))
-    swarm.call("hdsm_dswarm_download_raw", dsw.h, raw, None)
-    return raw
+def scenario():
+    return sc.circle_scenario(N_ROB, radius=RADIUS)
 
 
 class _SeenView:
@@ -54,9 +42,9 @@ def test_deliveries_equal_the_host_function_bit_for_bit(hdsm, n_hor, name, time_
     from multi_agent_pkgs_amd import lib
     prm = agile_params(n_hor, max_rows_static=18)
     fate = lc.crafted_tables(N_ROB)[name]
-    sol, loop, dsw = _dswarm(hdsm, prm)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario())
     dsw.round()                                            # one round without links: the view of the call holds real plans
-    plans0, has0 = _raw(dsw), dsw.download(states=False)[1]
+    plans0, has0 = raw(dsw), dsw.download(states=False)[1]
     dsw.set_links(fate, time_aware)
     step_plan = swarm.default_swarm_config().step_plan
     host = lib.LinkView(fate, N_ROB, n_hor, step_plan, time_aware, plans0, has0)
@@ -65,7 +53,7 @@ def test_deliveries_equal_the_host_function_bit_for_bit(hdsm, n_hor, name, time_
     rounds = fate.shape[0] + 9
     for r in range(rounds):
         dsw.round()
-        host.deliver(_raw(dsw))
+        host.deliver(raw(dsw))
         s = _SeenView(dsw)
         for got, want, what in ((s.seen, host.seen, "seen"), (s.seen_has, host.seen_has, "seen_has"), (s.seen_round, host.seen_round, "seen_round"),
                                 (s.shift, host.shift, "shift")):
@@ -83,17 +71,17 @@ def test_deliveries_equal_the_host_function_bit_for_bit(hdsm, n_hor, name, time_
 
 def test_an_all_zero_table_is_the_links_off_flight(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
-    sol0, loop0, off = _dswarm(hdsm, prm)
-    sol1, loop1, on = _dswarm(hdsm, prm)
+    sol0, loop0, off = circle_flight(hdsm, prm, *scenario())
+    sol1, loop1, on = circle_flight(hdsm, prm, *scenario())
     assert off.link_stats() == dict(rounds=0, delivered=0, lost=0, max_age=0)
     with pytest.raises(hdsm.HdsmError):
         off.download_seen()                                # nothing was allocated
     on.set_links(np.zeros((3, N_ROB), np.int8), True)
     for r in range(10):
         off.round(), on.round()
-        assert _raw(on).tobytes() == _raw(off).tobytes(), r
+        assert raw(on).tobytes() == raw(off).tobytes(), r
         s = _SeenView(on)
-        assert s.seen.tobytes() == _raw(on).tobytes() and (s.shift == 0).all() and (s.seen_round == r).all(), r
+        assert s.seen.tobytes() == raw(on).tobytes() and (s.shift == 0).all() and (s.seen_round == r).all(), r
         assert (on.download(states=False)[2] == off.download(states=False)[2]).all()
     assert on.link_stats() == dict(rounds=10, delivered=10 * N_ROB, lost=0, max_age=0)
     for x in (off, on, sol0, sol1):
@@ -150,7 +138,7 @@ def flights(hdsm):  # noqa: F811
     fate = _twin_table()
     got = {}
     for key, ta in (("off", None), ("aware", True), ("as-is", False)):
-        sol, loop, dsw = _dswarm(hdsm, prm)
+        sol, loop, dsw = circle_flight(hdsm, prm, *scenario())
         if ta is not None:
             dsw.set_links(fate, ta)
         rounds = []
@@ -222,7 +210,7 @@ def test_two_local_ranks_see_the_same_bytes_and_fly_the_one_rank_flight(hdsm, fl
 
 def test_the_audit_judges_what_was_flown_not_what_was_believed(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
-    sol, loop, dsw = _dswarm(hdsm, prm, audit=True)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario(), audit=True)
     dsw.set_links(_twin_table(), True)
     differs = 0
     for r in range(10):

@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 import loop_cases as lc
+from flight_harness import circle_flight, device_loop, hdsm  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import assert_no_scratch_no_lds
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
 from multi_agent_pkgs_amd.params import agile_params, agile_ref_config
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 
 pytestmark = pytest.mark.gpu
 
@@ -81,19 +82,12 @@ def check_same_flight(ranks, one):
     return h1, worst
 
 
-def _one_rank(hdsm, prm, cfg, starts, goals, setup=None):  # noqa: F811
-    sol, loop = _device_loop(hdsm, prm, cfg, starts.shape[0], starts=starts, goals=goals)
-    if setup is not None:
-        setup(loop.shard, 0)
-    return sol, loop, swarm.DeviceSwarm(loop.shard, sol)
-
-
 def _fly(hdsm, n_rob, world, n_hor=10, streams=None, setup=None, scene=None, devices=None, each_round=None):  # noqa: F811
     """ROUNDS rounds of the sharded flight next to the one-rank flight, checks 1 and 2 after every round. Returns both, open."""
     prm, cfg = _params(n_hor)
     starts, goals = sc.circle_scenario(n_rob, radius=4.0) if scene is None else scene
     ranks = swarm.LocalRanks(prm, cfg, n_rob, world, starts=starts, goals=goals, setup=setup, devices=devices)
-    sol, loop, one = _one_rank(hdsm, prm, cfg, starts, goals, setup)
+    sol, loop, one = circle_flight(hdsm, prm, starts, goals, setup=setup)
     worst = pads = 0
     for rnd in range(ROUNDS):
         ranks.round(streams)
@@ -158,7 +152,7 @@ def test_the_sharded_host_mirror_is_a_second_yardstick(hdsm):  # noqa: F811
 
     ranks, one = _fly(hdsm, n_rob, world, each_round=keep)
     _close(ranks, one)
-    sol, whole = _device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
+    sol, whole = device_loop(hdsm, prm, cfg, n_rob, starts=starts, goals=goals)
     records = []
     for _ in range(ROUNDS):
         whole.step()
@@ -291,7 +285,7 @@ def test_refusals_launch_nothing(hdsm):  # noqa: F811
     prm, cfg = _params()
     starts, goals = sc.circle_scenario(10, radius=4.0)
     ranks = swarm.LocalRanks(prm, cfg, 10, 3, starts=starts, goals=goals)
-    sol, loop, one = _one_rank(hdsm, prm, cfg, starts, goals)
+    sol, loop, one = circle_flight(hdsm, prm, starts, goals)
     d = [x.h.value for x in ranks.dswarms]
     c = ranks.comms
 
@@ -357,7 +351,7 @@ def test_download_raw_on_a_plain_single_rank(hdsm):  # noqa: F811
     zeros; either pointer may be NULL."""
     prm, cfg = _params()
     starts, goals = sc.circle_scenario(3, radius=4.0)
-    sol, loop, one = _one_rank(hdsm, prm, cfg, starts, goals)
+    sol, loop, one = circle_flight(hdsm, prm, starts, goals)
     one.round()
     plans, send = np.full((3, 11, 9), 7.0), np.full((3, 11, 9), 7.0)
     hdsm.call("hdsm_dswarm_download_raw", one.h, plans, send)
@@ -405,16 +399,4 @@ def test_gather_kernel_at_every_alignment(hdsm, src_odd, dst_odd):  # noqa: F811
 
 def test_gather_kernel_uses_no_scratch_and_no_lds(tmp_path):
     """Check 7: k_gather_local as built into the library — private segment 0, no spills, group segment 0."""
-    import os
-
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
-    assert os.path.exists(LIB), "libhdsm.so is not built"
-    desc = _kernel_descriptors(tmp_path)
-    mine = {k: v for k, v in desc.items() if "k_gather_local" in k}
-    assert len(mine) == 1, sorted(mine)
-    lds = _group_segments(tmp_path)
-    for k, v in mine.items():
-        print(k, v, "group_segment_fixed_size", lds[k])
-        assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
-        assert lds[k] == 0, (k, lds[k])
+    assert_no_scratch_no_lds(tmp_path, "k_gather_local")

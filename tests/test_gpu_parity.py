@@ -8,29 +8,19 @@ import numpy as np
 import pytest
 
 import problems
+from enum_cases import enum_cases, enum_snapshot
 from multi_agent_pkgs_amd.params import agile_params, default_params, make_params
+from parity_cases import ARG_KEYS, FORCED_SHAPES, compare
+from wave_cases import _mixed_batch
 
 pytestmark = pytest.mark.gpu
 
-TRAJ_TOL = 1e-7
-OBJ_RTOL = 1e-6
-ARG_KEYS = ("agent_id", "state", "ref", "n_poly", "n_rows", "A", "b", "plans", "has_plan")
 
 
 @pytest.fixture(scope="module")
 def hdsm():
     from multi_agent_pkgs_amd import lib
     return lib
-
-
-def compare(g, o, polys=None):
-    assert (g["status"] == o["status"]).all(), (g["status"].tolist(), o["status"].tolist())
-    ok = o["status"] != 2
-    if ok.any():
-        assert np.abs(g["traj"] - o["traj"])[ok].max() < TRAJ_TOL
-        assert np.abs(g["ctrl"] - o["ctrl"])[ok].max() < TRAJ_TOL * 100  # jerks are O(60)
-        rel = np.abs(g["obj"] - o["obj"])[ok] / np.maximum(1.0, np.abs(o["obj"][ok]))
-        assert rel.max() < OBJ_RTOL
 
 
 CASES = [
@@ -555,7 +545,6 @@ def test_enumerated_miqp_goldens_on_the_device(hdsm):
     admissible assignment resolved (scipy + KKT certificates + LP infeasibility proofs; planes from refmath, not from the
     oracle): the device must return the enumerated optimum. Objective to 1e-6 relative, trajectory to 1e-4 (the tolerance
     BASELINE.json states against the reference solve) where the optimum is unique."""
-    from test_oracle import enum_cases, enum_snapshot
     import refmath as rm
     n = 0
     for k, c in enum_cases():
@@ -579,7 +568,6 @@ def test_subtree_splitting_gives_the_unsplit_answer(hdsm, oracle, depth, monkeyp
     """The split launch forced on (HDSM_SPLIT=1) with a two-node budget: every instance that branches is handed over to
     poly_hor^depth sub-blocks (shared incumbent, merge kernel). Same answers as the one-kernel launch and as the oracle, on
     corridors that force real branching and on the enumerated MIQP goldens (where the optimum is certified independently)."""
-    from test_oracle import enum_cases, enum_snapshot
     prm = agile_params(10, max_rows_static=18)
     plain_sol = hdsm.Solver(prm, 10, 10)
     monkeypatch.setenv("HDSM_SPLIT", "1")
@@ -655,20 +643,11 @@ def test_the_set_up_map_on_the_matrix_cores_gives_the_answers_of_the_per_instanc
         assert (np.abs(mfma["obj"] - o["obj"])[ok] / np.maximum(1.0, np.abs(o["obj"][ok]))).max() < 1e-6
 
 
-# every launch shape, forced by the execution knobs on an ordinary batch: (H, threads_per_instance, environment)
-FORCED_SHAPES = {"replan30_64": (10, 64, {}), "replan30": (10, 256, dict(HDSM_DUO_MIN="0")),
-                 "duo": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="0", HDSM_QUAD_MIN="0")),
-                 "tri": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="1", HDSM_QUAD_MIN="0")),
-                 "quad": (10, 256, dict(HDSM_DUO_MIN="1", HDSM_TRI_MIN="1", HDSM_QUAD_MIN="1")),
-                 "replan48_64": (15, 64, {}), "replan48": (15, 256, dict(HDSM_DUO_MIN="0")), "duo48": (15, 256, dict(HDSM_DUO_MIN="1"))}
-
-
 @pytest.mark.parametrize("shape", list(FORCED_SHAPES))
 def test_every_launch_shape_matches_the_oracle(hdsm, oracle, monkeypatch, shape):
     """Each of the eight k_replan* launch shapes (tests/test_wave_shapes.py: the same batches through their CPU execution) picked on
     purpose for one batch that narrows, turns, is chamfered and has neighbours without a plan — until now only the fuzz reached some
     of them, by chance."""
-    from test_wave_shapes import _mixed_batch
     import staging_cases as sc
     n_hor, threads, env = FORCED_SHAPES[shape]
     prm = make_params(n_hor=n_hor, max_rows_static=18, poly_hor=4, threads_per_instance=threads)

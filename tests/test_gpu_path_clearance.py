@@ -5,10 +5,7 @@ import pytest
 
 import dmp_cases as dc
 import path_cases as pc
-from multi_agent_pkgs_amd import scenarios as sc
-from multi_agent_pkgs_amd.params import agile_params
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
-from test_gpu_path_replanning import _compare
+from flight_harness import _compare, forest_pair, hdsm  # noqa: F401  (hdsm: the module's fixture)
 
 
 def _same(dev, host):
@@ -61,29 +58,12 @@ def test_local_path_dmp_batch_equals_the_host_form(hdsm):  # noqa: F811
     assert (dev[2] == 0).any()
 
 
-def _forest_pair(hdsm, n_rob, period, clearance, seed=21):  # noqa: F811
-    from multi_agent_pkgs_amd import swarm
-    prm = agile_params(10, max_rows_static=18)
-    raw, origin = sc.forest_for_circle(n_rob, seed=seed)
-    world = dc.preprocessed(raw, hdsm.map_preprocess)
-
-    def make():
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
-        assert loop.set_world(world, origin) == 0
-        loop.pmax = 49
-        loop.shard.set_path_clearance(clearance)
-        loop.shard.set_path_period(period)
-        return sol, loop
-
-    return make(), make()
-
-
 @pytest.mark.gpu
 def test_device_loop_in_clearance_mode_follows_the_host_mirror(hdsm):  # noqa: F811
     """48 agents in the pre-processed forest, clearance 1.8, path period 1: k_dmp plans every agent every round, the host mirror
     with the same setting plans the same paths; 30 rounds agree to 1e-7, statuses, paths and path errors equal."""
     from multi_agent_pkgs_amd import swarm
-    (_, host), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1, 1.8)
+    (_, host), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1, lambda raw: dc.preprocessed(raw, hdsm.map_preprocess), clearance=1.8)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     for r in range(30):
         _compare(host, dsw, r)
@@ -101,7 +81,7 @@ def test_device_loop_in_clearance_mode_follows_the_host_mirror(hdsm):  # noqa: F
 @pytest.mark.gpu
 def test_clearance_path_step_timing_is_reported(hdsm):  # noqa: F811
     from multi_agent_pkgs_amd import swarm
-    (_, _), (sol_d, dev_loop) = _forest_pair(hdsm, 64, 1, 1.8)
+    (_, _), (sol_d, dev_loop) = forest_pair(hdsm, 64, 1, lambda raw: dc.preprocessed(raw, hdsm.map_preprocess), clearance=1.8)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     dsw.set_phase_timing(True)
     dsw.round()

@@ -4,10 +4,10 @@ import numpy as np
 import pytest
 
 import path_cases as pc
+from flight_harness import _compare, device_loop, forest_pair, hdsm  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import _kernel_blocks, _kernel_descriptors
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import agile_params
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
-from test_kernel_resources import _kernel_descriptors
 
 
 @pytest.mark.gpu
@@ -41,39 +41,12 @@ def test_local_path_batch_equals_the_host_form(hdsm):  # noqa: F811
     assert all(np.array_equal(x, y) for x, y in zip(bd, bh)) and (bd[2] == 0).any()
 
 
-def _forest_pair(hdsm, n_rob, period, seed=21):  # noqa: F811
-    from multi_agent_pkgs_amd import swarm
-    prm = agile_params(10, max_rows_static=18)
-
-    def make():
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
-        raw, origin = sc.forest_for_circle(n_rob, seed=seed)
-        assert loop.set_world(sc.inflate(raw), origin) == 0
-        loop.pmax = 49
-        loop.shard.set_path_period(period)
-        return sol, loop
-
-    return make(), make()
-
-
-PLAN_TOL = 1e-7   # plans of two flights that plan the same: the solver's staging order is not deterministic
-
-
-def _compare(host, dsw, r):
-    out = host.step()
-    dsw.round()
-    plans, has, status, failed = dsw.download(states=False)
-    assert (has == host.has_plan).all(), r
-    assert (status == out["status"]).all(), (r, status.tolist(), out["status"].tolist())
-    assert np.abs(plans - host.plans_all).max() < PLAN_TOL, (r, float(np.abs(plans - host.plans_all).max()))
-
-
 @pytest.mark.gpu
 def test_device_loop_with_a_path_period_follows_the_host_mirror(hdsm):  # noqa: F811
     """set_path_period(1) in the forest (48 agents): k_path plans every agent every round, the host mirror with the same setting
     plans the same paths; 30 rounds agree to 1e-7 (the solver's staging order is not deterministic), paths bit for bit."""
     from multi_agent_pkgs_amd import swarm
-    (_, host), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    (_, host), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     for r in range(30):
         _compare(host, dsw, r)
@@ -97,7 +70,7 @@ def test_new_goals_in_flight_on_the_device(hdsm, scene):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
 
     def make():  # (in the forest a path ends at the local grid's intermediate goal: it is planned again every round)
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
+        sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob)
         if scene == "forest":
             raw, origin = sc.forest_for_circle(n_rob, seed=6)
             world = sc.inflate(raw)
@@ -134,39 +107,12 @@ def test_new_goals_in_flight_on_the_device(hdsm, scene):  # noqa: F811
 @pytest.mark.gpu
 def test_path_step_timing_is_reported(hdsm):  # noqa: F811
     from multi_agent_pkgs_amd import swarm
-    (_, _), (sol_d, dev_loop) = _forest_pair(hdsm, 64, 1)
+    (_, _), (sol_d, dev_loop) = forest_pair(hdsm, 64, 1)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     dsw.set_phase_timing(True)
     dsw.round()
     assert dsw.last_path_ms() > 0 and dsw.phase_ms()["k_corridor"] > 0
     dsw.close()
-
-
-def _kernel_blocks(tmp_path):
-    """{kernel name: {field: int}} read from the gfx950 code objects of the library with every field of a kernel's metadata entry
-    (test_kernel_resources reads the fields that follow `.name`; the group segment precedes it)."""
-    import os
-    import re
-    import subprocess
-    from test_kernel_resources import LIB, LLVM, MAGIC
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not os.path.exists(LIB) or not all(os.path.exists(t) for t in tools):
-        pytest.skip("libhdsm.so or the ROCm LLVM tools missing")
-    fat = str(tmp_path / "fat.bin")
-    subprocess.check_call([tools[0], "--dump-section", ".hip_fatbin=" + fat, LIB, str(tmp_path / "unused.so")])
-    blob = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-    out = {}
-    for k, st in enumerate(starts):
-        part, co = str(tmp_path / ("b%d.bin" % k)), str(tmp_path / ("d%d.co" % k))
-        open(part, "wb").write(blob[st:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-        subprocess.check_call([tools[1], "--unbundle", "--type=o", "--input=" + part, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([tools[2], "--notes", co], text=True)
-        for block in re.split(r"\n  - \.", notes)[1:]:
-            name = re.search(r"^\s*\.name:\s+(\S+)\s*$", block, re.M)
-            if name:
-                out[name.group(1)] = {m.group(1): int(m.group(2)) for m in re.finditer(r"^\s{4}\.(\w+):\s+(\d+)\s*$", block, re.M)}
-    return out
 
 
 def test_k_path_has_no_scratch_and_fits_two_workgroups_per_cu(tmp_path):

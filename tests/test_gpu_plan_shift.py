@@ -9,8 +9,7 @@ import numpy as np
 import pytest
 
 import shift_cases as sc
-from test_gpu_parity import compare
-from test_gpu_round_overhead import stale_outputs
+from parity_cases import compare, stale_outputs
 
 pytestmark = pytest.mark.gpu
 ARG_KEYS = sc.ARG_KEYS

@@ -11,6 +11,7 @@ import pytest
 
 import problems
 from multi_agent_pkgs_amd.params import agile_params
+from parity_cases import compare, stale_outputs
 
 pytestmark = pytest.mark.gpu
 
@@ -47,13 +48,6 @@ def ring_round(prm, n_rob, absent=()):
 def device_args(sn, dev):
     import torch
     return {k: torch.from_numpy(np.ascontiguousarray(sn[k])).to(dev) for k in ARG_KEYS}
-
-
-def stale_outputs(n, N, P, dev):
-    import torch
-    return dict(traj=torch.full((n, N + 1, 9), np.nan, dtype=torch.float64, device=dev), ctrl=torch.full((n, N, 3), np.nan, dtype=torch.float64, device=dev),
-                used=torch.zeros((n, P), dtype=torch.uint8, device=dev), status=torch.full((n,), -1, dtype=torch.int32, device=dev),
-                obj=torch.full((n,), np.nan, dtype=torch.float64, device=dev))
 
 
 @pytest.mark.parametrize("n", [1, 63, 256, 257, 600])
@@ -103,7 +97,6 @@ def test_prepass_outputs_with_absent_and_non_finite_plans_match_the_oracle(hdsm,
     of the set-up map. H = 10: 18 k-steps per tile, two chunks; H = 15: 25 k-steps, three. hdsm_replan_device against the oracle with
     the tolerances of test_gpu_parity.py. (Written when unconditional plan loads and one-trip tiles were tried: profiles/README.md.)"""
     import torch
-    from test_gpu_parity import compare
     prm = agile_params(n_hor, max_rows_static=18, prefilter_min_agents=1)
     N, P = prm.n_hor, prm.poly_hor
     absent = [k for k in (0, 5, 14, 16, 20, 39) if k < n_rob and n_rob > 1]

@@ -21,10 +21,11 @@ import numpy as np
 import pytest
 
 import script_cases as scs
+from flight_harness import circle_flight, hdsm, raw  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import assert_no_scratch_no_lds
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
 from multi_agent_pkgs_amd.params import agile_params, agile_ref_config
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 
 pytestmark = pytest.mark.gpu
 
@@ -79,23 +80,6 @@ def twin_conditions(seen, blind):
     return dist, sum(int((s["status"][:N_FLY] == 2).sum()) for s in seen)
 
 
-def _dswarm(hdsm, prm, audit=False, groups=None, n_rob=N_ROB):  # noqa: F811
-    starts, goals = scenario()
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), n_rob, starts=starts[:n_rob], goals=goals[:n_rob])
-    if groups is not None:
-        loop.shard.set_groups(groups)
-    if audit:
-        loop.shard.set_audit(True, 1.0)
-    return sol, loop, swarm.DeviceSwarm(loop.shard, sol)
-
-
-def _raw(dsw):
-    N, G = dsw.shard.prm.n_hor, dsw.per * dsw.world_size
-    raw = np.zeros((G, N + 1, 9))
-    swarm.call("hdsm_dswarm_download_raw", dsw.h, raw, None)
-    return raw
-
-
 def _host(hdsm, tracks, prm, predict, q):  # noqa: F811
     return hdsm.script_records(tracks, prm.n_hor, swarm.default_swarm_config().step_plan, prm.dt, predict, q)
 
@@ -120,14 +104,14 @@ def test_the_scripted_slots_are_the_host_records_every_round(hdsm, n_hor, predic
     prm = agile_params(n_hor, max_rows_static=18)
     step_plan = swarm.default_swarm_config().step_plan
     tracks = script_tracks()
-    sol, loop, dsw = _dswarm(hdsm, prm)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario())
     dsw.set_history(ROUNDS)
     assert dsw.script_stats() == dict(rounds=0, n_script=0, launches=0)
     dsw.set_script(tracks, predict)
     for r in range(ROUNDS):
         dsw.round()
         want = _host(hdsm, tracks, prm, predict, r)
-        assert _raw(dsw)[N_FLY:].tobytes() == want.tobytes(), r
+        assert raw(dsw)[N_FLY:].tobytes() == want.tobytes(), r
         plans, has, status, _ = dsw.download(states=False)
         assert (has[N_FLY:] == 1).all() and (status[N_FLY:] == 0).all() and plans[N_FLY:].tobytes() == want.tobytes(), r
     hist, dropped = dsw.history(mirror=False)
@@ -158,7 +142,7 @@ def flights(hdsm):  # noqa: F811
     tracks = script_tracks()
     got = {}
     for key, predict, blind in (("truth", 0, False), ("constant-velocity", 1, False), ("blind", 0, True)):
-        sol, loop, dsw = _dswarm(hdsm, prm, audit=True)
+        sol, loop, dsw = circle_flight(hdsm, prm, *scenario(), audit=True)
         dsw.set_history(ROUNDS)
         dsw.set_script(tracks, predict)
         if blind:
@@ -238,13 +222,13 @@ def test_sight_against_blindness(hdsm, flights):  # noqa: F811
 
 def test_an_agent_drops_out_in_flight(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
-    sol0, loop0, plain = _dswarm(hdsm, prm)
-    sol1, loop1, dsw = _dswarm(hdsm, prm)
+    sol0, loop0, plain = circle_flight(hdsm, prm, *scenario())
+    sol1, loop1, dsw = circle_flight(hdsm, prm, *scenario())
     L = hdsm.load()
     assert L.hdsm_dswarm_set_script(dsw.h, 0, 1, None, 0) == 0 and dsw.script_stats() == dict(rounds=0, n_script=0, launches=0)   # a no-op
     for r in range(5):
         plain.round(), dsw.round()
-        assert _raw(dsw).tobytes() == _raw(plain).tobytes(), r
+        assert raw(dsw).tobytes() == raw(plain).tobytes(), r
     plans, has, status, _ = dsw.download(states=True)
     where = plans[N_FLY:, swarm.default_swarm_config().step_plan, :3].copy()
     assert (has == 1).all() and np.abs(loop1.shard.state()[0][N_FLY:] - where).max() == 0
@@ -261,10 +245,10 @@ def test_an_agent_drops_out_in_flight(hdsm):  # noqa: F811
     moved = 0.0
     for q in range(7):
         plain.round(), dsw.round()
-        raw = _raw(dsw)
-        assert raw[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, q).tobytes(), q
-        assert (raw[N_FLY:, :, :3] == where[:, None, :]).all() and (raw[N_FLY:, :, 3:] == 0).all()
-        moved = max(moved, float(np.abs(raw[:N_FLY] - _raw(plain)[:N_FLY]).max()))
+        buf = raw(dsw)
+        assert buf[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, q).tobytes(), q
+        assert (buf[N_FLY:, :, :3] == where[:, None, :]).all() and (buf[N_FLY:, :, 3:] == 0).all()
+        moved = max(moved, float(np.abs(buf[:N_FLY] - raw(plain)[:N_FLY]).max()))
         assert dsw.script_stats() == dict(rounds=q + 1, n_script=2, launches=q + 1)
         if q == 3:                                         # shrinking is refused and leaves the flight untouched
             with pytest.raises(hdsm.HdsmError) as e:
@@ -279,20 +263,20 @@ def test_an_agent_drops_out_in_flight(hdsm):  # noqa: F811
     planned = dsw.path_stats()["planned"]
     dsw.set_goals(scenario()[1] + [0.5, 0.0, 0.0])
     dsw.round()
-    assert dsw.path_stats()["planned"] - planned == N_FLY and _raw(dsw)[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, 7).tobytes()
+    assert dsw.path_stats()["planned"] - planned == N_FLY and raw(dsw)[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, 7).tobytes()
     dsw.set_script(tracks)                                 # the same n_script: new tracks, tau starts again
     dsw.round()
-    assert dsw.script_stats() == dict(rounds=1, n_script=2, launches=9) and _raw(dsw)[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, 0).tobytes()
+    assert dsw.script_stats() == dict(rounds=1, n_script=2, launches=9) and raw(dsw)[N_FLY:].tobytes() == _host(hdsm, tracks, prm, 0, 0).tobytes()
     for x in (plain, dsw, sol0, sol1):
         x.close()
     # everybody scripted: the rank solves nothing and publishes eight tracks
-    sol, loop, full = _dswarm(hdsm, prm)
+    sol, loop, full = circle_flight(hdsm, prm, *scenario())
     starts, _ = scenario()
     every = sc.stack_tracks(*[sc.line_track(starts[k], HOVER, 1.0 + 0.25 * k) for k in range(N_ROB)])
     full.set_script(every, 1)
     for q in range(3):
         full.round()
-        assert _raw(full).tobytes() == _host(hdsm, every, prm, 1, q).tobytes(), q
+        assert raw(full).tobytes() == _host(hdsm, every, prm, 1, q).tobytes(), q
     _, has, status, failed = full.download(states=False)
     assert (has == 1).all() and (status == 0).all() and failed == 0 and full.script_stats() == dict(rounds=3, n_script=8, launches=3)
     full.close(), sol.close()
@@ -323,13 +307,13 @@ def test_a_mover_of_another_group_is_nobody(hdsm):  # noqa: F811
     """Groups [0,4) [4,8) on one rank, id 7 scripted through the middle of the circle: the agents of [0,4) fly bit for bit what they
     fly in a swarm of seven with groups [0,4) [4,7), and their audit never names 7."""
     prm = agile_params(10, max_rows_static=18)
-    sol8, loop8, with7 = _dswarm(hdsm, prm, audit=True, groups=[0, 4, 8])
-    sol7, loop7, without = _dswarm(hdsm, prm, audit=True, groups=[0, 4, 7], n_rob=7)
+    sol8, loop8, with7 = circle_flight(hdsm, prm, *scenario(), audit=True, groups=[0, 4, 8])
+    sol7, loop7, without = circle_flight(hdsm, prm, *(x[:7] for x in scenario()), audit=True, groups=[0, 4, 7])
     with7.set_script(CHORD[None], 0)
     partners = set()
     for r in range(10):
         with7.round(), without.round()
-        assert _raw(with7)[:4].tobytes() == _raw(without)[:4].tobytes(), r
+        assert raw(with7)[:4].tobytes() == raw(without)[:4].tobytes(), r
         audit = with7.last_audit_round()
         partners |= set(audit["partner"][:4].tolist())
         assert audit["partner"][7] in (4, 5, 6), r          # ... while 7 itself is judged inside its own range
@@ -341,16 +325,4 @@ def test_a_mover_of_another_group_is_nobody(hdsm):  # noqa: F811
 
 
 def test_k_script_uses_no_scratch_and_no_lds(tmp_path):
-    import os
-
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
-    assert os.path.exists(LIB), "libhdsm.so is not built"
-    desc = _kernel_descriptors(tmp_path)
-    mine = {k: v for k, v in desc.items() if "k_script" in k}
-    assert len(mine) == 1, sorted(mine)
-    lds = _group_segments(tmp_path)
-    for k, v in mine.items():
-        assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
-        assert lds[k] == 0, (k, lds[k])
-    print({k: dict(v, group_segment_fixed_size=lds[k]) for k, v in mine.items()})
+    assert_no_scratch_no_lds(tmp_path, "k_script")

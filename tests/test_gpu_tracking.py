@@ -13,13 +13,12 @@ Tolerances: those of tests/test_gpu_links.py (device loop against host mirror): 
 import numpy as np
 import pytest
 
-import corridor_oracle as co
-import loop_cases as lc
 import tracking_cases as tc
+from flight_harness import agent_states, circle_flight, device_loop, hdsm, model, raw  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import assert_no_scratch_no_lds
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
 from multi_agent_pkgs_amd.params import agile_params
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,35 +26,8 @@ N_ROB, RADIUS, PLAN_TOL, ROUNDS = 8, 4.0, 1e-7, 14
 IDS = np.arange(N_ROB, dtype=np.int32)
 
 
-def model():
-    """The proposed model, as it stands: seed 7, wind (0.5, 0, 0), gust (2, 2, 1) m/s^2, jitter (0.01, 0.01, 0.005) m."""
-    return sc.gust_model(7, (0.5, 0.0, 0.0), (2.0, 2.0, 1.0), (0.01, 0.01, 0.005))
-
-
 def scenario():
     return sc.circle_scenario(N_ROB, radius=RADIUS)
-
-
-def _dswarm(hdsm, prm, audit=False):  # noqa: F811
-    starts, goals = scenario()
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=starts, goals=goals)
-    if audit:
-        loop.shard.set_audit(True, 1.0)
-    return sol, loop, swarm.DeviceSwarm(loop.shard, sol)
-
-
-def _raw(dsw):
-    N, G = dsw.shard.prm.n_hor, dsw.per * dsw.world_size
-    raw = np.zeros((G, N + 1, 9))
-    swarm.call("hdsm_dswarm_download_raw", dsw.h, raw, None)
-    return raw
-
-
-def _states(dsw, loop):
-    """state_curr [n][9] of every agent, through a download into the host mirror"""
-    dsw.download(states=True)
-    ag = co.export_agents(loop.shard)[0]
-    return np.array([lc.arr(ag[a].state_curr, 9) for a in range(loop.shard.n_local)])
 
 
 def _start_states():
@@ -66,7 +38,7 @@ def _start_states():
 
 def fly(hdsm, prm, tracking=None, audit=False, rounds=ROUNDS, simulator=None):  # noqa: F811
     """One device flight with the history on; per round the downloaded records, flags, statuses (and the audit's round)."""
-    sol, loop, dsw = _dswarm(hdsm, prm, audit=audit)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario(), audit=audit)
     dsw.set_history(rounds)
     if tracking is not None:
         dsw.set_tracking(tracking)
@@ -74,7 +46,7 @@ def fly(hdsm, prm, tracking=None, audit=False, rounds=ROUNDS, simulator=None):  
     for r in range(rounds):
         dsw.round()
         plans, has, status, _ = dsw.download(states=False)
-        out.append(dict(plans=plans, has=has, status=status, raw=_raw(dsw), audit=dsw.last_audit_round() if audit else None))
+        out.append(dict(plans=plans, has=has, status=status, raw=raw(dsw), audit=dsw.last_audit_round() if audit else None))
         if simulator is not None:
             simulator(dsw, r, plans, has)
     got = dict(rounds=out, hist=dsw.history(mirror=False)[0], records=dsw.track_records(), stats=dsw.track_stats(),
@@ -164,7 +136,7 @@ def test_the_flight_is_its_host_mirror(hdsm, flights):  # noqa: F811
     prm, got = flights
     twins = {}
     for key, m in (("tracked", model()), ("plain", None)):
-        sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
+        sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
         if m is not None:
             loop.shard.set_tracking(m)
         rounds = []
@@ -192,14 +164,14 @@ def test_the_flight_is_its_host_mirror(hdsm, flights):  # noqa: F811
 
 def test_off_is_off(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
-    sol0, loop0, plain = _dswarm(hdsm, prm)
-    sol1, loop1, unset = _dswarm(hdsm, prm)
+    sol0, loop0, plain = circle_flight(hdsm, prm, *scenario())
+    sol1, loop1, unset = circle_flight(hdsm, prm, *scenario())
     plain.set_history(6), unset.set_history(6)
     unset.set_tracking(model())
     unset.set_tracking(None)
     for r in range(6):
         plain.round(), unset.round()
-        assert _raw(plain).tobytes() == _raw(unset).tobytes(), r
+        assert raw(plain).tobytes() == raw(unset).tobytes(), r
     assert plain.history(mirror=False)[0].tobytes() == unset.history(mirror=False)[0].tobytes()
     zero = dict(rounds=0, model_launches=0, external_launches=0)
     assert plain.track_stats() == zero and unset.track_stats() == zero
@@ -240,7 +212,7 @@ def test_a_simulator_drives_the_loop_from_outside(hdsm, flights):  # noqa: F811
             N, G = prm.n_hor, dsw.per * dsw.world_size
             seen["plans"] = torch.as_tensor(_DeviceArray(d_plans, (G, N + 1, 9), "<f8"), device="cuda").cpu().numpy()
             seen["has"] = torch.as_tensor(_DeviceArray(d_has, (G,), "|u1"), device="cuda").cpu().numpy()
-            seen["want"] = (plans, has, _raw(dsw))
+            seen["want"] = (plans, has, raw(dsw))
 
     ext, built = fly(hdsm, prm, None, simulator=simulator), got["tracked"]
     assert ext["hist"].tobytes() == built["hist"].tobytes()
@@ -255,22 +227,22 @@ def test_a_simulator_drives_the_loop_from_outside(hdsm, flights):  # noqa: F811
     assert (e["rounds"] == 0).all() and (e["external"] == ROUNDS).all() and (b["rounds"] == ROUNDS).all() and (b["external"] == 0).all()
     for name in ("dist_sum", "dist_sq_sum", "dist_max", "dvel_max"):
         assert e[name].tobytes() == b[name].tobytes(), name
-    plans, has, raw = seen["want"]
-    assert seen["plans"].tobytes() == raw.tobytes() == plans.tobytes() and seen["has"].tobytes() == has.tobytes()
+    plans, has, buf = seen["want"]
+    assert seen["plans"].tobytes() == buf.tobytes() == plans.tobytes() and seen["has"].tobytes() == has.tobytes()
 
 
 def test_masks_and_rows_that_are_not_finite(hdsm):  # noqa: F811
     import torch
     prm = agile_params(10, max_rows_static=18)
-    sol, loop, dsw = _dswarm(hdsm, prm)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario())
     for _ in range(2):
         dsw.round()
-    before = _states(dsw, loop)
+    before = agent_states(dsw, loop.shard)
     given = before + 0.01 * (1.0 + np.arange(N_ROB * 9).reshape(N_ROB, 9))
     mask = np.zeros(N_ROB, np.uint8)
     mask[[1, 4]] = 1
     dsw.set_states(given, mask)                                               # the host form: exactly the two masked agents
-    after = _states(dsw, loop)
+    after = agent_states(dsw, loop.shard)
     assert after[[1, 4]].tobytes() == given[[1, 4]].tobytes() and np.delete(after, [1, 4], 0).tobytes() == np.delete(before, [1, 4], 0).tobytes()
     want = [tc.Record() for _ in range(N_ROB)]
     for k in (1, 4):
@@ -280,7 +252,7 @@ def test_masks_and_rows_that_are_not_finite(hdsm):  # noqa: F811
     again[2, 7], again[5, 0] = np.nan, np.inf                                 # two rows that are skipped and counted nowhere
     t, tm = torch.from_numpy(again).cuda(), torch.ones(N_ROB, dtype=torch.uint8, device="cuda")
     dsw.set_states(t, tm, stream=torch.cuda.current_stream())                 # the device form, masked: everybody
-    last = _states(dsw, loop)
+    last = agent_states(dsw, loop.shard)
     ok = [k for k in range(N_ROB) if k not in (2, 5)]
     assert last[ok].tobytes() == again[ok].tobytes() and last[[2, 5]].tobytes() == after[[2, 5]].tobytes()
     assert dsw.track_records()["external"].tolist() == [1, 2, 0, 1, 2, 0, 1, 1] and not dsw.track_records()["rounds"].any()
@@ -319,7 +291,7 @@ def test_a_scripted_tail_is_not_disturbed(hdsm):  # noqa: F811
     prm, m = agile_params(10, max_rows_static=18), model()
     step = swarm.default_swarm_config().step_plan
     tracks = sc.stack_tracks(sc.hold_track((20.0, 15.0, 1.5)), np.array([[0.0, 20.8, 12.2, 1.5], [0.7, 19.0, 13.6, 1.5], [1.6, 16.4, 13.2, 1.5]]))
-    sol, loop, dsw = _dswarm(hdsm, prm)
+    sol, loop, dsw = circle_flight(hdsm, prm, *scenario())
     dsw.set_history(8)
     dsw.set_script(tracks, 0)
     dsw.set_tracking(m)
@@ -369,16 +341,4 @@ def test_the_flown_motion_through_the_audit(hdsm, flights):  # noqa: F811
 
 
 def test_k_track_uses_no_scratch_and_no_lds(tmp_path):
-    import os
-
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
-    assert os.path.exists(LIB), "libhdsm.so is not built"
-    desc = _kernel_descriptors(tmp_path)
-    mine = {k: v for k, v in desc.items() if "k_track" in k}
-    assert len(mine) == 1, sorted(mine)
-    lds = _group_segments(tmp_path)
-    for k, v in mine.items():
-        assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0 and v.get("sgpr_spill_count", 0) == 0, (k, v)
-        assert lds[k] == 0, (k, lds[k])
-    print({k: dict(v, group_segment_fixed_size=lds[k]) for k, v in mine.items()})
+    assert_no_scratch_no_lds(tmp_path, "k_track")

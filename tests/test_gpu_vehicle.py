@@ -10,8 +10,6 @@ k_vehicle; include/hdsm_swarm.h). 8 agents on the 4 m circle of tests/test_vehic
   * off is off; a flight taken over and handed back keeps every vehicle's 128 bytes; local ranks; the device pointer; resources.
 
 Tolerances: those of tests/test_gpu_tracking.py (device loop against host mirror): statuses equal, plans 1e-7."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -19,13 +17,13 @@ import corridor_oracle as co
 import loop_cases as lc
 import tracking_cases as tc
 import vehicle_cases as vc
+from flight_harness import MirroredRank, device_loop, hdsm, raw  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import assert_no_scratch_no_lds
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd import swarm
-from multi_agent_pkgs_amd.lib import VEHICLE_STATE, call
+from multi_agent_pkgs_amd.lib import VEHICLE_STATE
 from multi_agent_pkgs_amd.params import agile_params
-from test_gpu_commands import Rank
-from test_gpu_configs import _device_loop, hdsm  # noqa: F401  (the module's fixture and loop builder)
-from test_vehicle import N_ROB, RECORDED, gusty, scenario
+from vehicle_cases import N_ROB, RECORDED, gusty, scenario
 
 pytestmark = pytest.mark.gpu
 
@@ -69,8 +67,8 @@ def test_the_batch_equals_the_host_form_bit_for_bit(hdsm):  # noqa: F811
     assert (flown == -7.0).all()
 
 
-class VRank(Rank):
-    """tests/test_gpu_commands.py's Rank — a device shard with the host mirror that follows it: before a round the mirror takes the device's
+class VRank(MirroredRank):
+    """tests/flight_harness.py's MirroredRank — a device shard with the host mirror that follows it: before a round the mirror takes the device's
     flight (agents, yaw, vehicles), after it the device's solutions, and commits them itself — with a vehicle on both."""
 
     def __init__(self, *a, **kw):
@@ -89,26 +87,8 @@ class VRank(Rank):
         super().before_round()
         self.vs_before = self.dsw.vehicle_states() if self.veh is not None else None
 
-    def after_round(self, tag):
-        n, N, P, fly = self.n, self.prm.n_hor, self.prm.poly_hor, self.n_fly
-        G = self.dsw.per * self.dsw.world_size
-        plans, has, status, failed = np.zeros((G, N + 1, 9)), np.zeros(G, np.uint8), np.zeros(n, np.int32), C.c_int32(0)
-        call("hdsm_dswarm_download", self.dsw.h, self.post.h if n else None, plans, has, status, C.byref(failed))
-        if n == 0:
-            return
-        ag = co.export_agents(self.post)[0]
-        ref_full = np.array([lc.arr(ag[k].traj_ref, co.MAXH + 1, 6)[:N + 1] for k in range(n)])
-        self.mirror.set_reference(ref_full, np.array([ag[k].path_vel for k in range(n)]))
-        traj = np.array([lc.arr(ag[k].traj_curr, co.MAXH + 1, 9)[:N + 1] for k in range(n)])
-        out = dict(traj=traj, ctrl=np.array([lc.arr(ag[k].ctrl_curr, co.MAXH, 3)[:N] for k in range(n)]),
-                   used=np.array([[ag[k].poly_used[j] for j in range(P)] for k in range(n)], np.uint8), status=status)
-        mine, mine_has = self.mirror.commit(out)
-        first = self.mirror.first_id
-        assert mine[:fly].tobytes() == plans[first:first + fly].tobytes() and (mine_has[:fly] == has[first:first + fly]).all(), tag
-        after = co.export_agents(self.mirror)[0]
-        state = np.array([lc.arr(after[k].state_curr, 9) for k in range(n)])
-        dev_state = np.array([lc.arr(ag[k].state_curr, 9) for k in range(n)])
-        assert state[:fly].tobytes() == dev_state[:fly].tobytes(), tag          # state_curr: what the vehicle flew, on both sides
+    def feature_round(self, tag, ref_full, out, after, state):
+        n, fly, first, traj = self.n, self.n_fly, self.mirror.first_id, out["traj"]
         sp, pose = self.dsw.commands()
         m_sp, m_pose, m_yaw = self.mirror.commands()
         assert sp[:fly].tobytes() == m_sp[:fly].tobytes() and pose[:fly].tobytes() == m_pose[:fly].tobytes(), tag
@@ -191,7 +171,7 @@ def test_the_device_loop_is_its_host_mirror(hdsm, flavour, n_hor):  # noqa: F811
 def _fly(hdsm, prm, m, rounds):  # noqa: F811
     """a device flight on its own: per round the plans, flags and statuses"""
     starts, goals = scenario()
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=starts, goals=goals)
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=starts, goals=goals)
     dsw = swarm.DeviceSwarm(loop.shard, sol)
     if m is not None:
         dsw.set_commands(True), dsw.set_vehicle(m)
@@ -211,7 +191,7 @@ def test_the_flight_is_its_host_mirror(hdsm, n_hor):  # noqa: F811
     solver's differences pass through the vehicle's gains into the next round's x_0, so this is where feedback could amplify them."""
     prm, m, rounds = agile_params(n_hor, max_rows_static=18), gusty(), 14
     dev = _fly(hdsm, prm, m, rounds)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
     loop.shard.set_commands(True), loop.shard.set_vehicle(m)
     worst = 0.0
     for r, d in enumerate(dev["rounds"]):
@@ -242,13 +222,6 @@ def test_the_vehicle_leaves_the_vehicle_less_flight(hdsm):  # noqa: F811
     assert not without["records"]["rounds"].any()
 
 
-def _raw(dsw):
-    N, G = dsw.shard.prm.n_hor, dsw.per * dsw.world_size
-    raw = np.zeros((G, N + 1, 9))
-    call("hdsm_dswarm_download_raw", dsw.h, raw, None)
-    return raw.tobytes()
-
-
 def test_off_is_off_and_the_refusals(hdsm):  # noqa: F811
     prm = agile_params(10, max_rows_static=18)
     (sol0, plain), (sol1, unset) = _one_rank(hdsm, prm), _one_rank(hdsm, prm)
@@ -276,7 +249,7 @@ def test_off_is_off_and_the_refusals(hdsm):  # noqa: F811
     plain.set_vehicle(None)                                                         # off on a dswarm that never had one: a no-op
     for r in range(6):
         plain.round(), unset.round()
-        assert _raw(plain) == _raw(unset), r
+        assert raw(plain).tobytes() == raw(unset).tobytes(), r
     assert plain.history(mirror=False)[0].tobytes() == unset.history(mirror=False)[0].tobytes()
     assert plain.vehicle_stats() == zero and unset.vehicle_stats() == zero and refused(plain.vehicle_states_device)
     assert not unset.track_records()["rounds"].any()
@@ -286,7 +259,7 @@ def test_off_is_off_and_the_refusals(hdsm):  # noqa: F811
 
 def test_a_flight_taken_over_and_handed_back_keeps_every_vehicle(hdsm):  # noqa: F811
     prm, m = agile_params(10, max_rows_static=18), gusty(feed=1)
-    sol, loop = _device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
+    sol, loop = device_loop(hdsm, prm, swarm.default_swarm_config(), N_ROB, starts=scenario()[0], goals=scenario()[1])
     loop.shard.set_commands(True), loop.shard.set_vehicle(m)
     for _ in range(3):
         loop.step()
@@ -367,18 +340,7 @@ def test_the_device_pointer(hdsm):  # noqa: F811
 
 
 def test_k_vehicle_uses_no_scratch_and_no_lds(tmp_path):
-    import os
-
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
-    assert os.path.exists(LIB), "libhdsm.so is not built"
-    desc = _kernel_descriptors(tmp_path)
-    mine = {k: v for k, v in desc.items() if "k_vehicle" in k or "k_seat" in k}
-    assert len(mine) == 2 and sum("k_vehicle" in k for k in mine) == 1, sorted(mine)
-    lds = _group_segments(tmp_path)
-    for k, v in mine.items():
-        # (scalar registers parked in the lanes of a vector register are neither: k_vehicle holds a 224-byte setting and parks some of
-        # the pointers of its prologue and epilogue there, none inside the sub-step loop — DESIGN §8)
-        assert v["private_segment_fixed_size"] == 0 and v.get("vgpr_spill_count", 0) == 0, (k, v)
-        assert lds[k] == 0, (k, lds[k])
-    print({k: dict(v, group_segment_fixed_size=lds[k]) for k, v in mine.items()})
+    # (scalar registers parked in the lanes of a vector register are neither: k_vehicle holds a 224-byte setting and parks some of
+    # the pointers of its prologue and epilogue there, none inside the sub-step loop — DESIGN §8)
+    assert_no_scratch_no_lds(tmp_path, "k_vehicle", scalar_spills=True)
+    assert_no_scratch_no_lds(tmp_path, "k_seat", scalar_spills=True)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from multi_agent_pkgs_amd.params import agile_params
-from test_warm_probe import KEYS, REPLAYS, compare, ring, ring_oracle  # noqa: F401  (fixtures: one oracle pass for the module)
+from warm_probe_cases import KEYS, REPLAYS, compare, ring, ring_oracle  # noqa: F401  (fixtures: one oracle pass for the module)
 
 pytestmark = pytest.mark.gpu
 

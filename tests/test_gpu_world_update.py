@@ -4,12 +4,11 @@ invalidation, a takeover after edits, the new kernels' resources, and "off means
 import numpy as np
 import pytest
 
-import test_world_update as wu
+import world_cases as wu
+from flight_harness import PLAN_TOL, _compare, device_loop, forest_pair, hdsm  # noqa: F401  (hdsm: the module's fixture)
+from kernel_elf import LIB, _kernel_descriptors
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import default_map_config
-from test_gpu_configs import hdsm  # noqa: F401  (the module's fixture)
-from test_gpu_path_replanning import PLAN_TOL, _compare, _forest_pair
-from test_kernel_resources import _kernel_descriptors
 
 LOOK = (42 + 5) // 6 + 2 + 1   # wave_map_radius(n_it_decomp = 42) and the voxel of margin: what an invalidation looks at round a seed
 MAP_CFG = dict(voxel_size=0.3, inflation_dist=0.3, potential_dist=1.5, potential_pow=4)
@@ -137,7 +136,7 @@ def test_device_loop_follows_the_host_mirror_across_edits(hdsm):  # noqa: F811
     structures grown in the old world, and this test fails in the first round after the first
     edit, with plans 0.13 apart."""
     from multi_agent_pkgs_amd import swarm
-    (_, host), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    (_, host), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1)
     _, world, origin = _world_of(48)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     assert dsw.world_stats() == {"updates": 0, "voxels": 0, "dropped": 0, "raw_resident": False}
@@ -173,7 +172,7 @@ def test_raw_world_updates_on_the_device(hdsm):  # noqa: F811
     host mirror that is given the processed voxels of W through update_world."""
     import torch
     from multi_agent_pkgs_amd import swarm
-    (_, host), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    (_, host), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1)
     raw, _, origin = _world_of(48)
     cfg = default_map_config(**MAP_CFG)
     full = lambda g: hdsm.map_preprocess(cfg, g[None])[0]
@@ -229,7 +228,7 @@ def test_an_edit_far_from_every_agent_drops_nothing(hdsm):  # noqa: F811
     the local grid's half width plus what an invalidation looks at. No cache entry is dropped and the next rounds' cache counters
     grow exactly as the twin's."""
     from multi_agent_pkgs_amd import swarm
-    (sol_a, loop_a), (sol_b, loop_b) = _forest_pair(hdsm, 48, 1)
+    (sol_a, loop_a), (sol_b, loop_b) = forest_pair(hdsm, 48, 1)
     _, world, origin = _world_of(48)
     a, b = swarm.DeviceSwarm(loop_a.shard, sol_a), swarm.DeviceSwarm(loop_b.shard, sol_b)
     for r in range(10):
@@ -259,7 +258,7 @@ def test_takeover_after_edits(hdsm):  # noqa: F811
     """A dswarm that took edits is downloaded — states, plans, and the device world into its mirror — and created again: the new one
     goes on like the host mirror that was kept in step, for 5 rounds."""
     from multi_agent_pkgs_amd import swarm
-    (_, host), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    (_, host), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1)
     _, world, origin = _world_of(48)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     for r in range(6):
@@ -296,7 +295,7 @@ def test_device_swarm_lifecycle_with_every_option_on(hdsm):  # noqa: F811
     after DSwarm owned its memory by type; with the working sets forgotten before each flight, or with a fresh handle per flight, all
     four rounds agree bit for bit. So each flight starts from the same solver state too: reset_warm_start() before it is created."""
     from multi_agent_pkgs_amd import swarm
-    (_, _), (sol_d, dev_loop) = _forest_pair(hdsm, 48, 1)
+    (_, _), (sol_d, dev_loop) = forest_pair(hdsm, 48, 1)
     raw, _, _ = _world_of(48)
     assert raw.shape == (67, 240, 240) and raw.dtype == np.int8
     cfg = default_map_config(**MAP_CFG)
@@ -339,7 +338,6 @@ def test_world_update_kernels_use_no_scratch(tmp_path):
     starts with, k_box_put, k_cache_invalidate — ask for no private segment and spill no vector register."""
     import os
 
-    from test_kernel_resources import LIB
     assert os.path.exists(LIB), "libhdsm.so is not built"
     desc = _kernel_descriptors(tmp_path)
     for tag in ("15k_region_gather", "16k_region_scatter", "6k_passILi0ELi0ELi0ELb0EE", "9k_box_put", "18k_cache_invalidate"):
@@ -357,8 +355,7 @@ def test_a_flight_without_map_updates_launches_nothing_new(hdsm):  # noqa: F811
     profiles/world_update_off_kernel_stats.csv: none of the new ones.)"""
     from multi_agent_pkgs_amd import swarm
     from multi_agent_pkgs_amd.params import agile_params
-    from test_gpu_configs import _device_loop
-    (_, _), (sol_d, dev_loop) = _forest_pair(hdsm, 16, 0)
+    (_, _), (sol_d, dev_loop) = forest_pair(hdsm, 16, 0)
     dsw = swarm.DeviceSwarm(dev_loop.shard, sol_d)
     for r in range(5):
         dsw.round()
@@ -371,7 +368,7 @@ def test_a_flight_without_map_updates_launches_nothing_new(hdsm):  # noqa: F811
         assert e.value.code == hdsm.HDSM_ERR_BAD_ARG
     assert dsw.world_stats()["updates"] == 0
     dsw.close()
-    sol, loop = _device_loop(hdsm, agile_params(10, max_rows_static=18), swarm.default_swarm_config(), 8)    # free space: no world
+    sol, loop = device_loop(hdsm, agile_params(10, max_rows_static=18), swarm.default_swarm_config(), 8)    # free space: no world
     free = swarm.DeviceSwarm(loop.shard, sol)
     for call in (lambda: free.update_world(one, [0, 0, 0]), lambda: free.set_raw_world(default_map_config(**MAP_CFG), one), free.download_world):
         with pytest.raises(hdsm.HdsmError) as e:

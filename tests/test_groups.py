@@ -114,8 +114,7 @@ def test_touched_and_new_kernels_use_no_scratch(tmp_path):
     LDS in k_group_report."""
     import os
 
-    from test_flight_audit import _group_segments
-    from test_kernel_resources import LIB, _kernel_descriptors
+    from kernel_elf import LIB, _group_segments, _kernel_descriptors
     assert os.path.exists(LIB), "libhdsm.so is not built"
     desc = _kernel_descriptors(tmp_path)
     lds = _group_segments(tmp_path)

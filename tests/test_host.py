@@ -2,23 +2,16 @@
 (corridor / reference / fallback logic of include/hdsm_swarm.h) and its closed loop driven by the oracle."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_headers import ROOT, declared_functions
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd.params import HdsmParams, agile_params
 from refmath import keep_only_free, py_raycast, velocity_limit, window_value   # the statement-by-statement renderings of the reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
-
-
-def declared_functions(header):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(hdsm_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_declared_symbol():

@@ -5,49 +5,11 @@ Round 3 removed every scratch access from the solver kernels (hoisted addresses 
 launch). The kernel descriptors in the library say what the hardware will be asked for (`.private_segment_fixed_size`), so the
 regression is caught here, without a GPU and without recompiling."""
 import os
-import re
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "multi_agent_pkgs_amd", "libhdsm.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-
-
-def _kernel_descriptors(tmp_path):
-    """{kernel name: {field: int}} of every gfx950 code object bundled into the library."""
-    objcopy, bundler, readelf = (os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"))
-    for t in (objcopy, bundler, readelf):
-        if not os.path.exists(t):
-            pytest.skip("ROCm LLVM tools not installed: " + t)
-    fat = str(tmp_path / "fat.bin")
-    subprocess.check_call([objcopy, "--dump-section", ".hip_fatbin=" + fat, LIB, str(tmp_path / "unused.so")])
-    blob = open(fat, "rb").read()
-    starts = [m.start() for m in re.finditer(re.escape(MAGIC), blob)]
-    assert starts, "no offload bundle in .hip_fatbin"
-    out = {}
-    for k, st in enumerate(starts):
-        part = str(tmp_path / ("bundle%d.bin" % k))
-        open(part, "wb").write(blob[st:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-        co = str(tmp_path / ("dev%d.co" % k))
-        subprocess.check_call([bundler, "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([readelf, "--notes", co], text=True)
-        cur = None
-        for ln in notes.splitlines():
-            m = re.match(r"\s*\.(\w+):\s+(\S+)\s*$", ln)
-            if not m:
-                continue
-            if m.group(1) == "name" and m.group(2).startswith("_Z"):
-                cur = out.setdefault(m.group(2), {})
-            elif cur is not None and m.group(1) in ("private_segment_fixed_size", "vgpr_count", "sgpr_spill_count", "vgpr_spill_count",
-                                                    "group_segment_fixed_size"):
-                cur[m.group(1)] = int(m.group(2))
-    return out
-
+from kernel_elf import LIB, _kernel_descriptors
 
 def test_no_solver_kernel_uses_scratch(tmp_path):
     if not os.path.exists(LIB):

@@ -190,7 +190,7 @@ def test_host_mirror_plans_in_clearance_mode():
 def test_clearance_kernels_have_no_scratch_and_fit_the_lds(tmp_path):
     """k_dmp and k_dmp_batch exist in the built library, use no scratch and at most 160 KB of LDS; no new symbol contains k_path
     (test_k_path_has_no_scratch_and_fits_two_workgroups_per_cu holds every *k_path* kernel to 80 KB)."""
-    from test_gpu_path_replanning import _kernel_blocks
+    from kernel_elf import _kernel_blocks
     desc = _kernel_blocks(tmp_path)
     ks = {k: v for k, v in desc.items() if "k_dmp" in k}
     assert any("5k_dmpE" in k for k in ks) and any("11k_dmp_batchE" in k for k in ks), sorted(ks)

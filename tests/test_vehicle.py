@@ -12,14 +12,10 @@ import vehicle_cases as vc
 from multi_agent_pkgs_amd import lib, swarm
 from multi_agent_pkgs_amd import scenarios as sc
 from multi_agent_pkgs_amd.params import Vehicle, VehicleState, agile_params
+from vehicle_cases import N_ROB, RECORDED, gusty, scenario
 
-N_ROB, RADIUS, ROUNDS = 8, 4.0, 14
+ROUNDS = 14
 REST = np.array([1.0, -2.0, 1.5, 0, 0, 0, 0, 0, 0.0])
-
-
-def gusty(**kw):
-    """The vehicle of the mirror flight and of the GPU flights: the defaults in a wind of 0.5 m/s^2 along x with gusts of (2, 2, 1) m/s^2."""
-    return sc.crazyflie_vehicle(seed=7, wind=(0.5, 0.0, 0.0), gust=(2.0, 2.0, 1.0), **kw)
 
 
 def test_the_host_form_against_the_restatement():
@@ -156,10 +152,6 @@ def test_every_argument_refusal_and_the_binding():
     assert C.sizeof(Vehicle) == 224 and C.sizeof(VehicleState) == 128
 
 
-def scenario():
-    return sc.circle_scenario(N_ROB, radius=RADIUS)
-
-
 def _loop(oracle, prm):
     starts, goals = scenario()
 
@@ -204,12 +196,6 @@ def test_the_mirror_refuses_what_cannot_be_flown(oracle):
     shard.set_tracking(sc.gust_model(1))                                        # off is off
     shard.set_tracking(None)
     shard.set_commands(False)
-
-
-# What this flight gave on the CPU with the oracle as the solver, recorded before any GPU run (tests/test_gpu_vehicle.py asserts the
-# first two against what the device flies): how far the flight leaves its vehicle-less copy (the largest difference of a planned
-# position, m), the instances without a solution, and the tracking distance's mean, standard deviation and maximum (m).
-RECORDED = dict(leaves_by=2.569689, unsolved=14, mean=0.047678, std=0.037373, max=0.218544)
 
 
 def test_the_mirror_flies_the_host_form(oracle):

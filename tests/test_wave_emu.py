@@ -8,9 +8,10 @@ import numpy as np
 import pytest
 
 import problems
+from enum_cases import enum_cases, enum_snapshot
 from multi_agent_pkgs_amd.params import agile_params, make_params
+from wave_cases import ARG_KEYS, compare
 
-ARG_KEYS = ("agent_id", "state", "ref", "n_poly", "n_rows", "A", "b", "plans", "has_plan")
 
 
 @pytest.fixture(scope="module")
@@ -18,14 +19,6 @@ def wave():
     from wave_emu import pywave
     pywave.lib()
     return pywave
-
-
-def compare(e, o, tol=1e-8):
-    assert (e["status"] == o["status"]).all(), (e["status"].tolist(), o["status"].tolist())
-    ok = o["status"] != 2
-    if ok.any():
-        assert np.abs(e["traj"] - o["traj"])[ok].max() < tol
-        assert (np.abs(e["obj"] - o["obj"])[ok] / np.maximum(1, np.abs(o["obj"][ok]))).max() < 1e-8
 
 
 CASES = [dict(n_rob=12, seed=1), dict(n_rob=12, seed=2, turn=True), dict(n_rob=12, seed=3, narrow=True, turn=True),
@@ -249,7 +242,6 @@ def test_level1_through_the_device_source(wave, oracle, kw):
 def test_device_source_reproduces_the_enumerated_miqps(wave):
     """tests/golden/miqp_enum.npz (every admissible assignment resolved by scipy + KKT certificates, see test_oracle.py): the
     device source's lazy branch and bound on the same snapshots — NV = 32 with n = 18 (padded factor) and n = 30."""
-    from test_oracle import enum_cases, enum_snapshot
     import refmath as rm
     for k, c in enum_cases():
         prm, polys, args = enum_snapshot(c)

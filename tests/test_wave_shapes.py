@@ -13,11 +13,11 @@ import shutil
 import numpy as np
 import pytest
 
-import problems
 import staging_cases as sc
+from kernel_elf import LIB, _kernel_descriptors
 from multi_agent_pkgs_amd.params import make_params
-from test_kernel_resources import LIB, _kernel_descriptors
-from test_wave_emu import ARG_KEYS, compare
+from parity_cases import FORCED_SHAPES
+from wave_cases import _mixed_batch, compare
 
 
 @pytest.fixture(scope="module")
@@ -69,7 +69,6 @@ def _create_knobs(n_hor, threads=256, env=None, P=4, RS=18, cus=256):
 def test_pick_shape_chooses_the_shape_each_pass_launches(wave):
     """hdsm::pick_shape, the one launch rule of hdsm_api.hip, for (ordinary launch or pass 1, pass 2 of a split launch, rescue):
     on the knobs with which test_gpu_parity.py forces each shape on its batch, on the bench line and on cfg 3 and cfg 5."""
-    from test_gpu_parity import FORCED_SHAPES
     passes = ("ordinary", "items", "rescue")
     forced = {"replan30_64": ("replan30_64", "replan30_64", "replan30_64"), "replan30": ("replan30", "replan30", "replan30"),
               "duo": ("duo", "duo", "replan30"), "tri": ("tri", "duo", "replan30"), "quad": ("quad", "duo", "replan30"),
@@ -107,13 +106,6 @@ def _run(wave, prm, args, shape, order, monkeypatch, yield_atomics=False):
     finally:
         monkeypatch.delenv("WEMU_ORDER")
         monkeypatch.delenv("WEMU_YIELD_ATOMICS", raising=False)
-
-
-def _mixed_batch(prm, n_rob, seed, every):
-    """Instances that narrow, turn, are chamfered, and neighbours without a plan."""
-    sn = problems.swarm_snapshot(prm, n_rob, seed, spacing=1.4, narrow=True, turn=True, chamfer=True, absent_frac=0.25)
-    idx = np.arange(0, n_rob, every)
-    return [sn[k] if k in ("plans", "has_plan") else sn[k][idx] for k in ARG_KEYS]
 
 
 @pytest.mark.parametrize("n_hor,rk4,drag,seed", [(10, False, (0, 0, 0), 310), (12, False, (0, 0, 0), 312), (15, False, (0, 0, 0), 317),

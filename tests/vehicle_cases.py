@@ -15,6 +15,21 @@ from multi_agent_pkgs_amd import scenarios as sc
 
 GZ = -9.81
 G3 = (0.0, 0.0, GZ)
+N_ROB, RADIUS = 8, 4.0
+# What the mirror flight of tests/test_vehicle.py gave on the CPU with the oracle as the solver, recorded before any GPU run
+# (tests/test_gpu_vehicle.py asserts the first two against what the device flies): how far the flight leaves its vehicle-less copy (the
+# largest difference of a planned position, m), the instances without a solution, and the tracking distance's mean, standard deviation
+# and maximum (m).
+RECORDED = dict(leaves_by=2.569689, unsolved=14, mean=0.047678, std=0.037373, max=0.218544)
+
+
+def gusty(**kw):
+    """The vehicle of the mirror flight and of the GPU flights: the defaults in a wind of 0.5 m/s^2 along x with gusts of (2, 2, 1) m/s^2."""
+    return sc.crazyflie_vehicle(seed=7, wind=(0.5, 0.0, 0.0), gust=(2.0, 2.0, 1.0), **kw)
+
+
+def scenario():
+    return sc.circle_scenario(N_ROB, radius=RADIUS)
 
 
 def sincos(x):
