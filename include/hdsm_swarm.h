@@ -755,6 +755,123 @@ int hdsm_dswarm_vehicle_states(void* dswarm, hdsm_vehicle_state* out);
 int hdsm_dswarm_vehicle_states_device(void* dswarm, void** d_states);
 int hdsm_dswarm_vehicle_stats(void* dswarm, int64_t out[5]);
 
+/* ---- missions: waypoints, arrival, stalls, fly to completion (no new ABI minor; discover by symbol) ---------------------------------------
+ * What a flight is for: per agent a list of waypoints visited in order, judged on the device behind the commit. An arrival makes the next
+ * waypoint the agent's goal and marks the agent due for a path at the start of the next round — no host round trip decides either.
+ * Opt-in; one source (csrc/mission_core.h: the order written there IS the definition) for the host form, the host mirror and k_mission,
+ * which agree bit for bit: only + - * /, sqrt and comparisons, contraction off.
+ *   setting    hdsm_mission, one for all agents: n_wp 1..HDSM_MISSION_MAX_WP waypoints per agent in the table; loop 0 = done after the
+ *              last waypoint, 1 = start over and count laps; dwell_rounds >= 1 consecutive rounds inside before an arrival counts;
+ *              stall_rounds >= 0 (0: no stall detection); arrive_radius R > 0 m; arrive_speed V m/s (<= 0: no speed test); stall_eps
+ *              >= 0 m. With it waypoints [n_local][n_wp][3] and count [n_local], 1..n_wp: the waypoints agent k visits.
+ *   record     hdsm_mission_record, 128 bytes per agent: wp the current waypoint index; done; dwell; stalled (now); laps;
+ *              stall_events; since (rounds since progress); arrivals (so far); done_round (-1 until done); last_arrival_round (-1
+ *              before the first); dist (this round's distance to the waypoint, -1 when the state was not finite); best_dist;
+ *              arrive_round[16] (mission round of the latest arrival at each waypoint, -1 before).
+ *              Reset (hdsm_*_set_mission): zeros, the rounds -1, best_dist = DBL_MAX (no distance seen yet: the first round judged
+ *              with a finite state counts as progress).
+ *   a step     per flown agent and round, on state_curr as the round leaves it (after the commit, the tracking model and the vehicle),
+ *              m the mission round (0 = the first round after hdsm_*_set_mission):
+ *                1. done: nothing.
+ *                2. d2 = (dx*dx + dy*dy) + dz*dz to waypoint[wp], d = sqrt(d2), v2 the same sum of the velocity.
+ *                3. finite = d2 - d2 == 0 and v2 - v2 == 0; inside = finite and d2 <= R*R and (V <= 0 or v2 <= V*V).
+ *                4. dist = finite ? d : -1; dwell = inside ? dwell + 1 : 0.
+ *                5. dwell >= dwell_rounds, an arrival: arrive_round[wp] = last_arrival_round = m, ++arrivals, ++wp, dwell = 0; at wp ==
+ *                   count: with loop wp = 0, ++laps, else done = 1, done_round = m. Unless done: the agent's goal becomes waypoint[wp],
+ *                   the agent is due, best_dist = the distance from where it is to the new waypoint, since = 0, stalled = 0.
+ *                6. otherwise progress is finite and d < best_dist - stall_eps: best_dist = d, since = 0, stalled = 0; without progress
+ *                   ++since, and when stall_rounds > 0 and since == stall_rounds: stalled = 1, ++stall_events.
+ *              Scripted agents (the shard's tail) fly no mission: their records stay as the reset left them.
+ *   summary    hdsm_mission_summary of a shard: round (the mission round judged last, -1 before the first), flown agents, done,
+ *              stalled now (and not done), arrivals of that round, arrivals in total, makespan (-1 until every flown agent is done, then the largest
+ *              done_round). Integer sums and maxima: independent of the order of reduction.
+ *   hdsm_mission_step_host    one step of n agents on plain arrays in mission round `round` (>= 0): states [n][9], waypoints
+ *                             [n][n_wp][3], count [n], records [n] in and out -> goals [n][3] and due [n] (written for the agents that
+ *                             arrived and are not done, left alone otherwise), summary (may be NULL). Pure.
+ *                             hdsm_mission_step_batch: the same through k_mission on `device` (host pointers), bit for bit.
+ *                             HDSM_ERR_BAD_ARG before anything is touched: a NULL where a pointer is needed, n < 0, round < 0, n_wp
+ *                             outside 1..16, a count outside 1..n_wp, dwell_rounds < 1, stall_rounds < 0, loop not 0 or 1,
+ *                             arrive_radius not positive and finite, arrive_speed or stall_eps not finite, stall_eps < 0, a waypoint
+ *                             that is not finite, a record's wp outside 0..count - 1 (count itself for a record that is done).
+ *   hdsm_swarm_set_mission    the host mirror: records reset, every agent's goal becomes its waypoint 0 and is due at the next round;
+ *                             hdsm_swarm_commit steps the mission behind the vehicle. NULL: off; goals and records stay.
+ *                             hdsm_swarm_mission_records / _summary: out [n_local] / one summary; an error before the first setting.
+ *                             hdsm_swarm_mission_due: the agents due at the next path step [n_local] and every agent's goal
+ *                             [n_local][3] (either may be NULL).
+ *   hdsm_dswarm_set_mission   the device loop: k_mission, one lane per flown agent, the last launch of entry [5] of the phase timing,
+ *                             behind k_vehicle. It writes an arrived agent's goal into the path step's goal buffer and sets its due
+ *                             flag ON THE DEVICE; while a mission is on the path step is launched over the flown agents and a
+ *                             workgroup whose agent is not flagged returns at once (rounds of the path period plan everybody, as
+ *                             without). A set-up call: it synchronises. Device memory is allocated by the first call with a setting; a
+ *                             flight that never calls it allocates and launches nothing new. NULL: off; goals and records stay, flags
+ *                             still pending go to the host's list. While a mission is on hdsm_dswarm_set_goals returns
+ *                             HDSM_ERR_BAD_ARG, and so does an hdsm_dswarm_set_script that would script more agents (the agents a
+ *                             mission flies are fixed when it is set: script first). hdsm_dswarm_path_stats keeps its meaning:
+ *                             out[2] counts the launches that planned somebody — of the device-sized ones those in which a flag
+ *                             was set, counted on the device.
+ *   hdsm_dswarm_mission_records / _summary   synchronise and copy; an error before the first setting.
+ *   hdsm_dswarm_mission_due   synchronises; the pending due flags [n_local] and the goal buffer [n_local][3] (either may be NULL). It
+ *                             reads the path step, not the mission: unlike the getters above it also answers before the first
+ *                             setting and while the mission is off, with the host's list of due agents.
+ *   hdsm_dswarm_mission_stats out[0] launches of k_mission, out[1] path launches sized on the device, out[2] agents those launches
+ *                             planned, since hdsm_dswarm_create. Synchronises once a mission was on.
+ *   hdsm_dswarm_mission_groups  one record per neighbour group (one for the whole shard without a partition) over the group's local
+ *                             flown agents, by k_mission_fold, one wavefront per group: count, done, stalled, arrivals, laps min and
+ *                             max (0 for an empty group), makespan (the group's; -1 until all its local flown agents are done).
+ *                             Synchronises; launched there and nowhere else.
+ *   hdsm_dswarm_fly           issues up to max_rounds rounds on hip_stream without the caller. After every check_every (>= 1) rounds it
+ *                             copies the summary into pinned memory and waits for that copy alone. It stops when done == flown; with
+ *                             stop_on_stall also when done + stalled == flown: at most check_every - 1 rounds are flown past the end.
+ *                             rounds_flown and last (either may be NULL) take the rounds issued and the last summary polled.
+ *                             HDSM_ERR_BAD_ARG: no mission on, world_size != 1 (ranks would have to agree on stopping), max_rounds < 0,
+ *                             check_every < 1.
+ * hdsm_dswarm_create takes the mirror's setting, waypoints, counts, records, mission round and pending due agents over,
+ * hdsm_dswarm_download(swarm) hands them back with the device's flags merged into the mirror's due agents. */
+#define HDSM_MISSION_MAX_WP 16
+
+typedef struct hdsm_mission {
+  int32_t n_wp, loop, dwell_rounds, stall_rounds;
+  double  arrive_radius, arrive_speed, stall_eps;
+  double  reserved0;                   /* 0; the setting is 48 bytes */
+} hdsm_mission;
+
+typedef struct hdsm_mission_record {
+  int32_t wp, done, dwell, stalled;
+  int32_t laps, stall_events, since, arrivals;
+  int64_t done_round, last_arrival_round;
+  double  dist, best_dist;
+  int32_t arrive_round[HDSM_MISSION_MAX_WP];
+} hdsm_mission_record;                 /* 128 bytes */
+
+typedef struct hdsm_mission_summary {
+  int64_t round;
+  int32_t flown, done, stalled, arrivals;
+  int64_t arrivals_total, makespan;
+} hdsm_mission_summary;                /* 40 bytes */
+
+typedef struct hdsm_mission_group {
+  int32_t first, count, n_local, done;
+  int32_t stalled, laps_min, laps_max, reserved0;
+  int64_t arrivals, makespan;
+} hdsm_mission_group;                  /* 48 bytes */
+
+int hdsm_mission_step_host(const hdsm_mission* m, int32_t n, int64_t round, const double* states, const double* waypoints,
+                           const int32_t* count, hdsm_mission_record* records, double* goals, uint8_t* due, hdsm_mission_summary* summary);
+int hdsm_mission_step_batch(int32_t device, const hdsm_mission* m, int32_t n, int64_t round, const double* states, const double* waypoints,
+                            const int32_t* count, hdsm_mission_record* records, double* goals, uint8_t* due, hdsm_mission_summary* summary);
+int hdsm_swarm_set_mission(void* swarm, const hdsm_mission* m, const double* waypoints, const int32_t* count);
+int hdsm_swarm_mission_records(void* swarm, hdsm_mission_record* out);
+int hdsm_swarm_mission_summary(void* swarm, hdsm_mission_summary* out);
+int hdsm_swarm_mission_due(void* swarm, uint8_t* due, double* goals);
+int hdsm_dswarm_set_mission(void* dswarm, const hdsm_mission* m, const double* waypoints, const int32_t* count);
+int hdsm_dswarm_mission_records(void* dswarm, hdsm_mission_record* out);
+int hdsm_dswarm_mission_summary(void* dswarm, hdsm_mission_summary* out);
+int hdsm_dswarm_mission_due(void* dswarm, uint8_t* due, double* goals);
+int hdsm_dswarm_mission_stats(void* dswarm, int64_t out[3]);
+int hdsm_dswarm_mission_groups(void* dswarm, hdsm_mission_group* out);
+int hdsm_dswarm_fly(void* dswarm, void* hip_stream, int32_t max_rounds, int32_t check_every, int32_t stop_on_stall, int32_t* rounds_flown,
+                    hdsm_mission_summary* last);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

@@ -1,7 +1,7 @@
 // dswarm.h — private host header of the hdsm_dswarm_ entry points: the state of a device-resident shard (DSwarm) and what the files
 // of the loop share and nothing else — swarm_kernels.hip (the round), dswarm_world.hip (map updates in flight), dswarm_audit.hip (audit,
 // history, groups), dswarm_flight.cpp (the flight in and out, goals) and dswarm_models.cpp (link faults, scripted agents, imperfect
-// tracking, commands, the vehicle). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
+// tracking, commands, the vehicle, missions). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "../../include/hdsm_swarm.h"
 #include "audit_device.h"
 #include "device_mem.h"
+#include "mission_core.h"
 #include "swarm_core.h"
 
 namespace hdsm_dswarm __attribute__((visibility("hidden"))) {
@@ -164,6 +165,27 @@ struct Vehicle {
   bool ready() const { return (bool)d_cnt; }
 };
 
+// a mission (hdsm_dswarm_set_mission; nothing is allocated or launched before the first call with a setting): the setting while it is
+// on, the mission round the next k_mission judges, the launches, the table ([n_local][MAX_WP][3] allocated once, n_wp of them in use)
+// and the counts, the record per agent, the due flags k_mission sets and the path step clears, the two tally slots of the summary,
+// the device counters [agents the device-sized path launches planned, the last such launch that planned somebody, how many did], the pinned copy hdsm_dswarm_fly polls and its event
+struct Mission {
+  bool on = false;
+  hdsm_mission m{};
+  long long q = 0, launches = 0, path_launches = 0;
+  DevBuf<double> d_wps;
+  DevBuf<int32_t> d_count;
+  DevBuf<hdsm_mission_record> d_rec;
+  DevBuf<uint8_t> d_flag;
+  DevBuf<hdsm_mission_rule::Tally> d_tally;
+  DevBuf<unsigned long long> d_planned;
+  DevBuf<hdsm_mission_group> d_groups;  // with the partition d_gstart, by the first hdsm_dswarm_mission_groups
+  DevBuf<int32_t> d_gstart;
+  hdsm_mem::PinnedBuf polled;
+  hdsm_mem::DevEvent copied;
+  bool ready() const { return (bool)d_planned; }
+};
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -204,6 +226,7 @@ struct DSwarm {
   DevBuf<int32_t> d_gstart, d_range;
   DevBuf<hdsm_group_report> d_greport;
   Vehicle veh;
+  Mission mission;
 };
 
 inline DSwarm* as_dswarm(void* dswarm) { return static_cast<DSwarm*>(dswarm); }
@@ -227,6 +250,13 @@ int commands_setup(DSwarm* d, bool on, int yaw_idx, double k_p_yaw, const double
 // the device, which is idle). vs [n_local]: the states to start from; NULL: every flown agent is seated on its state_curr and yaw,
 // unless the vehicle is on already.
 int vehicle_setup(DSwarm* d, const hdsm_vehicle& m, long long q, const hdsm_vehicle_state* vs);
+// (dswarm_models.cpp) the mission buffers, allocated by the first call that needs them, and the setting switched on with its table
+// (the caller has set the device, which is idle). rec [n_local] and due [n_local]: the records and pending agents to go on from, with
+// the mission round q; NULL: the records are reset, every flown agent turns to its waypoint 0 and is due.
+int mission_setup(DSwarm* d, const hdsm_mission& m, const double* waypoints, const int32_t* count, long long q, const hdsm_mission_record* rec,
+                  const uint8_t* due);
+// (dswarm_models.cpp) once a mission was set the goals live on the device: the goal buffer into path.goals (the device is idle)
+int mission_pull_goals(DSwarm* d);
 // (swarm_kernels.hip) every event a timed round records
 int timing_events(DSwarm* d);
 // (dswarm_audit.hip) the audit's scratch and (at the first switch-on) the flight record of the shard; `init` [n_local] or empty reports

@@ -78,6 +78,9 @@ int hdsm_dswarm::take_over(DSwarm& d, void* swarm, const int8_t* hworld) {
     if (int rc = commands_setup(&d, true, sw.cmd.yaw_idx, sw.cmd.k_p_yaw, sw.cmd.yaw.data())) return rc;
   if (sw.veh.on)  // the vehicle setting, round and states of the mirror (a vehicle has memory: a flight taken over does not jump)
     if (int rc = vehicle_setup(&d, sw.veh.m, sw.veh.q, sw.veh.state.data())) return rc;
+  if (sw.mission.on)  // the mission setting, table, records and round of the mirror; the agents it had due become the device's flags
+    if (int rc = mission_setup(&d, sw.mission.m, sw.mission.waypoints.data(), sw.mission.count.data(), sw.mission.q, sw.mission.rec.data(), p.due.data()))
+      return rc;
   return HDSM_OK;
 }
 
@@ -92,7 +95,24 @@ int hdsm_dswarm::hand_back(DSwarm& d, void* swarm) {
   int rc = hipMemcpy(tmp.get(), d.d_agents.get(), n * sizeof(AgentS), hipMemcpyDeviceToHost) == hipSuccess
                ? hdsm_swarm_import_state(swarm, tmp.get(), d.n_local)
                : HDSM_ERR_DEVICE;
-  if (rc == HDSM_OK) rc = sw.path.adopt(d.path.period, d.path.round, d.path.due);
+  std::vector<uint8_t> due = d.path.due;
+  if (rc == HDSM_OK && d.mission.on) {  // the device's flags are the agents due; the goals live on the device; the mission goes back whole
+    Mission& ms = d.mission;
+    const size_t W = n * 3 * (size_t)ms.m.n_wp;
+    std::vector<double> wps(W);
+    std::vector<int32_t> count(n);
+    std::vector<hdsm_mission_record> rec(n);
+    if (mission_pull_goals(&d) != HDSM_OK || hipMemcpy(due.data(), ms.d_flag.get(), n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(wps.data(), ms.d_wps.get(), W * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(count.data(), ms.d_count.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(rec.data(), ms.d_rec.get(), n * sizeof(hdsm_mission_record), hipMemcpyDeviceToHost) != hipSuccess)
+      rc = HDSM_ERR_DEVICE;
+    else sw.mission.adopt(ms.m, ms.q, std::move(wps), std::move(count), std::move(rec));
+  } else if (rc == HDSM_OK && sw.mission.on && d.mission.ready()) {
+    sw.mission.on = false;  // (switched off on the device)
+  }
+  for (size_t k = 0; k < n; ++k) due[k] |= d.path.due[k];  // (merged with the host's list, which is empty while a mission is on)
+  if (rc == HDSM_OK) rc = sw.path.adopt(d.path.period, d.path.round, due);
   if (rc == HDSM_OK) sw.adopt_goals(d.path.goals);
   if (rc == HDSM_OK && d.audit.ever) {
     std::vector<hdsm_flight_report> rep(n);
@@ -119,6 +139,7 @@ extern "C" {
 int hdsm_dswarm_set_goals(void* dswarm, const double* goals) {
   DSwarm* d = as_dswarm(dswarm);
   if (!d || (!goals && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  if (d->mission.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_goals: a mission is on (hdsm_dswarm_set_mission): the goals are its waypoints");
   if (d->n_local == 0) return HDSM_OK;
   if (int rc = device_idle(d)) return rc;
   PathStep& p = d->path;
@@ -141,6 +162,11 @@ int hdsm_dswarm_path_stats(void* dswarm, int64_t out[3]) {
   unsigned long long cnt[2] = {0, 0};
   HIP_TRY(hipMemcpy(cnt, d->path.d_cnt.get(), sizeof cnt, hipMemcpyDeviceToHost));
   out[0] = (int64_t)cnt[0], out[1] = (int64_t)cnt[1], out[2] = d->path.launches;
+  if (d->mission.ready()) {  // (the device-sized launches of a mission that planned somebody are counted where that is known: on the device)
+    unsigned long long planned[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpy(planned, d->mission.d_planned.get(), sizeof planned, hipMemcpyDeviceToHost));
+    out[2] += (int64_t)planned[2];
+  }
   return HDSM_OK;
 }
 

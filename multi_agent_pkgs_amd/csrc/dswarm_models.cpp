@@ -1,17 +1,19 @@
 // dswarm_models.cpp — what a caller puts between the plans and the flight of the device-resident loop, set between rounds: link faults
 // (k_deliver, swarm_kernels.hip), scripted agents (k_script, script_kernels.hip), imperfect tracking (k_track, track_kernels.hip), the
-// commands for the vehicle (k_command, command_kernels.hip) and the vehicle itself (k_vehicle, vehicle_kernels.hip), each with its
-// counters and downloads. Semantics in include/hdsm_swarm.h. The only launches from here are k_track's external form
-// (hdsm_dswarm_set_states*, through track_device.h) and k_seat (a vehicle seated at a switch-on or on a state from outside, through
-// vehicle_device.h).
+// commands for the vehicle (k_command, command_kernels.hip), the vehicle itself (k_vehicle, vehicle_kernels.hip) and missions (k_mission,
+// mission_kernels.hip, with hdsm_dswarm_fly), each with its counters and downloads. Semantics in include/hdsm_swarm.h. The only launches
+// from here are k_track's external form (hdsm_dswarm_set_states*, through track_device.h), k_seat (a vehicle seated at a switch-on or
+// on a state from outside, through vehicle_device.h) and k_mission_fold (hdsm_dswarm_mission_groups, through mission_device.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
 #include "command_core.h"
 #include "dswarm.h"
 #include "link_core.h"
+#include "mission_device.h"
 #include "script_device.h"
 #include "track_device.h"
 #include "vehicle_device.h"
@@ -97,7 +99,193 @@ int hdsm_dswarm::vehicle_setup(DSwarm* d, const hdsm_vehicle& m, long long q, co
   return HDSM_OK;
 }
 
+int hdsm_dswarm::mission_pull_goals(DSwarm* d) {
+  if (d->mission.ready() && d->n_local > 0)
+    HIP_TRY(hipMemcpy(d->path.goals.data(), d->path.d_goals.get(), d->path.goals.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm::mission_setup(DSwarm* d, const hdsm_mission& m, const double* waypoints, const int32_t* count, long long q,
+                               const hdsm_mission_record* rec, const uint8_t* due) {
+  using hdsm_mission_rule::Tally;
+  Mission& ms = d->mission;
+  const size_t n = (size_t)d->n_local;
+  const int n_fly = d->n_fly();
+  if (!ms.ready()) {
+    hdsm_mem::FirstError ok;
+    ok(ms.d_wps.alloc(n * hdsm_mission_rule::MAX_WP * 3)), ok(ms.d_count.alloc(n)), ok(ms.d_rec.alloc_zeroed(n)), ok(ms.d_flag.alloc_zeroed(n));
+    ok(ms.d_tally.alloc(2)), ok(ms.polled.ensure(2 * sizeof(Tally))), ok(ms.copied.create(hipEventDisableTiming)), ok(ms.d_planned.alloc_zeroed(3));
+    if (!ok.ok()) {
+      ms.d_planned.reset();
+      return fail(HDSM_ERR_DEVICE, std::string("hdsm_dswarm_set_mission: ") + hipGetErrorString(ok.e));
+    }
+  }
+  ms.on = false;
+  Tally tally[2] = {hdsm_mission_rule::tally_identity(), hdsm_mission_rule::tally_identity()};
+  if (n) {
+    HIP_TRY(hipMemcpy(ms.d_wps.get(), waypoints, n * 3 * (size_t)m.n_wp * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ms.d_count.get(), count, n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(ms.d_flag.get(), 0, n));
+  }
+  if (rec != nullptr) {  // a flight taken over goes on from its records; the tally of the round judged last is theirs
+    if (n) HIP_TRY(hipMemcpy(ms.d_rec.get(), rec, n * sizeof(hdsm_mission_record), hipMemcpyHostToDevice));
+    if (due != nullptr && n_fly > 0) HIP_TRY(hipMemcpy(ms.d_flag.get(), due, (size_t)n_fly, hipMemcpyHostToDevice));
+    if (q > 0)
+      for (int k = 0; k < n_fly; ++k) hdsm_mission_rule::tally_add(tally[(q - 1) & 1], rec[k], rec[k].last_arrival_round == q - 1);
+  } else if (n) {  // a new mission: blank records, every flown agent turns to its waypoint 0 and is flagged for the next round's path step
+    std::vector<hdsm_mission_record> blank(n);
+    for (hdsm_mission_record& r : blank) hdsm_mission_rule::reset(r);
+    HIP_TRY(hipMemcpy(ms.d_rec.get(), blank.data(), n * sizeof(hdsm_mission_record), hipMemcpyHostToDevice));
+    if (int rc = mission_pull_goals(d)) return rc;
+    for (int k = 0; k < n_fly; ++k)
+      for (int c = 0; c < 3; ++c) d->path.goals[3 * (size_t)k + c] = waypoints[(size_t)k * 3 * m.n_wp + c];
+    HIP_TRY(hipMemcpy(d->path.d_goals.get(), d->path.goals.data(), d->path.goals.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (n_fly > 0) HIP_TRY(hipMemset(ms.d_flag.get(), 1, (size_t)n_fly));
+  }
+  HIP_TRY(hipMemcpy(ms.d_tally.get(), tally, sizeof tally, hipMemcpyHostToDevice));
+  HIP_TRY(hipDeviceSynchronize());
+  // who is due is on the device from here on: the host's list is empty while the mission is on
+  std::fill(d->path.due.begin(), d->path.due.end(), (uint8_t)0);
+  d->path.n_due = 0;
+  ms.m = m, ms.q = q, ms.on = true;
+  return HDSM_OK;
+}
+
+namespace {
+
+// the summary of the mission round judged last, from the two tally slots as they stand on the device or in the polled copy
+hdsm_mission_summary mission_summary_of(const DSwarm& d, const hdsm_mission_rule::Tally* tally) {
+  const long long last = d.mission.q - 1;
+  // (before the first round, and on a shard that flies nobody — where k_mission is never launched and nothing resets a slot — the
+  // summary is the identity's: nothing done, makespan -1)
+  const bool judged = last >= 0 && d.n_fly() > 0;
+  return hdsm_mission_rule::summary_of(judged ? tally[last & 1] : hdsm_mission_rule::tally_identity(), last, d.n_fly());
+}
+
+}  // namespace
+
 extern "C" {
+
+// Missions (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_dswarm_set_mission(void* dswarm, const hdsm_mission* m, const double* waypoints, const int32_t* count) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  Mission& ms = d->mission;
+  if (!m) {
+    if (!ms.on) return HDSM_OK;
+    if (int rc = device_idle(d)) return rc;
+    // the goals and the agents still flagged go back to the host's side of the path step
+    if (int rc = mission_pull_goals(d)) return rc;
+    const int n_fly = d->n_fly();
+    if (n_fly > 0) {
+      HIP_TRY(hipMemcpy(d->path.due.data(), ms.d_flag.get(), (size_t)n_fly, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemset(ms.d_flag.get(), 0, (size_t)n_fly));
+    }
+    ms.on = false;
+    return upload_goals_and_due(d);
+  }
+  if (!hdsm_mission_rule::setting_valid(m, d->n_local, waypoints, count))
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_mission: a setting out of its bounds (include/hdsm_swarm.h), a count outside 1..n_wp or a waypoint not finite");
+  if (int rc = device_idle(d)) return rc;
+  return mission_setup(d, *m, waypoints, count, 0, nullptr, nullptr);
+}
+
+int hdsm_dswarm_mission_records(void* dswarm, hdsm_mission_record* out) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || (!out && d->n_local)) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_records: null argument");
+  if (!d->mission.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_records: no hdsm_dswarm_set_mission yet");
+  if (int rc = device_idle(d)) return rc;
+  if (d->n_local) HIP_TRY(hipMemcpy(out, d->mission.d_rec.get(), (size_t)d->n_local * sizeof(hdsm_mission_record), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_mission_summary(void* dswarm, hdsm_mission_summary* out) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_summary: null argument");
+  if (!d->mission.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_summary: no hdsm_dswarm_set_mission yet");
+  if (int rc = device_idle(d)) return rc;
+  hdsm_mission_rule::Tally tally[2];
+  HIP_TRY(hipMemcpy(tally, d->mission.d_tally.get(), sizeof tally, hipMemcpyDeviceToHost));
+  *out = mission_summary_of(*d, tally);
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_mission_due(void* dswarm, uint8_t* due, double* goals) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (int rc = device_idle(d)) return rc;
+  const size_t n = (size_t)d->n_local;
+  if (n == 0) return HDSM_OK;
+  if (due) {
+    if (d->mission.on) HIP_TRY(hipMemcpy(due, d->mission.d_flag.get(), n, hipMemcpyDeviceToHost));
+    else std::copy(d->path.due.begin(), d->path.due.end(), due);
+  }
+  if (goals) HIP_TRY(hipMemcpy(goals, d->path.d_goals.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+int hdsm_dswarm_mission_stats(void* dswarm, int64_t out[3]) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "null argument");
+  out[0] = d->mission.launches, out[1] = d->mission.path_launches, out[2] = 0;
+  if (!d->mission.ready()) return HDSM_OK;
+  if (int rc = device_idle(d)) return rc;
+  unsigned long long planned = 0;
+  HIP_TRY(hipMemcpy(&planned, d->mission.d_planned.get(), sizeof planned, hipMemcpyDeviceToHost));
+  out[2] = (int64_t)planned;
+  return HDSM_OK;
+}
+
+// The mission per group (one record for the whole shard without a partition): k_mission_fold over the records. Launched here and
+// nowhere else: a round never pays for it.
+int hdsm_dswarm_mission_groups(void* dswarm, hdsm_mission_group* out) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d || !out) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_groups: null argument");
+  Mission& ms = d->mission;
+  if (!ms.ready()) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_mission_groups: no hdsm_dswarm_set_mission yet");
+  const int ng = (int)d->group_start.size() - 1;
+  if (int rc = device_idle(d)) return rc;
+  if (!ms.d_gstart) {
+    HIP_TRY(ms.d_groups.alloc((size_t)ng));
+    HIP_TRY(ms.d_gstart.alloc(d->group_start.size()));
+    HIP_TRY(hipMemcpy(ms.d_gstart.get(), d->group_start.data(), d->group_start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hdsm_mission_rule::launch_fold(ng, d->first, d->n_fly(), ms.d_gstart.get(), ms.d_rec.get(), ms.d_groups.get(), nullptr));
+  HIP_TRY(hipMemcpy(out, ms.d_groups.get(), (size_t)ng * sizeof(hdsm_mission_group), hipMemcpyDeviceToHost));
+  return HDSM_OK;
+}
+
+// Rounds without the caller: every check_every rounds the two tally slots are copied into pinned memory on the rounds' stream and the
+// host waits for that copy alone — the event behind it — before it decides whether to go on.
+int hdsm_dswarm_fly(void* dswarm, void* hip_stream, int32_t max_rounds, int32_t check_every, int32_t stop_on_stall, int32_t* rounds_flown,
+                    hdsm_mission_summary* last) {
+  DSwarm* d = as_dswarm(dswarm);
+  if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
+  if (rounds_flown) *rounds_flown = 0;
+  if (d->world != 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_fly: world_size 1 only (ranks would have to agree on stopping)");
+  Mission& ms = d->mission;
+  if (!ms.on) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_fly: no mission is on (hdsm_dswarm_set_mission)");
+  if (max_rounds < 0 || check_every < 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_fly: max_rounds >= 0 and check_every >= 1");
+  HIP_TRY(hipSetDevice(d->device));
+  hipStream_t st = static_cast<hipStream_t>(hip_stream);
+  const hdsm_mission_rule::Tally* const polled = static_cast<const hdsm_mission_rule::Tally*>(ms.polled.get());
+  int32_t rounds = 0;
+  for (;;) {
+    if (rounds % check_every == 0 || rounds == max_rounds) {
+      HIP_TRY(hipMemcpyAsync(ms.polled.get(), ms.d_tally.get(), 2 * sizeof(hdsm_mission_rule::Tally), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipEventRecord(ms.copied.get(), st));
+      HIP_TRY(hipEventSynchronize(ms.copied.get()));
+      const hdsm_mission_summary s = mission_summary_of(*d, polled);
+      if (last) *last = s;
+      if (s.done == s.flown || (stop_on_stall && s.done + s.stalled == s.flown)) break;
+    }
+    if (rounds == max_rounds) break;
+    if (int rc = hdsm_dswarm_round(dswarm, nullptr, hip_stream)) return rc;
+    ++rounds;
+    if (rounds_flown) *rounds_flown = rounds;
+  }
+  return HDSM_OK;
+}
 
 // Link faults (include/hdsm_swarm.h). The call starts a new link history: the view is the plans buffer as it stands (every slot
 // delivered on time, held round -1, shift 0), the counters are zero, link round 0 is the next round.
@@ -175,12 +363,15 @@ int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, cons
   if (!d) return fail(HDSM_ERR_BAD_ARG, "null dswarm");
   Script& s = d->script;
   if (n_script < s.n) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: n_script may stay or grow (a scripted agent has no planner state to resume from)");
+  if (d->mission.on && n_script > s.n)
+    return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: a mission is on (hdsm_dswarm_set_mission): the agents it flies are fixed when it is set");
   if (n_script > d->n_local) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: more scripted agents than the shard has");
   if (predict != 0 && predict != 1) return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: predict is 0 or 1");
   if (!hdsm_script::tracks_valid(n_script, n_knots, knots))
     return fail(HDSM_ERR_BAD_ARG, "hdsm_dswarm_set_script: 1 .. 256 knots per track, every entry finite, times strictly increasing");
   if (n_script == 0) return HDSM_OK;
   if (int rc = device_idle(d)) return rc;
+  if (int rc = mission_pull_goals(d)) return rc;  // (once a mission was set the goals live on the device)
   if (!s.d_knots) HIP_TRY(s.d_knots.alloc((size_t)d->n_local * hdsm_script::MAX_KNOTS * 4));
   HIP_TRY(hipMemcpy(s.d_knots.get(), knots, (size_t)n_script * n_knots * 4 * sizeof(double), hipMemcpyHostToDevice));
   // a scripted agent's goal is its last knot, and it plans no path: the flown agents that are due stay due
@@ -192,6 +383,7 @@ int hdsm_dswarm_set_script(void* dswarm, int32_t n_script, int32_t n_knots, cons
     p.due[(size_t)k] = 0;
   }
   if (int rc = upload_goals_and_due(d)) return rc;
+  if (d->mission.ready()) HIP_TRY(hipMemset(d->mission.d_flag.get() + n_fly, 0, (size_t)n_script));  // (a scripted agent flies no mission)
   s.n = n_script, s.n_knots = n_knots, s.predict = predict, s.round = 0;
   return HDSM_OK;
 }

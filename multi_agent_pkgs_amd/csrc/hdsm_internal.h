@@ -60,6 +60,9 @@ int hdsm_internal_command_args(int32_t n, int32_t n_hor, int32_t step_plan, doub
 int hdsm_internal_vehicle_args(const hdsm_vehicle* m, int32_t n, const int32_t* agent_id, int32_t step_plan, double dt, int64_t round,
                                const double* start, const hdsm_command* setpoint, const double* planned_end, const hdsm_vehicle_state* vstate,
                                const double* flown);
+// (mission_host.cpp) the argument checks shared by hdsm_mission_step_host / _batch
+int hdsm_internal_mission_args(const hdsm_mission* m, int32_t n, int64_t round, const double* states, const double* waypoints, const int32_t* count,
+                               const hdsm_mission_record* records, const double* goals, const uint8_t* due);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

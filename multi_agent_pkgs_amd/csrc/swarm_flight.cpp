@@ -37,6 +37,15 @@ void Vehicle::adopt(bool on_, const hdsm_vehicle& m_, long long q_, std::vector<
   state = std::move(state_);
 }
 
+void Mission::adopt(const hdsm_mission& m_, long long q_, std::vector<double> waypoints_, std::vector<int32_t> count_,
+                    std::vector<hdsm_mission_record> rec_) {
+  on = ever = true, m = m_, q = q_;
+  waypoints = std::move(waypoints_), count = std::move(count_), rec = std::move(rec_);
+  last = hdsm_mission_rule::tally_identity();  // the tally of the round judged last is the records'
+  if (q > 0)
+    for (const hdsm_mission_record& r : rec) hdsm_mission_rule::tally_add(last, r, r.last_arrival_round == q - 1);
+}
+
 extern "C" {
 
 // the plain agent states and the configuration of a shard (hdsm_dswarm_create reads the configuration; the tests read the agents)

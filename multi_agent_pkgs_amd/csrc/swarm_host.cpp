@@ -236,6 +236,7 @@ int hdsm_swarm_commit(void* swarm, const double* traj_out, const double* ctrl_ou
   track_commit(*sw);
   commands_commit(*sw, before, status);
   vehicle_commit(*sw);
+  mission_commit(*sw);
   book_round(*sw);
   return HDSM_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "../../include/hdsm_stats.h"
 #include "../../include/hdsm_swarm.h"
+#include "mission_core.h"
 #include "path_core.h"
 #include "swarm_core.h"
 
@@ -114,6 +115,20 @@ struct Vehicle {
   void adopt(bool on_, const hdsm_vehicle& m_, long long q_, std::vector<hdsm_vehicle_state> state_);
 };
 
+// a mission (mission_core.h; hdsm_swarm_set_mission): the setting while it is on, the mission round the next commit judges, the table
+// [n_local][n_wp][3] with the counts, the record per agent (empty until the first setting) and the last round's tally
+struct Mission {
+  bool on = false, ever = false;
+  hdsm_mission m{};
+  long long q = 0;
+  std::vector<double> waypoints;
+  std::vector<int32_t> count;
+  std::vector<hdsm_mission_record> rec;
+  hdsm_mission_rule::Tally last = hdsm_mission_rule::tally_identity();
+  // (swarm_flight.cpp) the setting, the mission round, the table and the records [n_local] a device loop was left with, switched on
+  void adopt(const hdsm_mission& m_, long long q_, std::vector<double> waypoints_, std::vector<int32_t> count_, std::vector<hdsm_mission_record> rec_);
+};
+
 // timing of the round in flight (f3): the duration of the fused launch as reported by the caller, wall clock at prepare
 struct Round {
   double solve_ms = 0;
@@ -138,6 +153,7 @@ struct Swarm {
   Track track;
   Commands cmd;
   Vehicle veh;
+  Mission mission;
   // the core configuration of an entry point: built once per call and passed down (the test hook is read at every call)
   hdsm_sw::Cfg core_cfg() const {
     hdsm_sw::Cfg c{};
@@ -174,5 +190,8 @@ std::vector<double> commands_before(const Swarm& sw);
 void commands_commit(Swarm& sw, const std::vector<double>& before, const int32_t* status);
 // ... and, behind the commands, the vehicles flying this round's setpoints: state_curr, the track records and the poses take what they flew
 void vehicle_commit(Swarm& sw);
+// ... and, last, the mission judging what was flown: an arrival sets the agent's goal to its next waypoint and marks it in path.due, as a
+// changed goal does
+void mission_commit(Swarm& sw);
 
 }  // namespace hdsm_mirror

@@ -16,6 +16,9 @@
 //   k_vehicle    (only with a vehicle on, hdsm_dswarm_set_vehicle) every flown agent's quadrotor and controller fly those setpoints,
 //                step_plan * n_sub sub-steps; state_curr, the track record and the pose take what it flew (vehicle_kernels.hip)
 //                                                                                                one lane per flown agent
+//   k_mission    (only with a mission on, hdsm_dswarm_set_mission) every flown agent's state judged against its waypoint: arrival, the
+//                next goal and the due flag the next round's path step reads, stalls, the shard's tally (mission_kernels.hip)
+//                                                                                                one lane per flown agent
 //   exchange     ONE RCCL all-gather (hdsm_exchange_device), nothing on a single rank (k_commit publishes straight into the plans
 //                buffer), or — the ranks of one process, hdsm_dswarm_round_ranks — ONE k_gather_local per rank (exchange_kernels.hip)
 // The per-agent functions are the SAME source as the host mirror (swarm_core.h), which is how the two loops are compared in
@@ -37,6 +40,7 @@
 #include "dswarm.h"
 #include "hdsm_internal.h"
 #include "link_core.h"
+#include "mission_device.h"
 #include "path_core.h"
 #include "script_device.h"
 #include "track_device.h"
@@ -514,11 +518,8 @@ __global__ __launch_bounds__(64) void k_commit(Cfg c, int n, int per, AgentS* ag
 // Agent::UpdatePath (AC:261-454) by the rule of path_core.h, ONE WORKGROUP PER DUE AGENT (idx: the due agents, NULL = all n):
 // the BFS as bit planes in LDS (hdsm_path::plan_block), the same points as the host mirror's hdsm_path::plan_serial. goals[k]
 // (hdsm_dswarm_set_goals) becomes the agent's goal first. cnt[0] agents planned, cnt[1] failed.
-__global__ __launch_bounds__(hdsm_path::THREADS) void k_path(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
-                                                              unsigned long long* cnt) {
-  __shared__ hdsm_path::PathLds lds;
-  const int tid = (int)threadIdx.x;
-  const int k = idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x;
+__device__ __forceinline__ void path_agent(const Cfg& c, int k, AgentS* agents, const double* goals, unsigned long long* cnt, hdsm_path::PathLds& lds,
+                                           int tid) {
   AgentS& ag = agents[k];
   const V3 goal = {{goals[3 * (size_t)k], goals[3 * (size_t)k + 1], goals[3 * (size_t)k + 2]}};
   const hdsm_path::PathIn in = hdsm_path::agent_problem(c, ag, goal);
@@ -534,14 +535,37 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_path(Cfg c, const int32_
   if (st == hdsm_path::PATH_OK)
     for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.out[t / 3][t % 3];
 }
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_path(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
+                                                              unsigned long long* cnt) {
+  __shared__ hdsm_path::PathLds lds;
+  path_agent(c, idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x, agents, goals, cnt, lds, (int)threadIdx.x);
+}
+// k_path sized on the device (only while a mission is on, hdsm_dswarm_set_mission): launched over the flown agents; the workgroup of an
+// agent whose due flag (k_mission) is not set returns at once, before it touches LDS — unless `all`, a round of the path period. The
+// flag is cleared when the agent is planned (behind the barrier every thread passes after reading it). planned (or NULL in an `all`
+// round, which the host counts): [0] the agents these launches planned, [1] the number `seq` (> 0) of the last launch that planned
+// somebody, [2] how many launches did — the first workgroup of a launch to plan finds another number in [1] and counts the launch.
+__device__ __forceinline__ void count_planned(unsigned long long* planned, unsigned long long seq) {
+  if (planned == nullptr) return;
+  atomicAdd(&planned[0], 1ull);
+  if (atomicExch(&planned[1], seq) != seq) atomicAdd(&planned[2], 1ull);
+}
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_due_path(Cfg c, int all, uint8_t* flag, AgentS* agents, const double* goals,
+                                                                  unsigned long long* cnt, unsigned long long* planned, unsigned long long seq) {
+  __shared__ hdsm_path::PathLds lds;
+  const int k = (int)blockIdx.x;
+  if (!all && flag[k] == 0) return;
+  path_agent(c, k, agents, goals, cnt, lds, (int)threadIdx.x);
+  if (threadIdx.x == 0) {
+    flag[k] = 0;
+    count_planned(planned, seq);
+  }
+}
 
 // k_path in clearance mode (path_core.h, 6a-7': the distance-map planner and ShortenDMPPath after the descent); rn, rows: the tunnel's
 // mask (hdsm_path::DmpMask). The same bookkeeping as k_path.
-__global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
-                                                             unsigned long long* cnt, int rn, const uint32_t* rows) {
-  __shared__ hdsm_path::DmpLds lds;
-  const int tid = (int)threadIdx.x;
-  const int k = idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x;
+__device__ __forceinline__ void dmp_agent(const Cfg& c, int k, AgentS* agents, const double* goals, unsigned long long* cnt, int rn,
+                                          const uint32_t* rows, hdsm_path::DmpLds& lds, int tid) {
   AgentS& ag = agents[k];
   const V3 goal = {{goals[3 * (size_t)k], goals[3 * (size_t)k + 1], goals[3 * (size_t)k + 2]}};
   const hdsm_path::PathIn in = hdsm_path::agent_problem(c, ag, goal);
@@ -556,6 +580,24 @@ __global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t
   }
   if (st == hdsm_path::PATH_OK)
     for (int t = tid; t < 3 * n; t += hdsm_path::THREADS) ag.path[t / 3][t % 3] = lds.p.out[t / 3][t % 3];
+}
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_dmp(Cfg c, const int32_t* idx, AgentS* agents, const double* goals,
+                                                             unsigned long long* cnt, int rn, const uint32_t* rows) {
+  __shared__ hdsm_path::DmpLds lds;
+  dmp_agent(c, idx != nullptr ? idx[blockIdx.x] : (int)blockIdx.x, agents, goals, cnt, rn, rows, lds, (int)threadIdx.x);
+}
+// k_dmp sized on the device: as k_due_path
+__global__ __launch_bounds__(hdsm_path::THREADS) void k_due_dmp(Cfg c, int all, uint8_t* flag, AgentS* agents, const double* goals,
+                                                                 unsigned long long* cnt, unsigned long long* planned, unsigned long long seq, int rn,
+                                                                 const uint32_t* rows) {
+  __shared__ hdsm_path::DmpLds lds;
+  const int k = (int)blockIdx.x;
+  if (!all && flag[k] == 0) return;
+  dmp_agent(c, k, agents, goals, cnt, rn, rows, lds, (int)threadIdx.x);
+  if (threadIdx.x == 0) {
+    flag[k] = 0;
+    count_planned(planned, seq);
+  }
 }
 
 // One link round (link_core.h, deliver_slot): a wavefront per slot of the plans buffer, four per workgroup. No LDS, no atomics: a
@@ -600,12 +642,34 @@ hipError_t alloc_round_buffers(DSwarm* d, const int8_t* hworld) {
 int path_step(DSwarm& d, hipStream_t st) {
   PathStep& p = d.path;
   const bool all = p.period > 0 && p.round % p.period == 0;
+  p.timed.valid = false;
+  if (Mission& ms = d.mission; ms.on) {
+    // a mission is on: who is due is on the device (k_mission's flags). ONE launch over the flown agents; a workgroup that is not
+    // flagged returns at once. No host round trip decides this.
+    if (const int n_fly = d.n_fly(); n_fly > 0) {
+      if (d.phase_timing) HIP_TRY(p.timed.record_start(st));
+      // hdsm_dswarm_path_stats keeps counting the launches that planned somebody: an `all` round here, a device-sized one on the device
+      unsigned long long* const planned = all ? nullptr : ms.d_planned.get();
+      const unsigned long long seq = (unsigned long long)ms.path_launches + 1ull;
+      if (p.dmp)
+        hipLaunchKernelGGL(k_due_dmp, dim3((unsigned)n_fly), dim3(hdsm_path::THREADS), 0, st, d.c, all ? 1 : 0, ms.d_flag.get(), d.d_agents.get(),
+                           p.d_goals.get(), p.d_cnt.get(), planned, seq, p.dmp_rn, p.d_dmp_rows.get());
+      else
+        hipLaunchKernelGGL(k_due_path, dim3((unsigned)n_fly), dim3(hdsm_path::THREADS), 0, st, d.c, all ? 1 : 0, ms.d_flag.get(), d.d_agents.get(),
+                           p.d_goals.get(), p.d_cnt.get(), planned, seq);
+      HIP_TRY(hipGetLastError());
+      if (d.phase_timing) HIP_TRY(p.timed.record_stop(st));
+      if (all) ++p.launches;
+      else ++ms.path_launches;
+    }
+    ++p.round;
+    return HDSM_OK;
+  }
   int n_plan = all ? d.n_fly() : p.n_due;
   if (!all && d.script.n > 0) {  // (the list of the due agents ascends: the flown ones come first)
     n_plan = 0;
     for (int k = 0; k < d.n_fly(); ++k) n_plan += p.due[(size_t)k] != 0;
   }
-  p.timed.valid = false;
   if (n_plan > 0) {
     if (d.phase_timing) HIP_TRY(p.timed.record_start(st));
     if (p.dmp)
@@ -725,6 +789,16 @@ int commit(DSwarm& d, void* local, hipStream_t st) {
       ++v.launches;
     }
     ++v.q;
+  }
+  if (Mission& ms = d.mission; ms.on) {  // what the flown agents flew is judged against their waypoints (the last launch of phase [5]): an
+    // arrival writes the next goal into the path step's goal buffer and flags the agent for the next round's path step
+    if (n_fly > 0) {
+      HIP_TRY(hdsm_mission_rule::launch(hdsm_mission_rule::Launch{n_fly, 0, ms.q, ms.m, d.d_agents.get(), nullptr, ms.d_wps.get(), ms.d_count.get(),
+                                                                  ms.d_rec.get(), d.path.d_goals.get(), ms.d_flag.get(), ms.d_tally.get()},
+                                        st));
+      ++ms.launches;
+    }
+    ++ms.q;
   }
   if (local) {
     if (int rc = hdsm_internal_local_published(local, st)) return fail(rc, std::string("local ranks: ") + hdsm_last_error());

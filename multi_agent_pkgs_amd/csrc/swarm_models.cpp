@@ -1,5 +1,5 @@
 // swarm_models.cpp — the models the host mirror flies beside the round (include/hdsm_swarm.h): the flight audit, neighbour groups,
-// imperfect tracking, commands for the vehicle and the vehicle in the loop, each with its entry points and its step of
+// imperfect tracking, commands for the vehicle, the vehicle in the loop and missions, each with its entry points and its step of
 // hdsm_swarm_commit. Pure host C++.
 #include <algorithm>
 
@@ -74,7 +74,73 @@ void hdsm_mirror::vehicle_commit(Swarm& sw) {
   ++v.q;
 }
 
+// the mission judges state_curr as the commit, the tracking model and the vehicle left it (mission_core.h); an agent that turns to
+// another waypoint gets it as its goal and plans a path at the start of the next round
+void hdsm_mirror::mission_commit(Swarm& sw) {
+  Mission& ms = sw.mission;
+  if (!ms.on) return;
+  ms.last = hdsm_mission_rule::tally_identity();
+  for (int k = 0; k < sw.n_local; ++k) {
+    AgentS& ag = sw.agents[k];
+    double goal[3];
+    int turn = 0;
+    const int arrived = hdsm_mission_rule::step(ms.m, ms.rec[(size_t)k], ag.state_curr, &ms.waypoints[(size_t)k * 3 * ms.m.n_wp], ms.count[(size_t)k], ms.q,
+                                                goal, &turn);
+    if (turn) ag.goal = V3{{goal[0], goal[1], goal[2]}}, sw.path.due[(size_t)k] = 1;
+    hdsm_mission_rule::tally_add(ms.last, ms.rec[(size_t)k], arrived);
+  }
+  ++ms.q;
+}
+
 extern "C" {
+
+// Missions on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
+int hdsm_swarm_set_mission(void* swarm, const hdsm_mission* m, const double* waypoints, const int32_t* count) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  Mission& ms = sw->mission;
+  if (!m) {
+    ms.on = false;
+    return HDSM_OK;
+  }
+  if (!hdsm_mission_rule::setting_valid(m, sw->n_local, waypoints, count)) return HDSM_ERR_BAD_ARG;
+  const size_t n = (size_t)sw->n_local;
+  ms.m = *m, ms.q = 0, ms.last = hdsm_mission_rule::tally_identity();
+  ms.waypoints.assign(waypoints, waypoints + n * 3 * (size_t)m->n_wp), ms.count.assign(count, count + n);
+  ms.rec.assign(n, hdsm_mission_record{});
+  for (size_t k = 0; k < n; ++k) {
+    AgentS& ag = sw->agents[k];
+    const double* w0 = &ms.waypoints[k * 3 * (size_t)m->n_wp];
+    hdsm_mission_rule::reset(ms.rec[k]);
+    ag.goal = V3{{w0[0], w0[1], w0[2]}}, sw->path.due[k] = 1;
+  }
+  ms.on = ms.ever = true;
+  return HDSM_OK;
+}
+
+int hdsm_swarm_mission_records(void* swarm, hdsm_mission_record* out) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw || !sw->mission.ever || (!out && sw->n_local)) return HDSM_ERR_BAD_ARG;
+  std::copy(sw->mission.rec.begin(), sw->mission.rec.end(), out);
+  return HDSM_OK;
+}
+
+int hdsm_swarm_mission_summary(void* swarm, hdsm_mission_summary* out) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw || !sw->mission.ever || !out) return HDSM_ERR_BAD_ARG;
+  *out = hdsm_mission_rule::summary_of(sw->mission.last, sw->mission.q - 1, sw->n_local);
+  return HDSM_OK;
+}
+
+int hdsm_swarm_mission_due(void* swarm, uint8_t* due, double* goals) {
+  Swarm* sw = as_swarm(swarm);
+  if (!sw) return HDSM_ERR_BAD_ARG;
+  if (due) std::copy(sw->path.due.begin(), sw->path.due.end(), due);
+  if (goals)
+    for (int k = 0; k < sw->n_local; ++k)
+      for (int c = 0; c < 3; ++c) goals[3 * (size_t)k + c] = sw->agents[k].goal[c];
+  return HDSM_OK;
+}
 
 // A vehicle in the loop on the host mirror (include/hdsm_swarm.h). Every refusal comes before anything is touched.
 int hdsm_swarm_set_vehicle(void* swarm, const hdsm_vehicle* m) {

@@ -16,7 +16,8 @@ import re
 
 import numpy as np
 
-from .params import Command, HdsmParams, MapConfig, RefConfig, SwarmConfig, Tracking, TrackRecord, Vehicle, VehicleState
+from .params import (Command, HdsmParams, MapConfig, Mission, MissionSummary, RefConfig, SwarmConfig, Tracking, TrackRecord, Vehicle,
+                     VehicleState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("HDSM_LIBRARY") or os.path.join(_HERE, "libhdsm.so")  # (HDSM_LIBRARY: a development build, e.g. -DCD_PROFILE)
@@ -47,6 +48,13 @@ VEHICLE_STATE = np.dtype([("pos", "<f8", 3), ("vel", "<f8", 3), ("quat", "<f8", 
 VEHICLE = np.dtype([("n_sub", "<i4"), ("feed", "<i4"), ("acc_from", "<i4"), ("pad", "<i4"), ("kp", "<f8", 3), ("kv", "<f8", 3), ("k_att", "<f8", 3),
                     ("tau_rate", "<f8"), ("tau_thrust", "<f8"), ("thrust_min", "<f8"), ("thrust_max", "<f8"), ("rate_max", "<f8", 3),
                     ("drag", "<f8", 3), ("seed", "<u8"), ("wind", "<f8", 3), ("gust", "<f8", 3)])            # hdsm_vehicle
+MISSION_RECORD = np.dtype([("wp", "<i4"), ("done", "<i4"), ("dwell", "<i4"), ("stalled", "<i4"), ("laps", "<i4"), ("stall_events", "<i4"),
+                           ("since", "<i4"), ("arrivals", "<i4"), ("done_round", "<i8"), ("last_arrival_round", "<i8"), ("dist", "<f8"),
+                           ("best_dist", "<f8"), ("arrive_round", "<i4", 16)])                            # hdsm_mission_record
+MISSION_GROUP = np.dtype([("first", "<i4"), ("count", "<i4"), ("n_local", "<i4"), ("done", "<i4"), ("stalled", "<i4"), ("laps_min", "<i4"),
+                          ("laps_max", "<i4"), ("reserved0", "<i4"), ("arrivals", "<i8"), ("makespan", "<i8")])    # hdsm_mission_group
+MISSION_MAX_WP = 16  # HDSM_MISSION_MAX_WP
+assert MISSION_RECORD.itemsize == 128 and MISSION_GROUP.itemsize == 48 and C.sizeof(Mission) == 48 and C.sizeof(MissionSummary) == 40
 assert COMMAND.itemsize == 128 == C.sizeof(Command)
 assert VEHICLE_STATE.itemsize == 128 == C.sizeof(VehicleState) and VEHICLE.itemsize == 224 == C.sizeof(Vehicle)
 assert AUDIT_ROUND.itemsize == 48 and FLIGHT_REPORT.itemsize == 104 and GROUP_REPORT.itemsize == 128
@@ -86,9 +94,11 @@ CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32
                                                   ("uint32_t", np.uint32), ("int64_t", np.int64), ("float", np.float32),
                                                   ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
                                                   ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD), ("hdsm_command", COMMAND),
-                                                  ("hdsm_vehicle_state", VEHICLE_STATE))})
+                                                  ("hdsm_vehicle_state", VEHICLE_STATE), ("hdsm_mission_record", MISSION_RECORD),
+                                                  ("hdsm_mission_group", MISSION_GROUP))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
-                                                  ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking), ("hdsm_vehicle", Vehicle))})
+                                                  ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking), ("hdsm_vehicle", Vehicle),
+                                                  ("hdsm_mission", Mission), ("hdsm_mission_summary", MissionSummary))})
 
 
 def parse_declarations(text):
@@ -129,7 +139,7 @@ EXPORTS = tuple(SIGNATURES)
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
               ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_track_", None),
-              ("hdsm_command_", None), ("hdsm_vehicle_", None),
+              ("hdsm_command_", None), ("hdsm_vehicle_", None), ("hdsm_mission_", None),
               ("hdsm_", "hdsm_last_error"))
 
 _lib = None
@@ -601,6 +611,37 @@ def vehicle_fly(model, ids, start, setpoint, planned_end, vstate, step_plan=1, d
     lead, fn = ((), "hdsm_vehicle_fly_host") if device is None else ((int(device),), "hdsm_vehicle_fly_batch")
     call(fn, *lead, model, n, ids, int(step_plan), float(dt), int(round), start, setpoint, planned_end, vs, flown, dist, pose, stats)
     return vs, flown, dist, pose, tuple(int(x) for x in stats)
+
+
+def mission_table(waypoints, count=None):
+    """(waypoints float64 [n][n_wp][3], count int32 [n]) as the mission entry points take them; count None: every agent visits all."""
+    waypoints = _f64(waypoints)
+    if waypoints.ndim != 3 or waypoints.shape[2] != 3:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "waypoints [n][n_wp][3] expected")
+    count = np.full(waypoints.shape[0], waypoints.shape[1], np.int32) if count is None else _i32(count).reshape(-1)
+    if count.size != waypoints.shape[0]:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "count [n] for waypoints [n][n_wp][3] expected")
+    return waypoints, count
+
+
+def mission_step(setting, records, states, waypoints, count=None, round=0, goals=None, due=None, device=None):
+    """hdsm_mission_step_host: one mission step (csrc/mission_core.h) of n agents in mission round `round` — setting (params.Mission,
+    scenarios.mission_setting), records [n] of lib.MISSION_RECORD (not modified), states [n][9], waypoints [n][n_wp][3], count [n]
+    (None: all), goals [n][3] and due [n] as they stand (None: zeros). Returns (records after the step, goals, due, summary dict): an
+    agent that arrived and is not done has its next waypoint in goals and 1 in due. device given: hdsm_mission_step_batch, the same
+    through k_mission on that device, bit for bit."""
+    rec = np.array(records, dtype=MISSION_RECORD, order="C", copy=True).reshape(-1)
+    n = rec.size
+    waypoints, count = mission_table(waypoints, count)
+    if waypoints.shape[0] != n or waypoints.shape[1] != setting.n_wp:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "mission_step: waypoints [n][setting.n_wp][3] for records [n] expected")
+    states = _f64(states).reshape(n, 9)
+    goals = np.zeros((n, 3)) if goals is None else np.array(goals, dtype=np.float64, order="C", copy=True).reshape(n, 3)
+    due = np.zeros(n, np.uint8) if due is None else np.array(due, dtype=np.uint8, order="C", copy=True).reshape(n)
+    summary = MissionSummary()
+    lead, fn = ((), "hdsm_mission_step_host") if device is None else ((int(device),), "hdsm_mission_step_batch")
+    call(fn, *lead, setting, n, int(round), states, waypoints, count, rec, goals, due, C.byref(summary))
+    return rec, goals, due, summary.as_dict()
 
 
 def command_atan2(y, x):

@@ -178,3 +178,22 @@ class VehicleState(C.Structure):
     commanded. lib.VEHICLE_STATE is the numpy dtype of the same layout."""
     _fields_ = [("pos", C.c_double * 3), ("vel", C.c_double * 3), ("quat", C.c_double * 4), ("omega", C.c_double * 3), ("thrust", C.c_double),
                 ("yaw_cmd", C.c_double), ("reserved0", C.c_double)]
+
+
+class Mission(C.Structure):
+    """hdsm_mission (include/hdsm_swarm.h, "missions"): waypoints per agent in the table (1..16), loop (0 done after the last, 1 start
+    over and count laps), the rounds an agent must stay inside before an arrival counts, the rounds without progress that raise a stall
+    (0: never), the arrival radius (m), the arrival speed (m/s; <= 0: no speed test) and the progress margin (m).
+    scenarios.mission_setting() fills it."""
+    _fields_ = [("n_wp", C.c_int32), ("loop", C.c_int32), ("dwell_rounds", C.c_int32), ("stall_rounds", C.c_int32),
+                ("arrive_radius", C.c_double), ("arrive_speed", C.c_double), ("stall_eps", C.c_double), ("reserved0", C.c_double)]
+
+
+class MissionSummary(C.Structure):
+    """hdsm_mission_summary: the mission round judged last (-1 before the first), flown agents, done, stalled now, arrivals of that
+    round and in total, makespan (-1 until every flown agent is done, then the largest done_round)."""
+    _fields_ = [("round", C.c_int64), ("flown", C.c_int32), ("done", C.c_int32), ("stalled", C.c_int32), ("arrivals", C.c_int32),
+                ("arrivals_total", C.c_int64), ("makespan", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}

@@ -132,6 +132,34 @@ def crazyflie_vehicle(n_sub=10, feed=0, acc_from=0, seed=0, wind=(0.0, 0.0, 0.0)
     return m
 
 
+def mission_setting(n_wp, loop=False, dwell_rounds=2, stall_rounds=0, arrive_radius=0.3, arrive_speed=0.3, stall_eps=0.05):
+    """A setting for SwarmShard.set_mission / DeviceSwarm.set_mission (params.Mission): n_wp waypoints per agent in the table, loop
+    (start over after the last and count laps), dwell_rounds consecutive rounds inside arrive_radius (m) and, if arrive_speed > 0,
+    below that speed (m/s) before an arrival counts; stall_rounds without progress of more than stall_eps (m) raise a stall (0: never).
+    The project's own scenario class (the reference flies one goal per agent)."""
+    from .params import Mission
+    return Mission(int(n_wp), 1 if loop else 0, int(dwell_rounds), int(stall_rounds), float(arrive_radius), float(arrive_speed), float(stall_eps), 0.0)
+
+
+def shuttle_mission(n, length, legs, x0=10.0, y0=10.0, z=1.5):
+    """n agents shuttling on parallel lanes 2 m apart in y: agent k starts at (x0, y0 + 2 k, z) and flies `legs` legs of `length` m
+    along x, to the far end and back in turn. Returns starts [n][3], waypoints [n][legs][3], count [n] (= legs)."""
+    y = y0 + 2.0 * np.arange(n)
+    starts = np.stack([np.full(n, x0), y, np.full(n, z)], axis=1)
+    waypoints = np.repeat(starts[:, None, :], legs, axis=1)
+    waypoints[:, 0::2, 0] += length
+    return starts, waypoints, np.full(n, legs, np.int32)
+
+
+def square_mission(side, legs, x0=10.0, y0=10.0, z=1.5):
+    """Four agents on the corners of a square of `side` m that all move one corner on at a time, `legs` times: agent k starts on
+    corner k (counter-clockwise from (x0, y0)) and its waypoint j is corner (k + j + 1) mod 4. Returns starts [4][3], waypoints
+    [4][legs][3], count [4] (= legs)."""
+    corners = np.array([[x0, y0, z], [x0 + side, y0, z], [x0 + side, y0 + side, z], [x0, y0 + side, z]])
+    waypoints = np.array([[corners[(k + j + 1) % 4] for j in range(legs)] for k in range(4)])
+    return corners.copy(), waypoints, np.full(4, legs, np.int32)
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

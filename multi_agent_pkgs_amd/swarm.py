@@ -15,8 +15,8 @@ import numpy as np
 
 from . import lib as _lib
 from .lib import _f64, _i8, _i32, _stream, _u8, call
-from .params import K_P_YAW, YAW_IDX, HdsmParams, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
-from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario, repeat_scenario  # noqa: F401  (scenario geometry lives in scenarios.py)
+from .params import K_P_YAW, YAW_IDX, HdsmParams, MissionSummary, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
+from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario, repeat_scenario, shuttle_mission, square_mission  # noqa: F401  (scenario geometry lives in scenarios.py)
 
 
 def default_swarm_config():
@@ -238,6 +238,38 @@ class SwarmShard:
         vs = np.zeros(self.n_local, _lib.VEHICLE_STATE)
         call("hdsm_swarm_vehicle_states", self.h, vs)
         return vs
+
+    # ---- missions (include/hdsm_swarm.h) ----
+    def set_mission(self, setting=None, waypoints=None, count=None):
+        """hdsm_swarm_set_mission: setting (params.Mission, scenarios.mission_setting), waypoints [n_local][n_wp][3], count [n_local]
+        (None: every agent visits all). The records are reset, every agent's goal becomes its waypoint 0 and is due at the next round;
+        from then on every commit judges the state flown (lib.mission_step). None: off, goals and records stay. A DeviceSwarm made
+        from this shard takes setting, table, records and mission round over."""
+        if setting is None:
+            call("hdsm_swarm_set_mission", self.h, None, None, None)
+            return
+        waypoints, count = _lib.mission_table(waypoints, count)
+        if waypoints.shape[:2] != (self.n_local, setting.n_wp):
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "set_mission: waypoints [n_local][setting.n_wp][3] expected")
+        call("hdsm_swarm_set_mission", self.h, setting, waypoints, count)
+
+    def mission_records(self):
+        """hdsm_swarm_mission_records: the mission record per local agent (lib.MISSION_RECORD)."""
+        rec = np.zeros(self.n_local, _lib.MISSION_RECORD)
+        call("hdsm_swarm_mission_records", self.h, rec)
+        return rec
+
+    def mission_summary(self):
+        """hdsm_swarm_mission_summary: the shard's summary of the mission round judged last, as a dict (params.MissionSummary)."""
+        s = MissionSummary()
+        call("hdsm_swarm_mission_summary", self.h, C.byref(s))
+        return s.as_dict()
+
+    def mission_due(self):
+        """hdsm_swarm_mission_due: (due uint8 [n_local]: the agents that plan a path at the next round, goals [n_local][3])."""
+        due, goals = np.zeros(self.n_local, np.uint8), np.zeros((self.n_local, 3))
+        call("hdsm_swarm_mission_due", self.h, due, goals)
+        return due, goals
 
     def state(self):
         pos = np.zeros((self.n_local, 3))
@@ -598,6 +630,57 @@ class DeviceSwarm:
         """hdsm_dswarm_vehicle_stats: launches of k_vehicle, agent-rounds flown, vehicles re-seated (an end state that was not finite),
         sub-steps with the thrust clamped, sub-steps with a body rate clamped. Synchronises once a vehicle was on."""
         return dict(zip(("launches", "flown", "reseated", "thrust_clamped", "rate_clamped"), self._counters("hdsm_dswarm_vehicle_stats", 5)))
+
+    # ---- missions (include/hdsm_swarm.h) ----
+    def set_mission(self, setting=None, waypoints=None, count=None):
+        """hdsm_dswarm_set_mission: setting (params.Mission, scenarios.mission_setting), waypoints [n_local][n_wp][3], count [n_local]
+        (None: all). The records are reset, every flown agent's goal becomes its waypoint 0 and is due at the next round; from then
+        on k_mission, the last launch behind k_commit, judges what was flown, writes an arrived agent's next goal and flags it for
+        the next round's path step — on the device. None: off, goals and records stay. While a mission is on set_goals is refused.
+        Synchronises."""
+        if setting is None:
+            call("hdsm_dswarm_set_mission", self.h, None, None, None)
+            return
+        waypoints, count = _lib.mission_table(waypoints, count)
+        if waypoints.shape[:2] != (self.shard.n_local, setting.n_wp):
+            raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "set_mission: waypoints [n_local][setting.n_wp][3] expected")
+        call("hdsm_dswarm_set_mission", self.h, setting, waypoints, count)
+
+    def mission_records(self):
+        """hdsm_dswarm_mission_records: the mission record per local agent (lib.MISSION_RECORD). Synchronises."""
+        rec = np.zeros(self.shard.n_local, _lib.MISSION_RECORD)
+        call("hdsm_dswarm_mission_records", self.h, rec)
+        return rec
+
+    def mission_summary(self):
+        """hdsm_dswarm_mission_summary: the shard's summary of the mission round judged last, as a dict. Synchronises."""
+        s = MissionSummary()
+        call("hdsm_dswarm_mission_summary", self.h, C.byref(s))
+        return s.as_dict()
+
+    def mission_due(self):
+        """hdsm_dswarm_mission_due: (the pending due flags uint8 [n_local], the goal buffer [n_local][3]). Synchronises."""
+        due, goals = np.zeros(self.shard.n_local, np.uint8), np.zeros((self.shard.n_local, 3))
+        call("hdsm_dswarm_mission_due", self.h, due, goals)
+        return due, goals
+
+    def mission_stats(self):
+        """hdsm_dswarm_mission_stats: launches of k_mission, path launches sized on the device, agents those launches planned."""
+        return dict(zip(("launches", "path_launches", "planned"), self._counters("hdsm_dswarm_mission_stats", 3)))
+
+    def mission_groups(self):
+        """hdsm_dswarm_mission_groups: the mission per neighbour group over the group's local flown agents (lib.MISSION_GROUP; one
+        record for the whole shard without a partition). Synchronises."""
+        out = np.zeros(self.n_groups, _lib.MISSION_GROUP)
+        call("hdsm_dswarm_mission_groups", self.h, out)
+        return out
+
+    def fly(self, max_rounds, check_every=4, stop_on_stall=False, stream=None):
+        """hdsm_dswarm_fly: rounds without the caller until every flown agent is done (stop_on_stall: done or stalled), polled every
+        check_every rounds, max_rounds at the most. Returns (rounds flown, the last summary polled as a dict). One rank only."""
+        rounds, last = C.c_int32(0), MissionSummary()
+        call("hdsm_dswarm_fly", self.h, _stream(stream), int(max_rounds), int(check_every), 1 if stop_on_stall else 0, C.byref(rounds), C.byref(last))
+        return rounds.value, last.as_dict()
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
