@@ -872,6 +872,69 @@ int hdsm_dswarm_mission_groups(void* dswarm, hdsm_mission_group* out);
 int hdsm_dswarm_fly(void* dswarm, void* hip_stream, int32_t max_rounds, int32_t check_every, int32_t stop_on_stall, int32_t* rounds_flown,
                     hdsm_mission_summary* last);
 
+/* ---- formations: which agent takes which slot (no new ABI minor; discover by symbol) ---------------------------------------------
+ * An exact linear assignment per neighbour group, minimising the sum of the quantised squared distances between the agents and the
+ * slots they take — for synchronous straight-line motion no two paths of the optimal pairing cross. Opt-in; one source
+ * (csrc/assign_core.h: the order written there IS the definition) for the host form, the host mirror and k_assign, which agree bit for
+ * bit: integers only, apart from the cost.
+ *   problem    one neighbour group group_start[g] .. group_start[g + 1] (the rules of hdsm_swarm_set_groups; n_groups = 0 or NULL: one
+ *              group of all n). Bidders: the group's agents k with active[k] != 0 (active NULL: all), in ascending order; objects: the
+ *              slots at the same indices, so the problem is square, m by m, m <= HDSM_ASSIGN_MAX. An inactive agent gets slot_of[k]
+ *              = -1 and price[k] = 0, and its slot is offered to nobody.
+ *   cost       d2 = (dx*dx + dy*dy) + dz*dz, contraction off; t = d2 * inv_q2 with inv_q2 = 1.0 / (quantum * quantum) formed once on
+ *              the host; c = t >= 2^34 ? 2^34 : (int64)t. A NULL setting stands for the defaults: quantum 0.01 m, max_iters 0.
+ *   auction    forward, Jacobi form, eps-scaling. Benefit a_ij = -c_ij * (m + 1); prices start at 0; eps0 = max(1, cmax * (m + 1) / 2)
+ *              with cmax the group's largest cost (integer division). Phases run while eps > 1 and then once more at eps = 1; between
+ *              phases eps = max(1, eps / 4). A phase starts with everybody unassigned and the prices kept. One iteration, for all
+ *              bidders unassigned at its start, on the prices at its start: j* = argmax_j (a_ij - p_j), ties to the lowest j; w the
+ *              best value over j != j* (m == 1: the best value itself); bid = p_j* + (best - w) + eps. Every object that received bids
+ *              takes the highest, ties to the lowest bidder: its price becomes the bid, its previous owner is unassigned. Because eps
+ *              = 1 < (m + 1) / m in the scaled units the final assignment is exactly optimal for the integer costs, and the final
+ *              prices are a dual solution with 0 <= dual - primal <= m.
+ *   status     per group: 0 optimal; 1 the budget of iterations ran out; 2 an active agent's position is not finite; 3 a bid reached
+ *              2^52. With a status other than 0 the group's active agents get the identity (slot_of[k] = k), the prices are 0 and the
+ *              cost is 0; iters, bids and phases say how far the auction came. m == 0: status 0, no assignment.
+ *   budget     max_iters of the setting, 0 = the default 240 m + 256 (four times the largest count recorded,
+ *              profiles/assign_iterations.json). It bounds the kernel's loop: no input makes it spin.
+ *   stats      per group: first, count (the group's range), active (m), status, phases, iters, bids (bidders summed over the
+ *              iterations), cost (the sum of c over the assignment).
+ *   hdsm_assign_host / hdsm_assign_batch   pos and slots [n][3], active [n] or NULL -> slot_of [n], price [n] indexed by slot (may be
+ *              NULL), stats [max(n_groups, 1)] (may be NULL). The batch form runs k_assign on `device` — one workgroup per group, host
+ *              pointers copied in and out — and agrees with the host form bit for bit. Before anything is touched: HDSM_ERR_BAD_ARG for a
+ *              needed NULL, n < 0, a bad partition, a slot that is not finite, a quantum that is not positive and finite (or whose inverse
+ *              square is not), max_iters < 0; HDSM_ERR_CAPACITY for a group of more than HDSM_ASSIGN_MAX active
+ *              agents.
+ *   hdsm_swarm_assign / hdsm_dswarm_assign   the shard's flown agents (the scripted tail is inactive) in the shard's own neighbour
+ *              groups, positions from state_curr as the last round left it; slots [n_local][3] -> slot_of [n_local], stats [groups]
+ *              (either may be NULL). In the device loop the positions are read on the device: no state is downloaded, only slot_of and
+ *              the stats come back; a set-up call, it synchronises. apply = 1 is exactly hdsm_*_set_goals(g) with g[k] =
+ *              slots[slot_of[k]] for the assigned agents and the current goal for the others, through the same path; like it, it is
+ *              refused with HDSM_ERR_BAD_ARG while a mission is on. apply = 0 is always allowed. world_size != 1: HDSM_ERR_BAD_ARG (a
+ *              group's agents must all be local). Device memory is allocated by the first call; a flight that never calls it allocates
+ *              and launches nothing new, and no round launches it. */
+#define HDSM_ASSIGN_MAX 1024           /* active agents per group */
+
+typedef struct hdsm_assign_setting {
+  double  quantum;
+  int32_t max_iters, reserved0;
+} hdsm_assign_setting;                 /* 16 bytes */
+
+typedef struct hdsm_assign_stats {
+  int32_t first, count, active, status;
+  int32_t phases, reserved0;
+  int64_t iters, bids, cost;
+} hdsm_assign_stats;                   /* 48 bytes */
+
+int hdsm_assign_host(const hdsm_assign_setting* setting, int32_t n, int32_t n_groups, const int32_t* group_start, const double* pos,
+                     const uint8_t* active, const double* slots, int32_t* slot_of, int64_t* price, hdsm_assign_stats* stats);
+int hdsm_assign_batch(int32_t device, const hdsm_assign_setting* setting, int32_t n, int32_t n_groups, const int32_t* group_start,
+                      const double* pos, const uint8_t* active, const double* slots, int32_t* slot_of, int64_t* price,
+                      hdsm_assign_stats* stats);
+int hdsm_swarm_assign(void* swarm, const hdsm_assign_setting* setting, const double* slots, int32_t apply, int32_t* slot_of,
+                      hdsm_assign_stats* stats);
+int hdsm_dswarm_assign(void* dswarm, const hdsm_assign_setting* setting, const double* slots, int32_t apply, int32_t* slot_of,
+                       hdsm_assign_stats* stats);
+
 /* Next row f3 (ROS-free half): every local agent keeps the records of Agent::TrajPlanningIteration — comp_time_sc_ (CPU time of
  * its corridor generation), comp_time_opt_ (the duration of the fused launch, handed in with hdsm_swarm_record_solve_ms between
  * prepare and commit; comp_time_tasc_ = 0 because the planes are generated inside that launch), comp_time_tot_,

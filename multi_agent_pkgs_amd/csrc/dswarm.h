@@ -1,7 +1,7 @@
 // dswarm.h — private host header of the hdsm_dswarm_ entry points: the state of a device-resident shard (DSwarm) and what the files
 // of the loop share and nothing else — swarm_kernels.hip (the round), dswarm_world.hip (map updates in flight), dswarm_audit.hip (audit,
 // history, groups), dswarm_flight.cpp (the flight in and out, goals) and dswarm_models.cpp (link faults, scripted agents, imperfect
-// tracking, commands, the vehicle, missions). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
+// tracking, commands, the vehicle, missions) and dswarm_assign.cpp (formations). They report through ONE error text of their own (hdsm_dswarm_last_error), not through the solver's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -186,6 +186,16 @@ struct Mission {
   bool ready() const { return (bool)d_planned; }
 };
 
+// formations (hdsm_dswarm_assign, dswarm_assign.cpp; nothing is allocated or launched before the first call, and no round launches
+// it): the slots as given, the assignment and the stats per group k_assign writes, the partition (one group without one), the launches
+struct Assign {
+  long long launches = 0;
+  DevBuf<double> d_slots;
+  DevBuf<int32_t> d_slot_of, d_gstart;
+  DevBuf<hdsm_assign_stats> d_stats;
+  bool ready() const { return (bool)d_stats; }
+};
+
 struct DSwarm {
   void* solver = nullptr;
   int device = 0, n_local = 0, n_rob = 0, first = 0, per = 0, world = 1;
@@ -227,6 +237,7 @@ struct DSwarm {
   DevBuf<hdsm_group_report> d_greport;
   Vehicle veh;
   Mission mission;
+  Assign assign;
 };
 
 inline DSwarm* as_dswarm(void* dswarm) { return static_cast<DSwarm*>(dswarm); }

@@ -63,6 +63,11 @@ int hdsm_internal_vehicle_args(const hdsm_vehicle* m, int32_t n, const int32_t* 
 // (mission_host.cpp) the argument checks shared by hdsm_mission_step_host / _batch
 int hdsm_internal_mission_args(const hdsm_mission* m, int32_t n, int64_t round, const double* states, const double* waypoints, const int32_t* count,
                                const hdsm_mission_record* records, const double* goals, const uint8_t* due);
+// (assign_kernels.hip) hdsm_assign_batch with the launch of k_assign repeated reps (>= 1) times on the same inputs, each between two HIP
+// events: ms [reps]. For scripts/gpu_assign_timing.py; the results are the last launch's, which are every launch's.
+int hdsm_internal_assign_batch_timed(int32_t device, const hdsm_assign_setting* setting, int32_t n, int32_t n_groups, const int32_t* group_start,
+                                     const double* pos, const uint8_t* active, const double* slots, int32_t* slot_of, int64_t* price,
+                                     hdsm_assign_stats* stats, int32_t reps, float* ms);
 // (path_host.cpp) the per-case problem (a hdsm_path::PathIn*) of hdsm_local_path_host / _dmp_host
 int hdsm_internal_path_case(int32_t t, const int8_t* world, const int32_t wdim[3], const int32_t ldim[3], const int32_t* off,
                             const int32_t* ground_k, const double* origin, const double* start, const double* goal, double res, void* problem);

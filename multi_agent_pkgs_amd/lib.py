@@ -16,8 +16,8 @@ import re
 
 import numpy as np
 
-from .params import (Command, HdsmParams, MapConfig, Mission, MissionSummary, RefConfig, SwarmConfig, Tracking, TrackRecord, Vehicle,
-                     VehicleState)
+from .params import (AssignSetting, AssignStats, Command, HdsmParams, MapConfig, Mission, MissionSummary, RefConfig, SwarmConfig, Tracking,
+                     TrackRecord, Vehicle, VehicleState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("HDSM_LIBRARY") or os.path.join(_HERE, "libhdsm.so")  # (HDSM_LIBRARY: a development build, e.g. -DCD_PROFILE)
@@ -54,6 +54,10 @@ MISSION_RECORD = np.dtype([("wp", "<i4"), ("done", "<i4"), ("dwell", "<i4"), ("s
 MISSION_GROUP = np.dtype([("first", "<i4"), ("count", "<i4"), ("n_local", "<i4"), ("done", "<i4"), ("stalled", "<i4"), ("laps_min", "<i4"),
                           ("laps_max", "<i4"), ("reserved0", "<i4"), ("arrivals", "<i8"), ("makespan", "<i8")])    # hdsm_mission_group
 MISSION_MAX_WP = 16  # HDSM_MISSION_MAX_WP
+ASSIGN_STATS = np.dtype([("first", "<i4"), ("count", "<i4"), ("active", "<i4"), ("status", "<i4"), ("phases", "<i4"), ("reserved0", "<i4"),
+                         ("iters", "<i8"), ("bids", "<i8"), ("cost", "<i8")])                              # hdsm_assign_stats
+ASSIGN_MAX = 1024  # HDSM_ASSIGN_MAX
+assert ASSIGN_STATS.itemsize == 48 == C.sizeof(AssignStats) and C.sizeof(AssignSetting) == 16
 assert MISSION_RECORD.itemsize == 128 and MISSION_GROUP.itemsize == 48 and C.sizeof(Mission) == 48 and C.sizeof(MissionSummary) == 40
 assert COMMAND.itemsize == 128 == C.sizeof(Command)
 assert VEHICLE_STATE.itemsize == 128 == C.sizeof(VehicleState) and VEHICLE.itemsize == 224 == C.sizeof(Vehicle)
@@ -95,10 +99,11 @@ CTYPES.update({t + "*": ArrayPtr(d) for t, d in (("double", np.float64), ("int32
                                                   ("hdsm_audit_round", AUDIT_ROUND), ("hdsm_flight_report", FLIGHT_REPORT),
                                                   ("hdsm_group_report", GROUP_REPORT), ("hdsm_track_record", TRACK_RECORD), ("hdsm_command", COMMAND),
                                                   ("hdsm_vehicle_state", VEHICLE_STATE), ("hdsm_mission_record", MISSION_RECORD),
-                                                  ("hdsm_mission_group", MISSION_GROUP))})
+                                                  ("hdsm_mission_group", MISSION_GROUP), ("hdsm_assign_stats", ASSIGN_STATS))})
 CTYPES.update({t + "*": C.POINTER(s) for t, s in (("hdsm_params", HdsmParams), ("hdsm_ref_config", RefConfig), ("hdsm_map_config", MapConfig),
                                                   ("hdsm_swarm_config", SwarmConfig), ("hdsm_tracking", Tracking), ("hdsm_vehicle", Vehicle),
-                                                  ("hdsm_mission", Mission), ("hdsm_mission_summary", MissionSummary))})
+                                                  ("hdsm_mission", Mission), ("hdsm_mission_summary", MissionSummary),
+                                                  ("hdsm_assign_setting", AssignSetting))})
 
 
 def parse_declarations(text):
@@ -139,7 +144,7 @@ EXPORTS = tuple(SIGNATURES)
 ERROR_TEXT = (("hdsm_dswarm_upload_plans", None), ("hdsm_dswarm_", "hdsm_dswarm_last_error"), ("hdsm_map_", "hdsm_map_last_error"),
               ("hdsm_poly_octa3d_batch", "hdsm_corridor_last_error"), ("hdsm_poly_octa3d", None), ("hdsm_swarm_", None),
               ("hdsm_local_path_", None), ("hdsm_flight_audit_", None), ("hdsm_link_", None), ("hdsm_script_", None), ("hdsm_track_", None),
-              ("hdsm_command_", None), ("hdsm_vehicle_", None), ("hdsm_mission_", None),
+              ("hdsm_command_", None), ("hdsm_vehicle_", None), ("hdsm_mission_", None), ("hdsm_assign_", None),
               ("hdsm_", "hdsm_last_error"))
 
 _lib = None
@@ -642,6 +647,31 @@ def mission_step(setting, records, states, waypoints, count=None, round=0, goals
     lead, fn = ((), "hdsm_mission_step_host") if device is None else ((int(device),), "hdsm_mission_step_batch")
     call(fn, *lead, setting, n, int(round), states, waypoints, count, rec, goals, due, C.byref(summary))
     return rec, goals, due, summary.as_dict()
+
+
+def assign_groups(groups, n):
+    """(n_groups, group_start int32 or None) as the assignment entry points take a partition: None (or fewer than two entries) is one
+    group of all n."""
+    gs = _i32([] if groups is None else groups).reshape(-1)
+    return (0, None) if gs.size < 2 else (gs.size - 1, gs)
+
+
+def assign(pos, slots, groups=None, active=None, setting=None, device=None):
+    """hdsm_assign_host: which agent takes which slot (csrc/assign_core.h) — per neighbour group (groups: group_start [n_groups + 1],
+    None one group) the exact minimum of the summed quantised squared distances between the active agents (active [n], None: all) at
+    pos [n][3] and the slots [n][3] at the same indices, by the integer auction. setting: params.AssignSetting (None: quantum 0.01 m,
+    the default budget). Returns (slot_of int32 [n], -1 for an inactive agent; price int64 [n] by slot, the dual solution; stats, one
+    lib.ASSIGN_STATS record per group). device given: hdsm_assign_batch, the same through k_assign on that device, bit for bit."""
+    pos, slots = _f64(pos).reshape(-1, 3), _f64(slots).reshape(-1, 3)
+    n = pos.shape[0]
+    if slots.shape[0] != n:
+        raise HdsmError(HDSM_ERR_BAD_ARG, "assign: slots [n][3] for pos [n][3] expected")
+    ng, gs = assign_groups(groups, n)
+    active = None if active is None else _u8(active).reshape(n)
+    slot_of, price, stats = np.full(n, -1, np.int32), np.zeros(n, np.int64), np.zeros(max(ng, 1), ASSIGN_STATS)
+    lead, fn = ((), "hdsm_assign_host") if device is None else ((int(device),), "hdsm_assign_batch")
+    call(fn, *lead, setting, n, ng, gs, pos, active, slots, slot_of, price, stats)
+    return slot_of, price, stats
 
 
 def command_atan2(y, x):

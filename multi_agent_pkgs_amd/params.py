@@ -197,3 +197,23 @@ class MissionSummary(C.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class AssignSetting(C.Structure):
+    """hdsm_assign_setting (include/hdsm_swarm.h, "formations"): the quantum of the cost (m; squared distances are counted in
+    quantum^2 and truncated) and the budget of auction iterations per group (0: the default, 240 m + 256)."""
+    _fields_ = [("quantum", C.c_double), ("max_iters", C.c_int32), ("reserved0", C.c_int32)]
+
+    def __init__(self, quantum=0.01, max_iters=0):
+        super().__init__(float(quantum), int(max_iters), 0)
+
+
+class AssignStats(C.Structure):
+    """hdsm_assign_stats, one per neighbour group: the group's range (first, count), its active agents m, status (0 optimal, 1 budget
+    ran out, 2 a position not finite, 3 a bid reached 2^52), phases, iterations, bids (bidders summed over the iterations) and the
+    cost of the assignment in quanta squared."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("active", C.c_int32), ("status", C.c_int32), ("phases", C.c_int32),
+                ("reserved0", C.c_int32), ("iters", C.c_int64), ("bids", C.c_int64), ("cost", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}

@@ -160,6 +160,33 @@ def square_mission(side, legs, x0=10.0, y0=10.0, z=1.5):
     return corners.copy(), waypoints, np.full(4, legs, np.int32)
 
 
+def line_formation(n, pitch=2.0, origin=(10.0, 10.0, 1.5), direction=(0.0, 1.0, 0.0)):
+    """n slots on a line: slot k at origin + k * pitch * direction (direction is normalised). Returns [n][3]. The formations are the
+    project's own scenario class: places to fill, handed to agents by SwarmShard.assign / DeviceSwarm.assign / swarm.fly_formations."""
+    d = np.asarray(direction, dtype=np.float64).reshape(3)
+    d = d / np.linalg.norm(d)
+    return np.asarray(origin, dtype=np.float64).reshape(1, 3) + pitch * np.arange(n)[:, None] * d[None, :]
+
+
+def circle_formation(n, radius=None, centre=(18.0, 15.0, 1.5), pitch=2.0):
+    """n slots on a horizontal circle round `centre`, slot k at the angle 2 pi k / n; radius None: the one whose chord between
+    neighbours is `pitch`. Returns [n][3]."""
+    if radius is None:
+        radius = pitch / (2.0 * np.sin(np.pi / n)) if n > 1 else 0.0
+    ang = 2.0 * np.pi * np.arange(n) / max(n, 1)
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    return np.stack([c[0] + radius * np.cos(ang), c[1] + radius * np.sin(ang), np.full(n, c[2])], axis=1)
+
+
+def grid_formation(n, pitch=2.0, origin=(10.0, 10.0, 1.5), columns=None):
+    """n slots on a horizontal grid of `columns` columns along x (None: ceil(sqrt(n))), filled row by row along y; the last row may
+    be short. Returns [n][3]."""
+    columns = int(np.ceil(np.sqrt(n))) if columns is None else int(columns)
+    k = np.arange(n)
+    o = np.asarray(origin, dtype=np.float64).reshape(3)
+    return np.stack([o[0] + pitch * (k % max(columns, 1)), o[1] + pitch * (k // max(columns, 1)), np.full(n, o[2])], axis=1)
+
+
 def lattice_scenario(n_y, n_z=1, pitch=2.01, length=96.01, x0=0.0, y0=5.0, z0=0.0):
     """multi_agent_planner_long.launch.py:36-42: start_i = (0, 5 + 2.01 i, 0), goal_i = start_i + (96.01, 0, 0); rows of
     the same line stacked in z with the same pitch for swarms larger than one line (agent index = j * n_y + i)."""

@@ -16,6 +16,7 @@ import numpy as np
 from . import lib as _lib
 from .lib import _f64, _i8, _i32, _stream, _u8, call
 from .params import K_P_YAW, YAW_IDX, HdsmParams, MissionSummary, SwarmConfig  # noqa: F401  (SwarmConfig: the struct mirrors live in params.py)
+from .scenarios import circle_formation, grid_formation, line_formation  # noqa: F401
 from .scenarios import circle_scenario, lane_forest_scenario, lattice_scenario, repeat_scenario, shuttle_mission, square_mission  # noqa: F401  (scenario geometry lives in scenarios.py)
 
 
@@ -37,6 +38,37 @@ def _box(values, lo):
     vals = _i8(values)
     assert vals.ndim == 3
     return vals, np.asarray(lo, dtype=np.int32), np.asarray(vals.shape[::-1], dtype=np.int32)
+
+
+def _assign_call(fn, handle, n_local, group_start, slots, apply, setting):
+    """hdsm_swarm_assign / hdsm_dswarm_assign: (slot_of int32 [n_local], stats lib.ASSIGN_STATS, one record per group)"""
+    slots = _f64(slots).reshape(-1, 3)
+    if slots.shape[0] != n_local:
+        raise _lib.HdsmError(_lib.HDSM_ERR_BAD_ARG, "assign: slots [n_local][3] expected")
+    slot_of = np.full(n_local, -1, np.int32)
+    stats = np.zeros(1 if group_start is None else len(group_start) - 1, _lib.ASSIGN_STATS)
+    call(fn, handle, setting, slots, 1 if apply else 0, slot_of, stats)
+    return slot_of, stats
+
+
+def fly_formations(dsw, formations, mission_setting=None, max_rounds=400, check_every=4):
+    """Fly a DeviceSwarm through formations (each [n_local][3], scenarios.*_formation) one after the other: assign(apply=False) on the
+    states as they stand on the device, a one-waypoint mission on slots[slot_of] (an agent without a slot — the scripted tail — gets
+    its own slot, which nobody flies), and fly() until every flown agent has arrived or max_rounds. mission_setting: params.Mission
+    with n_wp = 1 (None: scenarios.mission_setting(1)). Returns (the summaries, the assignments slot_of) per formation. Built from
+    the existing entries only."""
+    from .scenarios import mission_setting as _mission_setting
+    setting = _mission_setting(1) if mission_setting is None else mission_setting
+    summaries, assignments = [], []
+    for slots in formations:
+        slots = _f64(slots).reshape(-1, 3)
+        slot_of, _ = dsw.assign(slots, apply=False)
+        take = np.where(slot_of >= 0, slot_of, np.arange(len(slot_of)))
+        dsw.set_mission(setting, slots[take][:, None, :])
+        rounds, summary = dsw.fly(max_rounds, check_every=check_every)
+        summaries.append(dict(summary, rounds=rounds))
+        assignments.append(slot_of)
+    return summaries, assignments
 
 
 class SwarmShard:
@@ -270,6 +302,13 @@ class SwarmShard:
         due, goals = np.zeros(self.n_local, np.uint8), np.zeros((self.n_local, 3))
         call("hdsm_swarm_mission_due", self.h, due, goals)
         return due, goals
+
+    # ---- formations (include/hdsm_swarm.h) ----
+    def assign(self, slots, apply=True, setting=None):
+        """hdsm_swarm_assign: which agent takes which of slots [n_local][3] (lib.assign on state_curr, in the shard's neighbour
+        groups). apply: the permuted slots become the goals, exactly as set_goals would set them (refused while a mission is on).
+        Returns (slot_of int32 [n_local], stats: one lib.ASSIGN_STATS record per group). One rank only."""
+        return _assign_call("hdsm_swarm_assign", self.h, self.n_local, getattr(self, "group_start", None), slots, apply, setting)
 
     def state(self):
         pos = np.zeros((self.n_local, 3))
@@ -681,6 +720,15 @@ class DeviceSwarm:
         rounds, last = C.c_int32(0), MissionSummary()
         call("hdsm_dswarm_fly", self.h, _stream(stream), int(max_rounds), int(check_every), 1 if stop_on_stall else 0, C.byref(rounds), C.byref(last))
         return rounds.value, last.as_dict()
+
+    # ---- formations (include/hdsm_swarm.h) ----
+    def assign(self, slots, apply=True, setting=None):
+        """hdsm_dswarm_assign: which flown agent takes which of slots [n_local][3] — k_assign on state_curr where it lives, one
+        workgroup per neighbour group; no state is downloaded. The scripted tail keeps -1. apply: the permuted slots become the goals
+        through set_goals (refused while a mission is on). Returns (slot_of int32 [n_local], stats: one lib.ASSIGN_STATS record per
+        group). A set-up call: it synchronises. One rank only."""
+        return _assign_call("hdsm_dswarm_assign", self.h, self.shard.n_local, getattr(self.shard, "group_start", None) if self.n_groups > 1 else None,
+                            slots, apply, setting)
 
     def set_audit(self, on=True, sep_warn=1.0):
         """hdsm_dswarm_set_audit: the flight audit at the end of every round (k_audit_pack, k_audit, k_audit_track); synchronises."""
